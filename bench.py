@@ -2,6 +2,7 @@
 """Throughput benchmark of the MedMoE contrastive training step on MI355X.
 
   python bench.py --gpus N --steps K --warmup W [--config cfg2|cfg1|cfg0|cfg3|cfg4|tiny] [--global-batch G]
+                  [--dump-outputs DIR] [--full]
 
 One process per GPU (for N>1 launch through torch.distributed.run; RANK/LOCAL_RANK/WORLD_SIZE
 are read from the env).  A "step" is one full optimisation step of the hot path on one synthetic
@@ -9,7 +10,15 @@ batch already resident in HBM: ViT + frozen text tower + MoE forward, GLoRIA loc
 router-CE losses, full backward, gradient all-reduce (N>1), global-norm clip + Adam.
 Default workload = the configuration BASELINE.json's metric is quoted on: ViT-B/16 + 12-layer
 text tower, 8 experts top-2 (configs[2]) at GLOBAL batch 1024, split evenly over the N ranks
-(strong scaling; per-rank batch 1024/N).  Rank 0 prints ONE JSON line.
+(strong scaling; per-rank batch 1024/N).  Every warm-up and timed step starts from the same parameters and
+optimiser state (StepStart, restored outside the timed span: each step is timed by HIP events on the launch stream),
+so a step computes the same from run to run.
+Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (`roofline` null).  --full adds the secondary
+measurements: one extra step with HIP events around every launch (`roofline`), the Hydra-built LightningModule's fused
+step (`module_path`, --path both) and the CPU oracle (`cpu_baseline`, one GPU, unless --no-cpu-baseline).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -189,7 +198,7 @@ def bench_ref_swin(args, world, local_rank):
         return dt / args.steps, float(loss.detach())
 
     res_mod = None
-    if args.path in ("module", "both"):
+    if args.path == "module" or (args.path == "both" and args.full):
         hc, lit, mb = build(False)
         params = [p for p in lit.parameters() if p.requires_grad]
         opt = torch.optim.Adam(params, lr=float(hc.model.optimizer.lr), weight_decay=float(hc.model.optimizer.weight_decay), fused=True)
@@ -225,7 +234,7 @@ def bench_ref_swin(args, world, local_rank):
                        "global_batch": B * world, "per_gpu_batch": B, "parallelism": f"dp{world}", "loss": loss,
                        "trainable_parameters_m": n_par, "hbm_peak_gb": torch.cuda.max_memory_allocated() / 1e9},
            "roofline": None, "note": "secondary workload (BASELINE.md section 4); the BASELINE.json configs name ViT towers"}
-    if res_mod is not None and args.path == "both":
+    if res_mod is not None and args.path == "both":         # timed beside the engine with --full
         res["module_path"] = res_mod
     if rank == 0:
         print(json.dumps(res), flush=True)
@@ -299,6 +308,64 @@ def cpu_baseline(cfg_name):
     return res
 
 
+DUMP_SAMPLE = 1 << 20          # elements kept of a larger output: a fixed, seeded sample (sorted flat indices)
+
+
+def _dump_array(t):
+    """fp64 stays fp64, everything else becomes fp32; outputs over DUMP_SAMPLE elements are cut to a fixed sample of their flat
+    (row-major) elements, the same for every run of the same shape."""
+    t = t.detach()
+    dt = torch.float64 if t.dtype == torch.float64 else torch.float32
+    if t.numel() <= DUMP_SAMPLE:
+        return t.to(dt).cpu().numpy(), False
+    g = torch.Generator().manual_seed(0)
+    idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+    return t.reshape(-1)[idx.to(t.device)].to(dt).cpu().numpy(), True
+
+
+def dump_outputs(path, arrays):
+    """arrays: name -> tensor.  Writes DIR/<name>.npy (DIR/<name>_sample.npy for a sampled output)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        a, sampled = _dump_array(t)
+        np.save(os.path.join(path, f"{name}_sample.npy" if sampled else f"{name}.npy"), a)
+
+
+def engine_outputs(eng, out):
+    """What a caller of Engine.train_step receives from the last step: the reported losses, the model outputs of the step in the
+    reference layout (Engine.outputs) and the parameter gradients, in name order (the reference's names, not a buffer layout)."""
+    res = {k: v.double() for k, v in out.items()}
+    for k, v in eng.outputs().items():
+        res[k] = v if torch.is_tensor(v) else torch.as_tensor(v)
+    res["grads"] = torch.cat([v.reshape(-1) for _, v in sorted(eng.params.named_views(eng.params.g32).items())])
+    return res
+
+
+class StepStart:
+    """What a training step changes in the engine's parameter stores - fp32 masters, Adam moments and step counts, bf16 and e4m3
+    working copies - saved once on the device and copied back in place on the launch stream (graph-captured addresses stay valid) before
+    every warm-up and timed step, so that every step starts from the same state and the last timed step computes the same outputs on
+    every run with the same arguments.  Chained steps would not: Adam's first updates are sign-like, gradient signs at rounding level flip
+    between runs (the weight gradients meet in fp32 atomics), and within three steps every output has moved."""
+    NAMES = ("p32", "m", "v", "p16", "p16t")
+
+    def __init__(self, eng):
+        self.saved = []
+        for st in (eng.params, getattr(eng, "tstore", None)):
+            if st is None:
+                continue
+            ts = [getattr(st, n) for n in self.NAMES] + [t for q in getattr(st, "fp8", {}).values() for t in q]
+            self.saved.append((st, st.step_count, [(t, t.clone()) for t in ts]))
+        self.nbytes = sum(c.numel() * c.element_size() for _, _, pairs in self.saved for _, c in pairs)
+
+    def restore(self):
+        for st, count, pairs in self.saved:
+            st.step_count = count
+            for t, c in pairs:
+                t.copy_(c)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -311,9 +378,19 @@ def main():
                     help="cfg.freeze_text = False: the text tower trains too (reference freeze_bert: false; SURVEY 8(d) column 'train (full)') - "
                          "NOT the BASELINE metric's workload, which freezes it as the reference experiment does")
     ap.add_argument("--path", default="both", choices=["engine", "module", "both"],
-                    help="engine: Engine.train_step only; module / both (default): also time the Hydra-built LightningModule's fused training_step "
-                         "and report it as the secondary field `module_path`")
+                    help="engine: Engine.train_step only; module / both (default): with --full also time the Hydra-built LightningModule's fused "
+                         "training_step and report it as the secondary field `module_path` (--config ref_swin --path module: the module path is the "
+                         "headline)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary measurements: the per-launch profiled step (`roofline`), `module_path` and `cpu_baseline`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed as DIR/<name>.npy (fp32 / fp64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.config == "ref_swin":
+        raise SystemExit("--dump-outputs: not for --config ref_swin (stochastic depth draws new masks every step, so its steps do not "
+                         "repeat from run to run)")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -358,34 +435,45 @@ def main():
             torch.distributed.barrier()
         torch.cuda.synchronize()
 
+    start = StepStart(eng)
     for _ in range(args.warmup):
+        start.restore()
         eng.train_step(batch)
     sync()
-    t0 = time.perf_counter()
+    spans = []
     for it in range(args.steps):
-        out = eng.train_step(batch)
+        start.restore()                                              # before the step's start event: outside the timed span
+        ev0 = torch.cuda.Event(enable_timing=True); ev0.record()
+        out = eng.train_step(batch)                                  # ends on the launch stream (the second stream joins before Adam)
+        ev1 = torch.cuda.Event(enable_timing=True); ev1.record()
+        spans.append((ev0, ev1))
     sync()
-    dt = time.perf_counter() - t0
+    dt = sum(a.elapsed_time(b) for a, b in spans) * 1e-3
     tmax = torch.tensor([dt], device=eng.device)
     if world > 1:
         torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
     dt = float(tmax.item())
     loss = float(out["loss"])
+    hbm_peak = torch.cuda.max_memory_allocated() - start.nbytes        # the step's own peak: the snapshot is not part of the workload
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, engine_outputs(eng, out))
 
-    # ONE more step, outside the timed region, with HIP events around every launch (on the stream the launch goes to): per-kernel
-    # durations for the roofline fields.  Every rank runs it (the step holds collectives); rank 0 reports.
     prof = []
     mean_tokens = float(batch["attn_mask"].float().sum(1).mean()) if getattr(eng, "text_varlen", False) else None
-    ops.ROWS_HINT = int(batch["attn_mask"].sum()) if mean_tokens is not None else 0
-    ops.PROFILE = prof
-    eng.train_step(batch)
-    sync()
-    ops.PROFILE = None
+    if args.full:
+        # ONE more step, outside the timed region, with HIP events around every launch (on the stream the launch goes to): per-kernel
+        # durations for the roofline fields.  Every rank runs it (the step holds collectives); rank 0 reports.
+        ops.ROWS_HINT = int(batch["attn_mask"].sum()) if mean_tokens is not None else 0
+        ops.PROFILE = prof
+        start.restore()
+        eng.train_step(batch)
+        sync()
+        ops.PROFILE = None
 
     # the drop-in path: the reference-named LightningModule built from the Hydra tree in its fused mode (model.fused_step: true), same
     # workload, same number of steps - a secondary field; `value` above stays the engine's own number
     module_path = None
-    if args.path in ("module", "both") and args.config in ("cfg1", "cfg2", "cfg3", "cfg4") and cfg.freeze_text:
+    if args.full and args.path in ("module", "both") and args.config in ("cfg1", "cfg2", "cfg3", "cfg4") and cfg.freeze_text:
         try:
             del eng
             eng = None
@@ -396,24 +484,6 @@ def main():
 
     if rank == 0:
         pairs_per_s = gb * args.steps / dt
-        mean_words = float(cap_lens_of(batch, cfg))                  # words per caption of this batch (after timing)
-        fpp = flops_per_pair(cfg, B, mean_words, mean_tokens, not cfg.freeze_text)
-        fpp_max = flops_per_pair(cfg, B, train_text=not cfg.freeze_text)
-        step_tflops = pairs_per_s * fpp / 1e12 / world
-        rows, kernels = kernel_table(prof)
-        dom = "gemm_nt4w_kernel"
-        d_n, d_ms, d_flop, d_bytes = 0, 0.0, 0.0, 0.0
-        fam_ms, fam_flop = 0.0, 0.0
-        for label, work, unit, ev0, ev1, detail in prof:
-            if label.startswith("gemm_nt") and not label.startswith("gemm_tn") and work is not None:
-                fam_ms += ev0.elapsed_time(ev1); fam_flop += work
-            if label == dom and work is not None:
-                d_n += 1; d_ms += ev0.elapsed_time(ev1); d_flop += work
-                if detail and detail[0] == "nt":
-                    d_bytes += detail[5]
-        gemm_tf = d_flop / (d_ms * 1e-3) / 1e12 if d_ms > 0 else 0.0
-        fam_tf = fam_flop / (fam_ms * 1e-3) / 1e12 if fam_ms > 0 else 0.0
-        tr = traffic_from_profile(args.config, gb, world)
         step_ms = dt / args.steps * 1e3
         res = {
             "metric": "image-text pairs/sec at global batch 1024" if gb == 1024 else f"image-text pairs/sec at global batch {gb}",
@@ -423,38 +493,58 @@ def main():
             "config": {"workload": f"{args.config}: ViT-{ {768: 'B', 1024: 'L'}.get(cfg.d_v, cfg.d_v) }/{cfg.patch} + {cfg.n_layer_t}-layer text tower ({'frozen' if cfg.freeze_text else 'TRAINED - not the BASELINE workload'}), "
                                    f"{cfg.n_expert} experts top-{cfg.top_k}{' fp8 expert weights' if cfg.expert_fp8 else ''}, {cfg.img_size}x{cfg.img_size}x3 + {cfg.max_len} tokens, fwd+bwd+clip+Adam",
                        "global_batch": gb, "per_gpu_batch": B, "parallelism": f"dp{world}", "loss": loss,
-                       "hbm_peak_gb": torch.cuda.max_memory_allocated() / 1e9},
-            "roofline": {"bound": "mfma",
-                         "kernel": "gemm_nt4w_kernel (the 256x256-tile, four-wave NT GEMM: every Linear forward / dgrad of the ViT tower and the "
-                                   "packed text tower, the local-loss dC; plain build - the GROUPED expert build is listed separately)",
-                         "achieved": gemm_tf, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": gemm_tf / PEAK_BF16_TFLOPS,
-                         "traffic": tr["bytes_per_launch"] if tr else None,
-                         "traffic_source": (f"{tr['file']} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command on the committed tree, FETCH "
-                                            f"doubled per the gfx950 note; kernel {tr['kernel']}; the algorithmic bytes of the same launches are "
-                                            f"the next field)") if tr else None,
-                         "algorithmic_bytes_per_launch": d_bytes / max(1, d_n),
-                         "launches": d_n, "avg_launch_ms": d_ms / max(1, d_n), "share_of_step": d_ms / step_ms if step_ms > 0 else None,
-                         "events": "HIP events on the launch stream around every launch of ONE extra step after the timed region "
-                                   "(at per-rank batches <= 512 the second stream's kernels share the chip: durations include that sharing)",
-                         "nt_family": {"kernels": "gemm_nt4w_kernel + GROUPED build + gemm_nt256_kernel + gemm_nt_kernel (every medmoe_gemm_nt launch)",
-                                       "achieved": fam_tf, "frac": fam_tf / PEAK_BF16_TFLOPS, "ms_per_step": fam_ms},
-                         "kernels": kernels,
-                         "profiled_step_ms": sum(r[1][1] for r in rows),
-                         "whole_step": {"algorithmic_gflop_per_pair": fpp / 1e9, "achieved": step_tflops,
-                                        "frac": step_tflops / PEAK_BF16_TFLOPS, "mean_words_per_caption": mean_words,
-                                        "mean_text_tokens_per_caption": mean_tokens,
-                                        "algorithmic_gflop_per_pair_at_max_len": fpp_max / 1e9,
-                                        "frac_at_max_len": pairs_per_s * fpp_max / 1e12 / world / PEAK_BF16_TFLOPS,
-                                        "note": "local-loss flops counted at each caption's own length, as the reference computes them "
-                                                "(losses.py:985), and the text tower at the captions' own token counts (it runs on the packed "
-                                                "non-padding tokens; MEDMOE_TEXT_VARLEN=0 computes all positions); the *_at_max_len fields are "
-                                                "the SURVEY 8d table's upper bound with every caption and every text position at max_len"}},
+                       "hbm_peak_gb": hbm_peak / 1e9},
+            "roofline": None,
         }
+        if args.full:
+            mean_words = float(cap_lens_of(batch, cfg))                  # words per caption of this batch (after timing)
+            fpp = flops_per_pair(cfg, B, mean_words, mean_tokens, not cfg.freeze_text)
+            fpp_max = flops_per_pair(cfg, B, train_text=not cfg.freeze_text)
+            step_tflops = pairs_per_s * fpp / 1e12 / world
+            rows, kernels = kernel_table(prof)
+            dom = "gemm_nt4w_kernel"
+            d_n, d_ms, d_flop, d_bytes = 0, 0.0, 0.0, 0.0
+            fam_ms, fam_flop = 0.0, 0.0
+            for label, work, unit, ev0, ev1, detail in prof:
+                if label.startswith("gemm_nt") and not label.startswith("gemm_tn") and work is not None:
+                    fam_ms += ev0.elapsed_time(ev1); fam_flop += work
+                if label == dom and work is not None:
+                    d_n += 1; d_ms += ev0.elapsed_time(ev1); d_flop += work
+                    if detail and detail[0] == "nt":
+                        d_bytes += detail[5]
+            gemm_tf = d_flop / (d_ms * 1e-3) / 1e12 if d_ms > 0 else 0.0
+            fam_tf = fam_flop / (fam_ms * 1e-3) / 1e12 if fam_ms > 0 else 0.0
+            tr = traffic_from_profile(args.config, gb, world)
+            res["roofline"] = {"bound": "mfma",
+                               "kernel": "gemm_nt4w_kernel (the 256x256-tile, four-wave NT GEMM: every Linear forward / dgrad of the ViT tower and the "
+                                         "packed text tower, the local-loss dC; plain build - the GROUPED expert build is listed separately)",
+                               "achieved": gemm_tf, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": gemm_tf / PEAK_BF16_TFLOPS,
+                               "traffic": tr["bytes_per_launch"] if tr else None,
+                               "traffic_source": (f"{tr['file']} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command on the committed tree, FETCH "
+                                                  f"doubled per the gfx950 note; kernel {tr['kernel']}; the algorithmic bytes of the same launches are "
+                                                  f"the next field)") if tr else None,
+                               "algorithmic_bytes_per_launch": d_bytes / max(1, d_n),
+                               "launches": d_n, "avg_launch_ms": d_ms / max(1, d_n), "share_of_step": d_ms / step_ms if step_ms > 0 else None,
+                               "events": "HIP events on the launch stream around every launch of ONE extra step after the timed region "
+                                         "(at per-rank batches <= 512 the second stream's kernels share the chip: durations include that sharing)",
+                               "nt_family": {"kernels": "gemm_nt4w_kernel + GROUPED build + gemm_nt256_kernel + gemm_nt_kernel (every medmoe_gemm_nt launch)",
+                                             "achieved": fam_tf, "frac": fam_tf / PEAK_BF16_TFLOPS, "ms_per_step": fam_ms},
+                               "kernels": kernels,
+                               "profiled_step_ms": sum(r[1][1] for r in rows),
+                               "whole_step": {"algorithmic_gflop_per_pair": fpp / 1e9, "achieved": step_tflops,
+                                              "frac": step_tflops / PEAK_BF16_TFLOPS, "mean_words_per_caption": mean_words,
+                                              "mean_text_tokens_per_caption": mean_tokens,
+                                              "algorithmic_gflop_per_pair_at_max_len": fpp_max / 1e9,
+                                              "frac_at_max_len": pairs_per_s * fpp_max / 1e12 / world / PEAK_BF16_TFLOPS,
+                                              "note": "local-loss flops counted at each caption's own length, as the reference computes them "
+                                                      "(losses.py:985), and the text tower at the captions' own token counts (it runs on the packed "
+                                                      "non-padding tokens; MEDMOE_TEXT_VARLEN=0 computes all positions); the *_at_max_len fields are "
+                                                      "the SURVEY 8d table's upper bound with every caption and every text position at max_len"}}
         if module_path is not None:
             if "ms_per_step" in module_path:
                 module_path["vs_engine"] = module_path["ms_per_step"] / step_ms
             res["module_path"] = module_path
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             eng = None
             torch.cuda.empty_cache()
             res["cpu_baseline"] = cpu_baseline(args.config)

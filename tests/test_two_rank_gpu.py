@@ -35,12 +35,13 @@ def test_two_ranks_with_the_globalised_local_loss_equal_one_process_on_the_conca
 
 @pytest.mark.gpu
 def test_bench_two_rank_rehearsal_prints_the_contract_line():
-    """bench.py through torch.distributed.run with two ranks on the one GPU (MEDMOE_DIST_BACKEND=gloo): rank 0 prints ONE
-    JSON line with the contract's keys, n_gpus = 2, strong scaling (per-rank batch halves)."""
+    """bench.py --full through torch.distributed.run with two ranks on the one GPU (MEDMOE_DIST_BACKEND=gloo): rank 0 prints ONE
+    JSON line with the contract's keys and the profiled step's roofline, n_gpus = 2, strong scaling (per-rank batch halves)."""
     import json
     env = dict(os.environ, MEDMOE_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29563", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--config", "tiny"]
+           "--master-port", "29563", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--config", "tiny",
+           "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -50,7 +51,7 @@ def test_bench_two_rank_rehearsal_prints_the_contract_line():
               "dtype", "data", "config", "roofline"):
         assert k in d, k
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["config"]["per_gpu_batch"] * 2 == d["config"]["global_batch"]
-    assert d["value"] > 0 and "cpu_baseline" not in d
+    assert d["value"] > 0 and "cpu_baseline" not in d and d["roofline"]["kernels"]
 
 
 @pytest.mark.gpu
