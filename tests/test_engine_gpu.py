@@ -182,8 +182,8 @@ def test_gradients(cfg_name):
     ref["loss"].backward()
     eng.train_step(to_dev(batch), optimizer=False)
     torch.cuda.synchronize()
-    if not torch.equal(eng.outputs()["idx"].cpu().long(), ref["idx"]):
-        pytest.skip("near-tie routing differs between bf16 and fp32 towers on this seed")
+    # seed 3 is chosen to keep every sample's routing away from near-ties between the bf16 and the fp32 tower
+    assert torch.equal(eng.outputs()["idx"].cpu().long(), ref["idx"]), "routing differs between the bf16 and the fp32 tower"
     if cfg_name == "tinyL336":
         assert len({tuple(sorted(r.tolist())) for r in ref["idx"]}) >= 2, ref["idx"]
     got = eng.params.export_named(eng.params.g32)
