@@ -198,6 +198,9 @@ int medmoe_local_fast_path(int HW, int T);
 int medmoe_local_gen_fwd_a(const void* lp, const int* cap_lens, void* A, int B, int Bc, int HW, int HWp, int T, int Tp, float temp1, long long ldp, hipStream_t stream);
 int medmoe_local_gen_cos(const float* wc, const void* words, const float* wnorm, const int* cap_lens, float* sim, float* stats, float* sume, int B, int Bc, int T, int Tp, int D, float temp2, float eps, long long Kp, hipStream_t stream);
 int medmoe_local_gen_dwctx(const float* wc, const void* words, const float* wnorm, const int* cap_lens, const float* gsim, const float* stats, const float* sume, void* dwc, int B, int Bc, int T, int Tp, int D, float temp2, float eps, long long Kp, hipStream_t stream);
+/* d loss / d words of the generic-geometry local loss (trainable text tower), fp32 [Bc][T][D]: dws (fp32 [Kp][D] = dS^T ctx, the path through
+   the word-softmax scores; NULL: none) + the cosine term summed over the B images in a fixed order; words t >= cap_lens[i] exactly 0 */
+int medmoe_local_gen_dwords(const float* wc, const void* words, const float* wnorm, const int* cap_lens, const float* gsim, const float* stats, const float* sume, const float* dws, float* d_words, int B, int Bc, int T, int Tp, int D, float temp2, float eps, long long Kp, hipStream_t stream);
 int medmoe_local_gen_bwd_s(const void* lp, const void* A, void* dA_io, const int* cap_lens, int B, int Bc, int HW, int HWp, int T, int Tp, float temp1, long long ldp, hipStream_t stream);
 int medmoe_unpad_cast2(const float* src, const float* src2, void* dst, int B, int HW, int HWp, int D, hipStream_t stream);
 

@@ -1574,6 +1574,95 @@ extern "C" int medmoe_local_gen_dwctx(const float* wc, const void* words, const 
   return mm_check_launch();
 }
 
+// d words (trainable text tower): word k = (caption i, word t), column i*Tp + t of every pair matrix.
+//   d w_k = dWS[k] + sum_b kc_b c_{b,k} + (sum_b kw_b) w_k
+// dWS = dS^T ctx (the path through the word-softmax scores, one wgrad-shaped GEMM by the caller, may be null), and the cosine term of
+// local_gen_dwctx_kernel seen from the word: d cos / d w = c / (|w||c|) - cos w / |w|^2, so kc = dcos / den and kw = -dcos cos / |w|^2
+// (den < eps: the clamped denominator has no |w| path, kc = dcos / eps, kw = 0).  One wave per word, NC float4 of the word per lane; the
+// sum over images runs in the order b = 0, 1, ... (each lane computes the scalars of one image, broadcast by shuffles): no atomics, the
+// result does not depend on the schedule.  Words t >= cap_lens[i] are written as exact zeros.
+template <int NC>
+__global__ __launch_bounds__(256) void local_gen_dwords_kernel(const float* __restrict__ wc, const bf16_t* __restrict__ words,
+                                                               const float* __restrict__ wnorm, const int* __restrict__ cap_lens,
+                                                               const float* __restrict__ gsim, const float4* __restrict__ stats,
+                                                               const float* __restrict__ sume, const float* __restrict__ dws,
+                                                               float* __restrict__ out, int B, int Bc, int T, int Tp, int D, float temp2,
+                                                               float eps, long long Kp) {
+  const int lane = threadIdx.x & 63;
+  const int wrow = blockIdx.x * 4 + (threadIdx.x >> 6);             // i * T + t
+  if (wrow >= Bc * T) return;
+  const int i = wrow / T, t = wrow - i * T;
+  const int cap = max(1, min(min(cap_lens[i], T), Tp));
+  const int D4 = D >> 2;
+  float4* orow = (float4*)(out + (long long)wrow * D);
+  if (t >= cap) {
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+      if (lane + 64 * c < D4) orow[lane + 64 * c] = make_float4(0.f, 0.f, 0.f, 0.f);
+    return;
+  }
+  const long long col = (long long)i * Tp + t;
+  const float nw = wnorm[wrow];
+  float4 acc[NC];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    const int d4 = lane + 64 * c;
+    acc[c] = (dws && d4 < D4) ? ((const float4*)(dws + col * D))[d4] : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  float kwsum = 0.f;
+  for (int b0 = 0; b0 < B; b0 += 64) {
+    const int b = b0 + lane;
+    float kc = 0.f, kw = 0.f;
+    if (b < B) {
+      const float4 st = stats[(long long)b * Kp + col];                  // cos, n2, e
+      const float dcos = gsim[(long long)b * Bc + i] * temp2 * st.z / sume[(long long)b * Bc + i];
+      const float den = nw * sqrtf(fmaxf(st.y, 0.f));
+      if (den >= eps) { kc = dcos / den; kw = -dcos * st.x / (nw * nw); }
+      else { kc = dcos / eps; }
+    }
+    const int nb = min(64, B - b0);
+#pragma unroll 4
+    for (int j = 0; j < nb; ++j) {
+      const float k = __shfl(kc, j, 64);
+      const float4* cr = (const float4*)(wc + ((long long)(b0 + j) * Kp + col) * D);
+#pragma unroll
+      for (int c = 0; c < NC; ++c) {
+        const int d4 = lane + 64 * c;
+        if (d4 < D4) {
+          const float4 v = cr[d4];
+          acc[c].x += k * v.x; acc[c].y += k * v.y; acc[c].z += k * v.z; acc[c].w += k * v.w;
+        }
+      }
+    }
+    kwsum += wave_sum(kw);
+  }
+  const bf16_t* wr = words + (long long)wrow * D;
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    const int d4 = lane + 64 * c;
+    if (d4 < D4) {
+      const uint2 w = *(const uint2*)(wr + 4 * d4);
+      float4 o = acc[c];
+      o.x += kwsum * __uint_as_float(w.x << 16); o.y += kwsum * __uint_as_float(w.x & 0xffff0000u);
+      o.z += kwsum * __uint_as_float(w.y << 16); o.w += kwsum * __uint_as_float(w.y & 0xffff0000u);
+      orow[d4] = o;
+    }
+  }
+}
+
+extern "C" int medmoe_local_gen_dwords(const float* wc, const void* words, const float* wnorm, const int* cap_lens, const float* gsim,
+                                       const float* stats, const float* sume, const float* dws, float* d_words, int B, int Bc, int T, int Tp,
+                                       int D, float temp2, float eps, long long Kp, hipStream_t stream) {
+  if (!wc || !words || !wnorm || !cap_lens || !gsim || !stats || !sume || !d_words) return MM_ERR_ARG;
+  if (B <= 0 || Bc <= 0 || T <= 0 || Tp < T || Tp > 80 || D <= 0 || (D % 4) || D > 1024 || Kp < (long long)Bc * Tp) return MM_ERR_SHAPE;
+  const int grid = (Bc * T + 3) / 4;
+#define LG_DW(N) hipLaunchKernelGGL(local_gen_dwords_kernel<N>, dim3(grid), dim3(256), 0, stream, wc, (const bf16_t*)words, wnorm, cap_lens, gsim, (const float4*)stats, sume, dws, d_words, B, Bc, T, Tp, D, temp2, eps, Kp)
+  const int nc = (D / 4 + 63) / 64;
+  switch (nc) { case 1: LG_DW(1); break; case 2: LG_DW(2); break; case 3: LG_DW(3); break; default: LG_DW(4); break; }
+#undef LG_DW
+  return mm_check_launch();
+}
+
 // dS (written over dA in place): region-softmax backward (column sums over hw), then word-softmax backward (row sums over t).
 // The lane layout of local_gen_fwd_a_kernel: the column sums meet by xor shuffles over the rows of a wave and in LDS over the waves, the
 // row sum is a shuffle reduction over the 1 << LP pieces of the row.

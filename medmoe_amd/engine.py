@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .local_generic import GenericLocalLoss
 from .local_transposed import TransposedLocalLoss, ragged_layout  # noqa: F401  (ragged_layout: the [region][word] path and the tests use it from here)
 from .config import MedMoEConfig
 from .params import ParamStore
@@ -111,6 +112,7 @@ class Engine:
             self.tstore = TextStore(cfg, self.device, self.params.text)
             self.params.text = self.tstore.as_dict()             # views of the flat buffers: an optimiser step updates them in place
         self._tlw = None                                             # TransposedLocalLoss in word-gradient mode (own buffers)
+        self._glw = None                                             # GenericLocalLoss in word-gradient mode (other geometries)
         self.local_dense = False
         self.HWp, self.Tp, self.GW = ops.local_geometry(cfg.n_patch, cfg.max_len)
         # LDS-tiled pair kernels exist for 64 / 208 / 256 regions; any other geometry (576 regions of ViT-L/14 at 336 px) runs
@@ -659,10 +661,12 @@ class Engine:
         ctx = ws["img_l"].view(B * P, Do)
         self._d_words = None
         if self.train_text:
-            if not self.local_t or (self.dist and c.local_loss_global):
-                raise NotImplementedError("trainable text tower: the word gradient of the local loss is built for the 196- / 64-region "
-                                          "geometries (csrc/pair3.hip), rank-local captions")
-            return self._local_loss_transposed_words(loss_scale)
+            if self.dist and c.local_loss_global:
+                raise NotImplementedError("trainable text tower: the word gradient of the local loss is built for rank-local captions "
+                                          "(local_loss_global gathers them)")
+            if self.local_t:
+                return self._local_loss_transposed_words(loss_scale)
+            return self._local_loss_generic_words(loss_scale)
         if not self.local_fast:
             return self._local_loss_generic(loss_scale)
         if self.dist and c.local_loss_global:
@@ -742,6 +746,22 @@ class Engine:
         self._head(ws["sim"], ws["gsim"], B, 1, wl, 0, lp[3:])
         self._head(ws["sim"], ws["gsim"], 1, B, wl, 1, lp[3:])
         self._d_words = tl.backward(ws["gsim"], ws["d_img_l"])
+
+    def _local_loss_generic_words(self, loss_scale: float):
+        """The word-gradient loss at a geometry without the transposed pair kernels (576 / 256 regions, any other): `GenericLocalLoss` in its
+        word-gradient mode (own buffers; d words = dS^T ctx + the cosine term, medmoe_amd/local_generic.py)."""
+        c, ws, B = self.cfg, self.ws, self.B
+        lp = ws["loss_parts"]
+        if self._glw is None or self._glw.B != B:
+            self._glw = GenericLocalLoss(B, c.n_patch, c.max_len, c.d_out, self.device, word_grad=True)
+        gl = self._glw
+        sim = gl.forward(ws["img_l"].view(B * c.n_patch, c.d_out), ws["words"], self.cap_lens, c.temp1, c.temp2)
+        ws["sim"].copy_(sim)
+        wl = c.w_local * loss_scale / B
+        self._head(ws["sim"], ws["gsim"], B, 1, wl, 0, lp[3:])
+        self._head(ws["sim"], ws["gsim"], 1, B, wl, 1, lp[3:])
+        d_ctx, self._d_words = gl.backward(ws["gsim"])
+        ws["d_img_l"].view(B * c.n_patch, c.d_out).copy_(d_ctx)
 
     def _local_loss_global(self, loss_scale: float):
         """cfg.local_loss_global under data parallelism: this rank's images against the captions of every rank (the

@@ -2,7 +2,8 @@
 kernels hold 64 / 196 / 256 / 576): the reference's own formulation - weighted context = bmm(ctx, attn) (losses.py:732), cosine against the word
 (:690-695, :1002) - as grouped GEMMs over uniform pair matrices [B*HWp, B*Tp] plus four elementwise kernels (loss.hip "GENERIC-GEOMETRY").
 The same launch sequence as `Engine._local_loss_generic`, with its own buffers, so that `src.losses.GLORIALocalContrastiveLoss` can run it
-behind torch autograd for the Swin tower's 56 x 56 local features."""
+behind torch autograd for the Swin tower's 56 x 56 local features.  With `word_grad=True` the backward also differentiates the word
+embeddings (trainable text tower): the SwinEngine and the ViT Engine use it at geometries without the transposed pair kernels."""
 from typing import Optional
 
 import torch
@@ -13,7 +14,7 @@ BF, F32, I32 = torch.bfloat16, torch.float32, torch.int32
 
 
 class GenericLocalLoss:
-    def __init__(self, B: int, HW: int, T: int, D: int, device):
+    def __init__(self, B: int, HW: int, T: int, D: int, device, word_grad: bool = False):
         if T > 80 or D % 64:
             raise ValueError("GenericLocalLoss: at most 80 words per caption, embedding width a multiple of 64")
         dev = torch.device(device)
@@ -43,6 +44,17 @@ class GenericLocalLoss:
             self.dC32, self.dC32b = z(B * HWp, D, dt=F32), z(B * HWp, D, dt=F32)
         arp = torch.arange(B * HWp, device=dev)
         self.xmap = (arp // HWp * HW + torch.clamp(arp % HWp, max=HW - 1)).to(I32)
+        # word_grad: backward also returns d loss / d words (losses.py:985-1012 differentiates the word embeddings too; the text tower trains).
+        # d words = dS^T ctx (through the word-softmax scores: one wgrad-shaped GEMM over all B*HWp region rows into dWS) + the cosine term
+        # (medmoe_local_gen_dwords, which reads WC once and adds dWS).  The GEMM runs in its staged form (partial tiles summed in a fixed
+        # order, no fp32 atomics) where the shape allows it: dense rows, Kp and D multiples of 256.
+        self.word_grad = word_grad
+        if word_grad:
+            self.dWS = z(Kp, D, dt=F32)
+            self.tn_scratch = None
+            if self.dense and Kp % 256 == 0 and D % 256 == 0 and B * HWp >= 4096:
+                ntile = (Kp // 256) * (D // 256)
+                self.tn_scratch = torch.empty(ntile * max(1, 256 // ntile) * 65536, device=dev, dtype=F32)
         self.generation = 0                                       # forward calls so far: a backward must belong to the latest one
 
     def forward(self, ctx16: torch.Tensor, words16: torch.Tensor, cap_lens: torch.Tensor, temp1: float, temp2: float) -> torch.Tensor:
@@ -74,14 +86,15 @@ class GenericLocalLoss:
         v = torch.as_strided(self.A, (B, T, HW), (HWp * Kp + Tp, 1, Kp))
         return v.float()
 
-    def backward(self, gsim: torch.Tensor, generation: Optional[int] = None) -> torch.Tensor:
-        """gsim fp32 [B, B] = dL/dsim -> d ctx bf16 [B*HW, D] (the text tower is frozen: no word gradient).  `generation`: the value of
-        self.generation right after the forward this backward belongs to - the pair matrices are consumed in place, a backward that arrives
-        after ANOTHER forward is refused."""
+    def backward(self, gsim: torch.Tensor, generation: Optional[int] = None):
+        """gsim fp32 [B, B] = dL/dsim -> d ctx bf16 [B*HW, D]; word_grad instances return (d ctx, d words fp32 [B, T, D]) - the word gradient
+        runs after d ctx and only reads, so d ctx is the same in both modes.  `generation`: the value of self.generation right after the
+        forward this backward belongs to - the pair matrices are consumed in place, a backward that arrives after ANOTHER forward is refused."""
         if generation is not None and generation != self.generation:
             raise RuntimeError("GenericLocalLoss: backward of an earlier forward - the instance keeps ONE forward's pair matrices")
         B, HW, T, D, HWp, Tp, Kp = self.B, self.HW, self.T, self.D, self.HWp, self.Tp, self.Kp
-        ops.call("local_gen_dwctx", self.WC, self.words, self.wn, self.cap, gsim.contiguous(), self.stats, self.sume, self.DWC, B, B, T, Tp, D,
+        gsim = gsim.contiguous()
+        ops.call("local_gen_dwctx", self.WC, self.words, self.wn, self.cap, gsim, self.stats, self.sume, self.DWC, B, B, T, Tp, D,
                  self.t2, 1e-8, Kp)
         ops.call("transpose_many", self.DWC, self.DWCt, self.trtab, B, ((Kp + 63) // 64) * ((D + 63) // 64))
         if self.dense:
@@ -91,7 +104,7 @@ class GenericLocalLoss:
             ops.call("local_gen_bwd_s", self.lp, self.A, self.dS, self.cap, B, B, HW, HWp, T, Tp, self.t1, Kp) # dS over dA in place
             dctx = torch.empty(B * HW, D, device=self.dev, dtype=BF)
             ops.gemm_nt(self.dS, self.wT, dctx, residual=self.X1)                                              # d ctx = dS . W + the direct part
-            return dctx
+            return (dctx, self._word_grad(gsim)) if self.word_grad else dctx
         grp = dict(tiles=self.tiles, tile_count=self.tile_count, max_tiles=self.tiles.shape[0], M=B * HWp)
         ops.gemm_nt(self.ctx, self.DWC, self.dS, a_rowmap=self.xmap, stride_b=Kp * D, N=Kp, **grp)            # dA_b = ctx_b dwctx_b^T
         ops.gemm_nt(self.A, self.DWCt, self.dC32b, stride_b=D * Kp, N=D, **grp)                                # d ctx_b (direct) = A_b dwctx_b
@@ -99,4 +112,19 @@ class GenericLocalLoss:
         ops.gemm_nt(self.dS, self.wT, self.dC32)                                                               # d ctx += dS . W
         dctx = torch.empty(B * HW, D, device=self.dev, dtype=BF)
         ops.call("unpad_cast2", self.dC32, self.dC32b, dctx, B, HW, HWp, D)
-        return dctx
+        return (dctx, self._word_grad(gsim)) if self.word_grad else dctx
+
+    def _word_grad(self, gsim: torch.Tensor) -> torch.Tensor:
+        """d loss / d words fp32 [B, T, D] from the pair matrices the backward left: dS (over dA) and WC / stats / sume of the forward."""
+        B, HW, T, D, HWp, Tp, Kp = self.B, self.HW, self.T, self.D, self.HWp, self.Tp, self.Kp
+        self.dWS.zero_()
+        if self.dense:
+            ops.gemm_tn(self.dS, self.ctx, self.dWS, M=B * HWp, scratch=self.tn_scratch)                      # dWS = dS^T ctx
+        else:
+            # local_gen_bwd_s writes every row < HWp of dS (exact zeros past HW), so the padded rows add nothing; their ctx operand rows
+            # are clamped to a real row through xmap
+            ops.gemm_tn(self.dS, self.ctx, self.dWS, x_rowmap=self.xmap, M=B * HWp)
+        d_words = torch.empty(B, T, D, device=self.dev, dtype=F32)
+        ops.call("local_gen_dwords", self.WC, self.words, self.wn, self.cap, gsim, self.stats, self.sume, self.dWS, d_words, B, B, T, Tp, D,
+                 self.t2, 1e-8, Kp)
+        return d_words

@@ -332,6 +332,7 @@ _SIGS = {
     "local_pair2_ragged": "pppppppppiiiifffpiill", "scale_blocks_ragged": "pppiiipl",
     "local_pair3": "ppppppppppppliiiifffpiilllip", "local_pair3_wgrad": "ppppppppppppliiiifffpiilllipp", "local_scores_t": "pppppiiiiipiilll", "gemm_tn_cols": "pipipiiiiilllil", "gemm_tn_gram": "piplipiiiill",
     "local_gen_fwd_a": "pppiiiiiifl", "local_gen_cos": "pppppppiiiiiffl", "local_gen_dwctx": "ppppppppiiiiiffl",
+    "local_gen_dwords": "pppppppppiiiiiffl",
     "local_gen_bwd_s": "ppppiiiiiifl", "unpad_cast2": "pppiiii",
     "quant_rows_e4m3": "pipppippii", "quant_weights_e4m3": "ppppiii", "gemm_fp8_grouped": "ppppppippppiiillli",
     "lerp_tokens_fwd": "ppiiii", "lerp_tokens_bwd": "pppiiii", "lerp_tokens_bwd2": "ppppiiii",

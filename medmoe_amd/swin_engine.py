@@ -2,12 +2,16 @@
 six pyramid experts over its four stages, 56 x 56 = 3136 local regions, frozen BERT-geometry text tower): medmoe_module.py:284-316 `model_step`
 + backward + clip_grad_norm_ + Adam as ONE hand-scheduled launch sequence, no torch autograd and no torch optimizer -
 
-    text tower (frozen; second stream)   Engine.forward_text                      -> words, txt_g, caption lengths
+    text tower (second stream)           Engine.forward_text                      -> words, txt_g, caption lengths
     image encoder                        SwinMoEEncoder.forward (swin.py:119-149) -> global_feat, local_feat [B, 3136, 768], router probabilities
     GLoRIA global loss, fwd + bwd        Engine.global_loss (losses.py:766-794; all-gather + local-rows InfoNCE under data parallelism)
     GLoRIA local loss, fwd + bwd         GenericLocalLoss (losses.py:961-1026 at 3136 regions)
     classifier term + encoder backward   SwinMoEEncoder.backward into the two flat gradient arenas (medmoe_amd.flat.FlatStore)
     clip + Adam                          one norm over both arenas, the fused Adam kernel on each, bf16 copies refreshed in place
+
+With a trainable text tower (engine.train_text: freeze_bert: false, text_encoder.py:27-30) the text pass is the padded one that keeps its
+activations, the local loss also returns d words (GenericLocalLoss(word_grad=True)), Engine.backward_text runs on the second stream underneath
+the encoder backward into the text store, and the clip norm and Adam cover the third arena too.
 
 The same losses and the same update rule as the torch-autograd mirror (src/models/components/swin.SWIN + src.losses + torch.optim.Adam:
 tests/test_swin_engine_gpu.py steps both from one initial state).  The `Engine` passed in hosts the text tower, the global loss and the loss
@@ -29,12 +33,12 @@ BF, F32, I32 = torch.bfloat16, torch.float32, torch.int32
 
 class SwinEngine:
     def __init__(self, engine: Engine, encoder: SwinMoEEncoder, drop_path_rate: float = 0.1):
-        if engine.train_text:
-            raise NotImplementedError("SwinEngine: the text tower stays frozen (med-moe.yaml:35); freeze_bert: false trains with the ViT towers")
         if engine.cfg.soft_label and engine.dist:
             raise NotImplementedError("soft_label with more than one rank (losses.py:826-883 has no gather)")
         self.eng, self.enc, self.cfg = engine, encoder, engine.cfg
         self.device = encoder.dev
+        self.train_text = engine.train_text
+        self._d_words = None                                        # d loss / d words of the last step (trainable text tower)
         self.drop_path_rate = float(drop_path_rate)
         self.training = True
         self._loc: Optional[GenericLocalLoss] = None
@@ -44,7 +48,7 @@ class SwinEngine:
 
     def _local(self, B: int, HW: int, T: int, D: int) -> GenericLocalLoss:
         if self._loc is None or (self._loc.B, self._loc.HW, self._loc.T, self._loc.D) != (B, HW, T, D):
-            self._loc = GenericLocalLoss(B, HW, T, D, self.device)
+            self._loc = GenericLocalLoss(B, HW, T, D, self.device, word_grad=self.train_text)
             self._gsim = torch.empty(B, B, device=self.device, dtype=F32)
         return self._loc
 
@@ -70,7 +74,7 @@ class SwinEngine:
         main = torch.cuda.current_stream()
         side = eng._side_stream()
         ev = torch.cuda.Event(); ev.record(main); side.wait_event(ev)
-        with torch.cuda.stream(side):                               # the frozen text tower is independent of the image encoder
+        with torch.cuda.stream(side):                               # the text tower is independent of the image encoder
             eng.forward_text(batch["ids"], batch["attn_mask"], batch.get("token_type"))
             done = torch.cuda.Event(); done.record(side)
         out = enc.forward(images.contiguous(), drop_path=drop_path, drop_path_rate=self.drop_path_rate)
@@ -82,6 +86,8 @@ class SwinEngine:
         the last micro-batch, zero_grad=False for all but the first, loss_scale = 1 / number of micro-batches)."""
         eng, enc, c = self.eng, self.enc, self.cfg
         B = batch["image"].shape[0]
+        if self.train_text and zero_grad:
+            eng.tstore.zero_grad()
         out = self.forward(batch, self._drop_path_masks(B))
         ws = eng.ws
         local = out["local_feat"]                                   # bf16 [B, 3136, 768]
@@ -97,6 +103,17 @@ class SwinEngine:
         eng._head(sim, self._gsim, B, 1, wl, 0, lp[3:])
         eng._head(sim, self._gsim, 1, B, wl, 1, lp[3:])
         d_local = loc.backward(self._gsim)
+        text_done = None
+        if self.train_text:
+            # the text backward (aggregation, post-norm blocks, embeddings) only needs the caption-side gradients: second stream, underneath
+            # the encoder backward; joined before the clip norm
+            d_local, self._d_words = d_local
+            main, side = torch.cuda.current_stream(), eng._side_stream()
+            ev = torch.cuda.Event(); ev.record(main); side.wait_event(ev)
+            with torch.cuda.stream(side):
+                eng.backward_text(self._d_words, ws["d_txt_g"])
+                text_done = torch.cuda.Event(); text_done.record(side)
+            self._d_words.record_stream(side)
         if eng.dist and optimizer:
             import torch.distributed as dist
             pending = []
@@ -112,9 +129,16 @@ class SwinEngine:
             dist.all_reduce(enc.tower.store.g32)
             pending[0].wait()
             enc.store.g32.div_(eng.world); enc.tower.store.g32.div_(eng.world)
+            if text_done is not None:                               # the text arena: one more all-reduce, averaged as Engine.train_step does
+                torch.cuda.current_stream().wait_event(text_done)
+                text_done = None
+                from . import dist as D_
+                D_.allreduce_mean_(eng.tstore.g32)
         else:
             enc.backward(ws["d_img_g"], d_local.view(B, HW, D), labels=batch["label"], cls_weight=c.w_cls * loss_scale, zero_grad=zero_grad,
                          loss_parts=lp)
+        if text_done is not None:
+            torch.cuda.current_stream().wait_event(text_done)
         if optimizer:
             self.optimizer_step()
         cls = lp[0] * loss_scale
@@ -122,12 +146,17 @@ class SwinEngine:
                 "g_loss": lp[2] / c.w_global, "l_loss": lp[3] / c.w_local}
 
     def optimizer_step(self, lr: Optional[float] = None):
-        """clip_grad_norm_(cfg.clip) over BOTH arenas + torch.optim.Adam(lr, weight_decay), fused; the bf16 working copies follow."""
+        """clip_grad_norm_(cfg.clip) over ALL arenas (tower, MoE, and the text store when the text tower trains) + torch.optim.Adam(lr,
+        weight_decay), fused; the bf16 working copies follow."""
         c, st_t, st_m = self.cfg, self.enc.tower.store, self.enc.store
         lr = c.lr if lr is None else lr
         torch.add(st_t.sumsq(), st_m.sumsq(), out=self._normsq)
+        if self.train_text:
+            self._normsq.add_(self.eng.tstore.sumsq())
         st_t.adam_step(self._normsq, lr, c.weight_decay, c.clip)
         st_m.adam_step(self._normsq, lr, c.weight_decay, c.clip)
+        if self.train_text:
+            self.eng.tstore.adam_step(self._normsq, lr)
         self.enc.tower.refresh(cast=False)                          # patch-embedding pad form, bias tables
 
     def eval_step(self, batch: Dict[str, torch.Tensor]):

@@ -173,7 +173,10 @@ class MedMoEPretrainingLightningModule(_Base):
         m = self.model
         if getattr(m, "swin", None) is not None:
             enc = m.swin._encoder()
-            return {"swin_tower": enc.tower.store, "swin_moe": enc.store}
+            out = {"swin_tower": enc.tower.store, "swin_moe": enc.store}
+            if m.engine.tstore is not None:                          # text.freeze_bert: false - the text tower's Adam state travels too
+                out["text"] = m.engine.tstore
+            return out
         out = {"image": m.engine.params}
         if m.engine.tstore is not None:
             out["text"] = m.engine.tstore
