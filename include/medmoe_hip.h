@@ -287,6 +287,19 @@ int medmoe_quant_weights_e4m3(const float* w, void* q, void* qT, float* s, int G
    epi 0 none, 1 ReLU, 2 (. + residual) * (aux > 0); C / residual / aux bf16 with row pitch ldc; sb may be NULL (scales folded into A) */
 int medmoe_gemm_fp8_grouped(const void* Aq, const float* sa, const void* Bq, const float* sb, const float* bias, void* C, int ldc, const void* residual, const void* aux, const int* tiles, const int* tile_count, int max_tiles, int N, int K, long long strideB, long long strideSb, long long strideBias, int epi, hipStream_t stream);
 
+/* ---- MXFP8 expert weights on the CDNA4 block-scaled MFMA (OCP Microscaling: e4m3 elements, one E8M0 scale byte per block of 32 along
+   the contraction dimension; DESIGN.md "MXFP8 expert weights") ---- */
+/* bf16 rows (gathered through rowmap when given) -> e4m3 rows q[M][K] + scale bytes s[M][K/32]; K % 32 == 0 */
+int medmoe_quant_rows_mx(const void* x, int ldx, const int* rowmap, void* q, void* s, int M, int K, hipStream_t stream);
+/* fp32 master weights [G][N][K] -> e4m3 q[G][N][K] + scale bytes sq[G][N][K/32] (blocks along K) and, quantised again with blocks
+   along N, e4m3 qT[G][K][N] + scale bytes sT[G][K][N/32]; K % 32 == 0, N % 32 == 0 */
+int medmoe_quant_weights_mx(const float* w, void* q, void* sq, void* qT, void* sT, int G, int N, int K, hipStream_t stream);
+/* grouped C[m][n] = epi(sum_k 2^(sa[m][k/32] - 127) Aq[m][k] * 2^(sb[g][n][k/32] - 127) Bq[g][n][k] (+ bias[g][n])) over the 128-row
+   tile table {group, m0, m_end, -}; any K % 32 == 0; epi 0 none, 1 ReLU, 2 (. + residual) * (aux > 0); C / residual / aux bf16 with
+   row pitch ldc.  Cq / Csq (both or neither; epi 1, N % 32 == 0): the bf16 result MX-quantised along n, Cq[M][N] + Csq[M][N/32],
+   bit-identical to medmoe_quant_rows_mx of C.  strideSb: scale bytes per group. */
+int medmoe_gemm_mx_grouped(const void* Aq, const void* sa, const void* Bq, const void* sb, const float* bias, void* C, int ldc, const void* residual, const void* aux, void* Cq, void* Csq, const int* tiles, const int* tile_count, int max_tiles, int N, int K, long long strideB, long long strideSb, long long strideBias, int epi, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

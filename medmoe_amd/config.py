@@ -32,6 +32,7 @@ class MedMoEConfig:
     router_hidden: int = 128
     d_out: int = 768
     expert_fp8: bool = False      # BASELINE configs[4]: e4m3 expert weights (per-output-channel scales) on the fp8 MFMA
+    expert_mx: bool = False       # MXFP8 expert weights (e4m3 + one E8M0 scale per 32 along the contraction) on the block-scaled MFMA
     # losses (med-moe_pretraining.yaml:20-41)
     temp1: float = 4.0
     temp2: float = 5.0
@@ -76,6 +77,10 @@ class MedMoEConfig:
         return [max(1, (L * (s + 1)) // 4) for s in range(4)]
 
     def validate(self):
+        if self.expert_fp8 and self.expert_mx:
+            raise ValueError("expert_fp8 and expert_mx are two formats of the same weights: set one")
+        if self.expert_mx and (self.d_v % 32 or self.d_out % 64):
+            raise ValueError("MXFP8 experts quantise in blocks of 32 along d_v, d_out and d_out/2")
         if self.d_v % self.n_head_v or self.d_v // self.n_head_v != 64:
             raise ValueError("image tower head_dim must be 64")
         if self.d_t % self.n_head_t or self.d_t // self.n_head_t != 64:
@@ -106,6 +111,12 @@ def config_by_name(name: str) -> MedMoEConfig:
         return MedMoEConfig(patch=14, d_v=1024, n_layer_v=24, n_head_v=16, ff_v=4096, n_expert=16, top_k=2, expert_fp8=True)
     if name == "cfg4_bf16":  # the same geometry with bf16 expert weights
         return MedMoEConfig(patch=14, d_v=1024, n_layer_v=24, n_head_v=16, ff_v=4096, n_expert=16, top_k=2)
+    if name == "cfg4_mx":    # the same geometry with MXFP8 expert weights on the block-scaled MFMA
+        return MedMoEConfig(patch=14, d_v=1024, n_layer_v=24, n_head_v=16, ff_v=4096, n_expert=16, top_k=2, expert_mx=True)
+    if name == "tinyL8mx":   # tinyL with MXFP8 expert weights
+        c = config_by_name("tinyL")
+        c.expert_mx = True
+        return c
     if name == "tinyL8":     # tinyL with fp8 expert weights (configs[4]'s expert arithmetic at unit-test width)
         c = config_by_name("tinyL")
         c.expert_fp8 = True

@@ -185,6 +185,9 @@ class Engine:
         buf("dG", (4, R, Do)); buf("dH1", (4, R, Dh)); buf("dF", (4, R, Dv))
         if c.expert_fp8:           # e4m3 activation rows + their scales (one set, reused by every fp8 GEMM of the step)
             buf("q8", (R, max(Dv, Do)), torch.uint8); buf("q8s", (R,), F32)
+        if c.expert_mx:            # MXFP8 rows + their scale bytes: one set for the separately quantised operands (x{l} gathered, dH1, dG)
+            buf("qmx", (R, max(Dv, Do)), torch.uint8); buf("qmxs", (R, max(Dv, Do) // 32), torch.uint8)    # and one the first projection's
+            buf("qG", (R, Do), torch.uint8); buf("qGs", (R, Do // 32), torch.uint8)                        # epilogue writes for the second
         buf("img_l", (B, P, Do)); buf("img_g", (B, Do), F32)
         buf("d_img_g", (B, Do), F32); buf("d_img_l", (B, P, Do)); buf("dgate", (B * k,), F32)
         buf("dlogits", (B, E), F32); buf("drouter_h", (B, c.router_hidden), F32); buf("drouter_in", (B, Dv), F32)
@@ -303,6 +306,21 @@ class Engine:
         ops.call("gemm_fp8_grouped", q, qs, wq, wscale, bias, out, out.stride(-2), residual, aux, ws["tiles"], ws["tile_count"], self.max_tiles,
                  N, K_, N * K_, N if wscale is not None else 0, N if bias is not None else 0, epi)
 
+    def _mx_gemm(self, x, K, rowmap, w, bias, out, N, epi, residual=None, aux=None, qout=None):
+        """out[r, :N] = epi(MXFP8 product of the rows of x with the expert's weight copy w = (e4m3 [E, N, K], scale bytes [E, N, K/32]))
+        over the dispatch's 128-row tiles on the block-scaled MFMA.  x: bf16 rows (gathered through rowmap), quantised here in blocks of
+        32 along K, or an already quantised (e4m3 [R, K], scale bytes [R, K/32]) pair.  qout = (e4m3 [R, N], scale bytes [R, N/32]): the
+        ReLU epilogue also writes its result MX-quantised along N (the next product's A operand, no separate pass over it)."""
+        ws, R = self.ws, self.R
+        if isinstance(x, tuple):
+            q, qs = x
+        else:
+            q, qs = ws["qmx"].view(-1)[:R * K].view(R, K), ws["qmxs"].view(-1)[:R * (K // 32)].view(R, K // 32)
+            ops.call("quant_rows_mx", x, x.stride(-2), rowmap, q, qs, R, K)
+        wq, wsc = w
+        ops.call("gemm_mx_grouped", q, qs, wq, wsc, bias, out, out.stride(-2), residual, aux, qout[0] if qout else None, qout[1] if qout else None,
+                 ws["tiles"], ws["tile_count"], self.max_tiles, N, K, N * K, N * (K // 32), N if bias is not None else 0, epi)
+
     def forward_image(self, images: torch.Tensor):
         B = images.shape[0]
         self._alloc(B)
@@ -365,6 +383,13 @@ class Engine:
                                p.f32(f"moe.proj.{s}.bias"), ws["G"][s], Do, Dv, 1)
                 self._fp8_gemm(ws["G"][s], Do, None, None, p.q8("moe.attn0.weight"), p.s8("moe.attn0.weight"), p.f32("moe.attn0.bias"),
                                ws["H1"][s], Dh, Do, 1)
+                continue
+            if c.expert_mx:
+                # MXFP8 weights x MXFP8 activation rows (one power-of-two scale per 32 along the contraction) on the block-scaled MFMA;
+                # the first product's epilogue hands G to the second already quantised
+                qG = (ws["qG"], ws["qGs"])
+                self._mx_gemm(ws[f"x{l}"], Dv, ws["rowmap"], p.qmx(f"moe.proj.{s}.weight"), p.f32(f"moe.proj.{s}.bias"), ws["G"][s], Do, 1, qout=qG)
+                self._mx_gemm(qG, Do, None, p.qmx("moe.attn0.weight"), p.f32("moe.attn0.bias"), ws["H1"][s], Dh, 1)
                 continue
             ops.gemm_nt(ws[f"x{l}"], p.w16(f"moe.proj.{s}.weight"), ws["G"][s], bias=p.f32(f"moe.proj.{s}.bias"),
                         a_rowmap=ws["rowmap"], stride_b=Do * Dv, stride_bias=Do, epi=ops.EPI_RELU, **grp(Dv))   # swin.py:40-41
@@ -933,6 +958,8 @@ class Engine:
             if c.expert_fp8:      # dgrad on the TRANSPOSED e4m3 weights; their output-channel scales ride on the gradient rows
                 self._fp8_gemm(ws["dH1"][s], Dh, None, p.s8("moe.attn0.weight"), p.q8t("moe.attn0.weight"), None, None, ws["dG"][s], Do, Dh, 2,
                                residual=ws["dG"][s], aux=ws["G"][s])
+            elif c.expert_mx:     # dgrad on the weight copies quantised along N (the contraction here); no scale folding: the scales are per block
+                self._mx_gemm(ws["dH1"][s], Dh, None, p.qmxt("moe.attn0.weight"), None, ws["dG"][s], Do, 2, residual=ws["dG"][s], aux=ws["G"][s])
             else:
                 ops.gemm_nt(ws["dH1"][s], p.w16t("moe.attn0.weight"), ws["dG"][s], residual=ws["dG"][s], aux=ws["G"][s],
                             stride_b=Dh * Do, epi=ops.EPI_MUL_DRELU, **grp(Dh))
@@ -941,6 +968,8 @@ class Engine:
                           nsplit=4, M=R)
             if c.expert_fp8:
                 self._fp8_gemm(ws["dG"][s], Do, None, p.s8(f"moe.proj.{s}.weight"), p.q8t(f"moe.proj.{s}.weight"), None, None, ws["dF"][s], Dv, Do, 0)
+            elif c.expert_mx:
+                self._mx_gemm(ws["dG"][s], Do, None, p.qmxt(f"moe.proj.{s}.weight"), None, ws["dF"][s], Dv, 0)
             else:
                 ops.gemm_nt(ws["dG"][s], p.w16t(f"moe.proj.{s}.weight"), ws["dF"][s], stride_b=Do * Dv, **grp(Do))
         # ---- router backward: CE on probabilities (medmoe_module.py:235-237) + gate gradients ----

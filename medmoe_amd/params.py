@@ -91,12 +91,20 @@ class ParamStore:
         self.step_count = 0
         # fp8 expert weights (BASELINE configs[4]): e4m3 copies [E,N,K] + transposes [E,K,N] + per-output-channel scales [E,N] of
         # the five expert projections, re-derived from the fp32 master after every update (requantise_experts)
-        self.fp8: Dict[str, Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = {}
+        self.fp8: Dict[str, Tuple[torch.Tensor, ...]] = {}
         if cfg.expert_fp8:
             for name in [f"moe.proj.{s_}.weight" for s_ in range(4)] + ["moe.attn0.weight"]:
                 Eg, N, K = self.shapes[name]
                 self.fp8[name] = (torch.empty(Eg, N, K, device=dev, dtype=torch.uint8), torch.empty(Eg, K, N, device=dev, dtype=torch.uint8),
                                   torch.empty(Eg, N, device=dev, dtype=torch.float32))
+        # MXFP8 expert weights (cfg.expert_mx; the same dict: it holds the 8-bit working copies of whichever format is on, and whoever
+        # saves / restores the parameter state walks it): per projection (q [E,N,K], scale bytes [E,N,K/32]) for the forward and,
+        # quantised again with blocks along N, (qT [E,K,N], scale bytes [E,K,N/32]) for dgrad
+        if cfg.expert_mx:
+            for name in [f"moe.proj.{s_}.weight" for s_ in range(4)] + ["moe.attn0.weight"]:
+                Eg, N, K = self.shapes[name]
+                self.fp8[name] = (torch.empty(Eg, N, K, device=dev, dtype=torch.uint8), torch.empty(Eg, N, K // 32, device=dev, dtype=torch.uint8),
+                                  torch.empty(Eg, K, N, device=dev, dtype=torch.uint8), torch.empty(Eg, K, N // 32, device=dev, dtype=torch.uint8))
         self._init_random(seed, std)
         # ---- frozen text tower ----
         self.text: Dict[str, torch.Tensor] = {}
@@ -168,13 +176,20 @@ class ParamStore:
         self.requantise_experts()
 
     def requantise_experts(self):
-        for name, (q, qT, s) in self.fp8.items():
+        for name, copies in self.fp8.items():
             Eg, N, K = self.shapes[name]
-            ops.call("quant_weights_e4m3", self.f32(name), q, qT, s, Eg, N, K)
+            if self.cfg.expert_mx:
+                q, sq, qT, sT = copies
+                ops.call("quant_weights_mx", self.f32(name), q, sq, qT, sT, Eg, N, K)
+            else:
+                q, qT, s = copies
+                ops.call("quant_weights_e4m3", self.f32(name), q, qT, s, Eg, N, K)
 
     def q8(self, name): return self.fp8[name][0]
     def q8t(self, name): return self.fp8[name][1]
     def s8(self, name): return self.fp8[name][2]
+    def qmx(self, name): return self.fp8[name][0], self.fp8[name][1]      # MXFP8 forward copy + scale bytes: blocks along K
+    def qmxt(self, name): return self.fp8[name][2], self.fp8[name][3]     # MXFP8 dgrad copy + scale bytes: blocks along N
 
     # -- reference-style names ------------------------------------------------------------------
     def load_named(self, named: Dict[str, torch.Tensor]):

@@ -64,9 +64,11 @@ def config_from_hydra(vision: Any, text: Any) -> MedMoEConfig:
     c.d_t = int(_get(text, "embed_dim", c.d_t))
     c.freeze_text = bool(_get(text, "freeze_bert", True))     # false: the text tower trains too (text_encoder.py:27-30) - fused step only
     dt = str(_get(vision, "expert_dtype", "bf16"))
-    if dt not in ("bf16", "fp8"):
-        raise NotImplementedError(f"vision.expert_dtype={dt!r}: bf16 or fp8 (e4m3 expert weights, BASELINE configs[4])")
+    if dt not in ("bf16", "fp8", "mxfp8"):
+        raise NotImplementedError(f"vision.expert_dtype={dt!r}: bf16, fp8 (e4m3 expert weights, per-row / per-channel scales, BASELINE configs[4]) "
+                                  f"or mxfp8 (e4m3 with one power-of-two scale per block of 32, the block-scaled MFMA)")
     c.expert_fp8 = dt == "fp8"
+    c.expert_mx = dt == "mxfp8"
     return c
 
 
