@@ -19,7 +19,10 @@
 extern "C" {
 #endif
 
-/* F.scaled_dot_product_attention over the fused QKV buffer (multi_head_attention.py:62-78) */
+/* F.scaled_dot_product_attention over the fused QKV buffer (multi_head_attention.py:62-78)
+ * key_mask: NULL (every key valid) or uint8 [B][N], one byte per key, non-zero = valid.  Any pattern is supported, holes and whole
+ * masked blocks included (tests/test_attention_gpu.py); every sequence must keep at least one valid key.  The contents of masked K / V
+ * rows do not influence any output as long as they are finite, and the backward writes zeros into their dK / dV rows. */
 int medmoe_attn_fwd(const void* qkv, void* out, float* lse, const unsigned char* key_mask, int B, int N, int H, int head_dim, hipStream_t stream);
 
 /* backward of the same (dQ, dK, dV written into a [B*N,3D] buffer) */

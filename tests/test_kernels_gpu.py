@@ -353,8 +353,10 @@ def _attention_case(ops, B, N, H, masked):
     dqkv = torch.zeros_like(qkv); delta = torch.empty(B, H, N, device="cuda")
     ops.attn_bwd(qkv, out, dout, lse, mask, dqkv, delta, B, N, H)
     g = qr.grad
-    if masked:   # gradients of padded key/value rows are exactly zero in both
-        pass
+    if masked:   # gradients of padded key/value rows are exactly zero in both (the kernel's: bit pattern zero)
+        pad = ~mask.bool()
+        assert not bool(dqkv.view(B, N, 3, D)[:, :, 1:][pad].contiguous().view(torch.int16).any())
+        assert bool((g.view(B, N, 3, D)[:, :, 1:][pad] == 0).all())
     assert rel_err(dqkv, g) < 2e-2
 
 
