@@ -139,6 +139,15 @@ int medmoe_gemm_tn_cols(const void* G, int ldg, const void* X, int ldx, float* d
    w[g*w_gstride + m*w_ld] fp32.  The local loss' dGm_b = sum over caption words of d2 * a a^T (backward of the weighted-context norm in
    attention_fn / cosine_similarity, losses.py:690-736) without a stored d2 * A matrix.  fp32 atomics into dW (zero it first). */
 int medmoe_gemm_tn_gram(const void* A, int lda, const float* w, long long w_gstride, int w_ld, float* dW, int ldw, int M, int Nn, int n_groups, long long col_stride, long long strideW, hipStream_t stream);
+/* the local similarity FORWARD ONLY (the evaluation step; losses.py:979-1012 with attention_fn :698-736), one launch per caption length class:
+   sim[b][i] = log sum_{t < len_i} exp(temp2 cos(w_it, sum_p a_pt ctx_bp)) for the n_cap captions i in cap_list (16 (ntt - 1) < len <= 16 ntt),
+   fp32 [B][Bc], BEFORE temp3.  ctx bf16 [B*HW][D], words bf16 [Bc][T][D], gm bf16 [B][GR][GR] Gram matrices ctx_b ctx_b^T (GR = 32 ceil(HW / 32),
+   zero outside [HW][HW]), wnorm fp32 [Bc][T].  Scores, probabilities, attention and per-word sums stay in registers / LDS: sim is the only
+   global store, one owner per element, no atomics (two launches give the same bits).  There is no pair matrix, hence no column base.
+   Geometries of medmoe_local_pair3_supported, D % 64 == 0; anything else returns -2 before a launch. */
+int medmoe_local_sim_fwd(const void* ctx, const void* words, const int* cap_lens, const void* gm, const float* wnorm, float* sim, int B, int Bc, int HW, int T, int D, float temp1, float temp2, float eps, const int* cap_list, int n_cap, int ntt, hipStream_t stream);
+/* tests: caption chunks per image of medmoe_local_sim_fwd (0 = automatic) */
+int medmoe_local_sim_chunks(int n);
 /* tests: caption chunks per image of medmoe_local_pair3 (0 = automatic) */
 int medmoe_local_pair3_chunks(int n);
 /* 1: medmoe_local_pair3 has an instantiation for (HW regions, T words) */
@@ -218,6 +227,10 @@ int medmoe_router_fwd(const float* x, const float* w1, const float* b1, const fl
 
 /* CE on router probabilities (medmoe_module.py:235-237) + gate gradients -> dlogits, dh */
 int medmoe_router_bwd(const float* probs, const float* h, const float* w2, const int* idx, const float* dgates, const int* labels, const float* dprobs_ext, float ce_scale, float* dlogits, float* dh, float* loss_acc, int B, int Hd, int E, int k, hipStream_t stream);
+
+/* the two values medmoe_router_bwd accumulates, without a gradient (the evaluation step): loss_acc[0] = mean CE on the router probabilities,
+   loss_acc[1] = accuracy; one workgroup, plain stores */
+int medmoe_router_eval(const float* probs, const int* labels, float* loss_acc, int B, int E, hipStream_t stream);
 
 /* small strided fp32 GEMM (router wgrad/dgrad, global-loss similarity and its gradients) */
 int medmoe_sgemm(const float* A, const float* Bm, float* C, int M, int N, int K, long long sam, long long sak, long long sbk, long long sbn, long long ldc, float alpha, float beta, hipStream_t stream);

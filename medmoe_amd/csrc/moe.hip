@@ -192,6 +192,48 @@ extern "C" int medmoe_router_bwd(const float* probs, const float* h, const float
   return mm_check_launch();
 }
 
+// router cross-entropy and accuracy alone (the evaluation step): the two values router_bwd_kernel accumulates, without a gradient.
+// ONE workgroup, plain stores: loss_acc[0] = mean CE over the already-softmaxed probabilities (medmoe_module.py:235-237),
+// loss_acc[1] = accuracy, summed as router_bwd's atomics sum it (1/B added once per hit), so the two paths report the same bits.
+__global__ __launch_bounds__(256) void router_eval_kernel(const float* __restrict__ probs, const int* __restrict__ labels,
+                                                          float* __restrict__ loss_acc, int B, int E) {
+  __shared__ float sl[256];
+  __shared__ int sh[256];
+  const int j = threadIdx.x;
+  float loss = 0.f;
+  int hits = 0;
+  for (int b = j; b < B; b += 256) {
+    const float* p = probs + (long long)b * E;
+    float m = p[0];
+    int am = 0;
+    for (int e = 1; e < E; ++e) { m = fmaxf(m, p[e]); if (p[e] > p[am]) am = e; }
+    float s = 0.f;
+    for (int e = 0; e < E; ++e) s += __expf(p[e] - m);
+    const int lab = labels[b];
+    if (lab >= 0 && lab < E) loss += -__logf(__expf(p[lab] - m) / s) / (float)B;
+    hits += am == lab;
+  }
+  sl[j] = loss; sh[j] = hits;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (j < o) { sl[j] += sl[j + o]; sh[j] += sh[j + o]; }
+    __syncthreads();
+  }
+  if (j == 0) {
+    float acc = 0.f;
+    for (int n = 0; n < sh[0]; ++n) acc += 1.f / (float)B;
+    loss_acc[0] = sl[0];
+    loss_acc[1] = acc;
+  }
+}
+
+extern "C" int medmoe_router_eval(const float* probs, const int* labels, float* loss_acc, int B, int E, hipStream_t stream) {
+  if (!probs || !labels || !loss_acc) return MM_ERR_ARG;
+  if (B <= 0 || E <= 0 || E > ROUTER_MAX_E) return MM_ERR_SHAPE;
+  hipLaunchKernelGGL(router_eval_kernel, dim3(1), dim3(256), 0, stream, probs, labels, loss_acc, B, E);
+  return mm_check_launch();
+}
+
 // ---------------------------------------------------------------------------------------------
 // generic small fp32 GEMM with arbitrary strides: C[m,n] = alpha*sum_k A[m,k]*B[k,n] + beta*C
 // (router wgrad/dgrad, global-loss similarity + its gradients).  64x64 tile, 4x4 per thread.

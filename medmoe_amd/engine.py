@@ -17,7 +17,7 @@ import torch
 
 from . import ops
 from .local_generic import GenericLocalLoss
-from .local_transposed import TransposedLocalLoss, ragged_layout  # noqa: F401  (ragged_layout: the [region][word] path and the tests use it from here)
+from .local_transposed import TransposedLocalLoss, local_sim_forward, ragged_layout  # noqa: F401  (ragged_layout: the [region][word] path and the tests use it from here)
 from .config import MedMoEConfig
 from .params import ParamStore
 
@@ -113,6 +113,8 @@ class Engine:
             self.params.text = self.tstore.as_dict()             # views of the flat buffers: an optimiser step updates them in place
         self._tlw = None                                             # TransposedLocalLoss in word-gradient mode (own buffers)
         self._glw = None                                             # GenericLocalLoss in word-gradient mode (other geometries)
+        self._gle = None                                             # GenericLocalLoss of eval_step at 256 regions (its forward launches only)
+        self._ev_g = None                                            # eval_step against the gathered captions: word norms, similarities
         self.local_dense = False
         self.HWp, self.Tp, self.GW = ops.local_geometry(cfg.n_patch, cfg.max_len)
         # LDS-tiled pair kernels exist for 64 / 208 / 256 regions; any other geometry (576 regions of ViT-L/14 at 336 px) runs
@@ -609,10 +611,12 @@ class Engine:
     # ------------------------------------------------------------------------------------------
     # losses: forward values + gradients w.r.t. img_g / img_l (text is frozen)
     # ------------------------------------------------------------------------------------------
-    def global_loss(self, loss_scale: float = 1.0):
+    def global_loss(self, loss_scale: float = 1.0, grad: bool = True):
         """GLoRIA global loss (losses.py:766-794) of ws["img_g"] against ws["txt_g"], forward and backward: zeroes ws["loss_parts"], adds the
         weighted loss to loss_parts[2], leaves dL/d img_g in ws["d_img_g"] (and dL/d txt_g in ws["d_txt_g"] when the text tower trains).
-        Any image encoder that fills ws["img_g"] can call it (the ViT towers here, the Swin-T encoder in medmoe_amd.swin_engine)."""
+        Any image encoder that fills ws["img_g"] can call it (the ViT towers here, the Swin-T encoder in medmoe_amd.swin_engine).
+        grad=False (eval_step): the loss value only - the heads still write d loss / d S into the scratch ws["dS"] (/ ws["dS2"]), nothing
+        reads it and no gradient buffer is touched."""
         c, ws = self.cfg, self.ws
         B, Do = self.B, c.d_out
         ws["loss_parts"].zero_()
@@ -632,6 +636,8 @@ class Engine:
             ops.call("cos_scale", ws["S"], ws["na"], ws["nb"], B, B, 1e-8)
             self._head(ws["S"], ws["dS"], B, 1, wg, 0, lp[2:])
             self._head(ws["S"], ws["dS"], 1, B, wg, 1, lp[2:])
+            if not grad:
+                return
             cb = None
             if self.train_text:
                 cb = ws["cb"]; cb.zero_()
@@ -652,19 +658,22 @@ class Engine:
             ops.call("sgemm", img_g, txt_all, ws["S"], B, Bg, Do, Do, 1, 1, Do, Bg, 1.0, 0.0)
             ops.call("cos_scale", ws["S"], ws["na"], ws["nb"], B, Bg, 1e-8)
             ops.call("ce_strided", ws["S"], ws["dS"], B, Bg, Bg, 1, off, c.temp3, wg, 0, lp[2:])
-            cb1 = None
-            if self.train_text:
-                cb1 = ws["cb1"]; cb1.zero_()
-            ops.call("cos_scale_bwd", ws["dS"], ws["S"], ws["na"], ws["nb"], ws["ca"], cb1, B, Bg, 1e-8)
-            ops.call("sgemm", ws["dS"], txt_all, ws["d_img_g"], B, Do, Bg, Bg, 1, Do, 1, Do, 1.0, 0.0)
-            ops.call("add_rowscaled", ws["d_img_g"], img_g, ws["ca"], B, Do)
-            if self.train_text:       # my images against ALL captions: the gathered captions' gradient, summed over ranks, my slice comes back
-                ops.call("sgemm", ws["dS"], img_g, ws["d_txt_all"], Bg, Do, B, 1, Bg, Do, 1, Do, 1.0, 0.0)
-                ops.call("add_rowscaled", ws["d_txt_all"], txt_all, cb1, Bg, Do)
+            if grad:
+                cb1 = None
+                if self.train_text:
+                    cb1 = ws["cb1"]; cb1.zero_()
+                ops.call("cos_scale_bwd", ws["dS"], ws["S"], ws["na"], ws["nb"], ws["ca"], cb1, B, Bg, 1e-8)
+                ops.call("sgemm", ws["dS"], txt_all, ws["d_img_g"], B, Do, Bg, Bg, 1, Do, 1, Do, 1.0, 0.0)
+                ops.call("add_rowscaled", ws["d_img_g"], img_g, ws["ca"], B, Do)
+                if self.train_text:       # my images against ALL captions: the gathered captions' gradient, summed over ranks, my slice comes back
+                    ops.call("sgemm", ws["dS"], img_g, ws["d_txt_all"], Bg, Do, B, 1, Bg, Do, 1, Do, 1.0, 0.0)
+                    ops.call("add_rowscaled", ws["d_txt_all"], txt_all, cb1, Bg, Do)
             ops.call("rownorm", txt_g, ws["na2"], B, Do); ops.call("rownorm", img_all, ws["nb2"], Bg, Do)
             ops.call("sgemm", txt_g, img_all, ws["S2"], B, Bg, Do, Do, 1, 1, Do, Bg, 1.0, 0.0)
             ops.call("cos_scale", ws["S2"], ws["na2"], ws["nb2"], B, Bg, 1e-8)
             ops.call("ce_strided", ws["S2"], ws["dS2"], B, Bg, Bg, 1, off, c.temp3, wg, 0, lp[2:])
+            if not grad:
+                return
             ws["cb2"].zero_()
             ops.call("cos_scale_bwd", ws["dS2"], ws["S2"], ws["na2"], ws["nb2"], ws["ca2"], ws["cb2"], B, Bg, 1e-8)
             # d img_all = dM^T txt_local + cb * img_all ; summed over ranks, my slice comes back
@@ -832,10 +841,8 @@ class Engine:
                 ws["l_d2"] = torch.empty((B, cap), device=self.device, dtype=torch.float32)
         self._pair_cap = cap
 
-    def _local_loss_generic(self, loss_scale: float):
-        """GLoRIA local loss for a geometry without LDS-tiled pair kernels (loss.hip "GENERIC-GEOMETRY"): the reference's own
-        formulation - weighted context = bmm(ctx, attn) (losses.py:732), cosine against the word (:690-695, :1002) - as grouped
-        GEMMs over the uniform pair matrices [B*HWp, B*Tp], plus four elementwise kernels."""
+    def _local_generic_forward(self):
+        """The forward launches of `_local_loss_generic`: word softmax, region attention, weighted contexts, cosines -> ws["sim"]."""
         c, ws = self.cfg, self.ws
         B, P, Do, T = self.B, c.n_patch, c.d_out, c.max_len
         HWp, Tp = self.HWp, self.Tp
@@ -846,7 +853,6 @@ class Engine:
             for t_ in (lp_, LA, DA, wT):
                 t_[:, B * Tp:].zero_()
             ws["l_DWC"][:, B * Tp:].zero_()
-        lp = ws["loss_parts"]
         ops.call("words_prep_ragged", ws["words"], ws["wn"], wT, B, T, Tp, Do, ws["l_col"], ws["l_tp"], Kp)
         ops.call("local_scores_ragged", ctx, ws["words"], self.cap_lens, lp_, ws["l_lse"], B, B, P, T, Do, ws["l_members"], B, Tp // 16, 0, Kp)
         ops.call("local_gen_fwd_a", lp_, self.cap_lens, LA, B, B, P, HWp, T, Tp, c.temp1, Kp)
@@ -855,6 +861,19 @@ class Engine:
                     M=B * HWp)                                    # wctx_b = A_b^T ctx_b
         ops.call("local_gen_cos", ws["l_WC"], ws["words"], ws["wn"], self.cap_lens, ws["sim"], ws["l_stats"], ws["l_sume"], B, B, T, Tp, Do,
                  c.temp2, 1e-8, Kp)
+
+    def _local_loss_generic(self, loss_scale: float):
+        """GLoRIA local loss for a geometry without LDS-tiled pair kernels (loss.hip "GENERIC-GEOMETRY"): the reference's own
+        formulation - weighted context = bmm(ctx, attn) (losses.py:732), cosine against the word (:690-695, :1002) - as grouped
+        GEMMs over the uniform pair matrices [B*HWp, B*Tp], plus four elementwise kernels."""
+        c, ws = self.cfg, self.ws
+        B, P, Do, T = self.B, c.n_patch, c.d_out, c.max_len
+        HWp, Tp = self.HWp, self.Tp
+        Kp = ws["l_A"].shape[1]                                   # B*Tp rounded up to the GEMM k-step
+        ctx = ws["img_l"].view(B * P, Do)
+        lp_, LA, DA, wT = ws["l_LP"], ws["l_A"], ws["l_dS"], ws["wT"]
+        lp = ws["loss_parts"]
+        self._local_generic_forward()
         wl = c.w_local * loss_scale / B
         self._head(ws["sim"], ws["gsim"], B, 1, wl, 0, lp[3:])
         self._head(ws["sim"], ws["gsim"], 1, B, wl, 1, lp[3:])
@@ -1093,6 +1112,66 @@ class Engine:
         cls = lp[0] * loss_scale
         return {"loss": c.w_cls * cls + lp[2] + lp[3], "classifier_loss": cls, "classifier_acc": lp[1],
                 "g_loss": lp[2] / c.w_global, "l_loss": lp[3] / c.w_local}
+
+    # ------------------------------------------------------------------------------------------
+    # evaluation (medmoe_module.py:114-134 validation_step / test_step: model_step without a backward)
+    # ------------------------------------------------------------------------------------------
+    def eval_step(self, batch: Dict[str, torch.Tensor]):
+        """The losses of `train_step` on a batch, forward only: same dict, same weighting, device scalars.  No gradient, Adam moment, master
+        or working parameter is written.  The towers and the global loss are the training launches; the local loss of the 196 / 64-region
+        geometries runs medmoe_local_sim_fwd (csrc/local_eval.hip), which keeps a pair's scores and attention on the chip - an engine that
+        only evaluates never allocates the ragged pair matrices; other geometries run the forward launches of the generic formulation.
+        The router's cross-entropy and accuracy come from medmoe_router_eval.  Always eager (no hipGraph replay)."""
+        c = self.cfg
+        B = batch["image"].shape[0]
+        self._alloc(B)
+        self.prefetch_cap_lens(batch["ids"])
+        self._forward_both(batch)
+        self.global_loss(grad=False)
+        self._local_loss_eval()
+        lp = self.ws["loss_parts"]
+        ops.call("router_eval", self.ws["probs"], batch["label"].to(I32).contiguous(), lp, B, c.n_expert)
+        return {"loss": c.w_cls * lp[0] + lp[2] + lp[3], "classifier_loss": lp[0].clone(), "classifier_acc": lp[1],
+                "g_loss": lp[2] / c.w_global, "l_loss": lp[3] / c.w_local}
+
+    def _local_loss_eval(self):
+        """GLoRIA local loss value (losses.py:961-1026) of ws["img_l"] against ws["words"] into loss_parts[3]; ws["gsim"] is the heads' scratch."""
+        c, ws, B = self.cfg, self.ws, self.B
+        P, T, Do = c.n_patch, c.max_len, c.d_out
+        lp = ws["loss_parts"]
+        ctx = ws["img_l"].view(B * P, Do)
+        gather = self.dist and c.local_loss_global
+        if gather and not self.local_t:
+            raise NotImplementedError("local_loss_global needs the transposed local-loss path (196 / 64 regions)")
+        if self.local_t:
+            tabs = dict(P=P, gm3=ws["gm3"], gm3_crowmap=ws["gm3_crowmap"], img_tiles=ws["img_tiles"], img_tile_count=ws["img_tile_count"])
+            if gather:
+                # this rank's images against the captions of every rank, both cross-entropies over the gathered [B_g, B_g] matrix
+                # (the heads of _local_loss_global)
+                from . import dist as D_
+                Bg = B * self.world
+                words_all = D_.gather_rows(ws["words"])
+                caps_all = D_.gather_rows(self.cap_lens)
+                if self._ev_g is None or self._ev_g[0].shape[0] != Bg or self._ev_g[1].shape[0] != B:
+                    self._ev_g = (torch.empty(Bg, T, device=self.device, dtype=F32), torch.empty(B, Bg, device=self.device, dtype=F32))
+                sim = local_sim_forward(ctx, words_all, caps_all, caps_all.cpu().numpy().astype(np.int64), c.temp1, c.temp2,
+                                        wn=self._ev_g[0], sim=self._ev_g[1], **tabs)
+                S = D_.gather_rows(sim)
+                G = torch.empty_like(S)
+                wl = c.w_local / Bg
+                ops.call("ce_strided", S, G, Bg, Bg, Bg, 1, 0, c.temp3, wl, 0, lp[3:])
+                ops.call("ce_strided", S, G, Bg, Bg, 1, Bg, 0, c.temp3, wl, 1, lp[3:])
+                return
+            local_sim_forward(ctx, ws["words"], self.cap_lens, self._cap_lens_host(), c.temp1, c.temp2, wn=ws["wn"], sim=ws["sim"], **tabs)
+        elif not self.local_fast:
+            self._local_generic_forward()
+        else:       # 256 regions: training uses the LDS-tiled pair kernels, whose forward and backward are one launch
+            if self._gle is None or self._gle.B != B:
+                self._gle = GenericLocalLoss(B, P, T, Do, self.device)
+            ws["sim"].copy_(self._gle.forward(ctx, ws["words"], self.cap_lens, c.temp1, c.temp2))
+        wl = c.w_local / B
+        self._head(ws["sim"], ws["gsim"], B, 1, wl, 0, lp[3:])
+        self._head(ws["sim"], ws["gsim"], 1, B, wl, 1, lp[3:])
 
     def _forward_both(self, b):
         if self.overlap_wgrad and b["image"].is_cuda and self.B * self.cfg.n_tok_v <= 131072:

@@ -38,6 +38,27 @@ def ragged_layout(cap_lens, T: int, Tp: int):
     return perm, col_of_cap, ntts, cap_of_chunk, classes, Kc, Kp
 
 
+def local_sim_forward(ctx: torch.Tensor, words: torch.Tensor, cap_lens: torch.Tensor, cap_lens_host, temp1: float, temp2: float, *, P: int,
+                      gm3: torch.Tensor, gm3_crowmap: torch.Tensor, img_tiles: torch.Tensor, img_tile_count: torch.Tensor,
+                      wn: torch.Tensor, sim: torch.Tensor) -> torch.Tensor:
+    """The similarity matrix alone, for evaluation (csrc/local_eval.hip): ctx bf16 [B*P, Do], words bf16 [Bc, T, Do], cap_lens int32 [Bc] on
+    the device + the same lengths on the host -> sim fp32 [B, Bc] BEFORE temp3.  The Gram GEMM and the word norms are the training path's;
+    the scores, the two softmaxes and the per-word sums of a pair then stay on the chip: no pair matrix exists, the workspace is the
+    caller's gm3 [B*GR, GR] (zero outside [P, P]), wn [Bc, T] and sim."""
+    Bc, T, Do = words.shape
+    B = ctx.shape[0] // P
+    _, Tp, _ = ops.local_geometry(P, T)
+    perm, col_of_cap, ntts, _, classes, _, Kp = ragged_layout(cap_lens_host, T, Tp)
+    meta = torch.from_numpy(np.concatenate((perm, col_of_cap, 16 * ntts)).astype(np.int32)).to(ctx.device, non_blocking=True)
+    d_perm, d_col, d_tp = meta[:Bc], meta[Bc:2 * Bc], meta[2 * Bc:]
+    ops.call("words_prep_ragged", words, wn, None, Bc, T, Tp, Do, d_col, d_tp, Kp)                         # word norms only
+    ops.gemm_nt(ctx, ctx, gm3, c_rowmap=gm3_crowmap, tiles=img_tiles, tile_count=img_tile_count, max_tiles=img_tiles.shape[0],
+                stride_b=P * Do, M=B * P, N=P)
+    for ntt, start, n_c, _ in classes:
+        ops.call("local_sim_fwd", ctx, words, cap_lens, gm3, wn, sim, B, Bc, P, T, Do, temp1, temp2, 1e-8, d_perm[start:start + n_c], n_c, ntt)
+    return sim
+
+
 class TransposedLocalLoss:
     """forward(ctx, words, cap_lens, cap_lens_host, temp1, temp2) fills ws["sim"] ([B, B] fp32, BEFORE temp3); the caller turns it into
     ws["gsim"] = d loss / d sim; backward(d_img_l) writes the bf16 gradient of the region features.

@@ -321,7 +321,7 @@ _SIGS = {
     "patchify": "ppiiiiii", "patchify_ld": "ppiiiiiii", "init_tokens": "pppiii", "pos_cls_grad": "pppiii",
     "text_embed_ln": "ppppppppiiiif", "text_aggregate": "ppppippppiii",
     "mean_tokens": "ppiiiii", "broadcast_tokens": "ppiiiiif",
-    "router_fwd": "pppppppppiiiii", "router_bwd": "pppppppfpppiiii",
+    "router_fwd": "pppppppppiiiii", "router_bwd": "pppppppfpppiiii", "router_eval": "pppii",
     "sgemm": "pppiiilllllff", "dispatch": "piiiiippppppip",
     "scale_attn_fwd": "pppppippiii", "combine_fwd": "ppppiiii",
     "scale_attn_bwd": "ppppppppppiipppppiii", "stage_grad_add": "pppiiiii",
@@ -330,7 +330,7 @@ _SIGS = {
     "local_pair": "pppppppppppppiiiiifffi", "local_scores": "pppppiiiii", "local_pair2": "ppppppppppiiiifff", "scale_blocks": "pppiiii",
     "words_prep_ragged": "pppiiiippl", "local_scores_ragged": "pppppiiiiipiill",
     "local_pair2_ragged": "pppppppppiiiifffpiill", "scale_blocks_ragged": "pppiiipl",
-    "local_pair3": "ppppppppppppliiiifffpiilllip", "local_pair3_wgrad": "ppppppppppppliiiifffpiilllipp", "local_scores_t": "pppppiiiiipiilll", "gemm_tn_cols": "pipipiiiiilllil", "gemm_tn_gram": "piplipiiiill",
+    "local_pair3": "ppppppppppppliiiifffpiilllip", "local_pair3_wgrad": "ppppppppppppliiiifffpiilllipp", "local_scores_t": "pppppiiiiipiilll", "local_sim_fwd": "ppppppiiiiifffpii", "gemm_tn_cols": "pipipiiiiilllil", "gemm_tn_gram": "piplipiiiill",
     "local_gen_fwd_a": "pppiiiiiifl", "local_gen_cos": "pppppppiiiiiffl", "local_gen_dwctx": "ppppppppiiiiiffl",
     "local_gen_dwords": "pppppppppiiiiiffl",
     "local_gen_bwd_s": "ppppiiiiiifl", "unpad_cast2": "pppiiii",
@@ -399,6 +399,10 @@ def _cost_pair3(a):         # (X, dS, AT, UT, lse, gm, wn, caps, gsim, sim, att,
     return "local_pair3_kernel<196, NTT, true> (backward)", 6.0 * elems, "byte"          # reads lp + A, writes dS
 
 
+def _cost_local_sim(a):     # (ctx, words, caps, gm, wn, sim, B, Bc, P, T, Do, t1, t2, eps, members, n_c, ntt)
+    return "local_sim_fwd_kernel<196, NTT> (scores + pair stage, forward only)", 2.0 * a[6] * a[8] * a[15] * 16 * a[16] * a[10], "flop"
+
+
 def _cost_tn_cols(a):       # (g, ldg, x, ldx, dw, ldw, M, Nn, Kk, n_groups, ...)
     return "gemm_tn4w_kernel<false, COLG, false> (local-loss dC)", 2.0 * a[6] * a[7] * a[8] * max(1, a[9]), "flop"
 
@@ -408,7 +412,7 @@ def _cost_tn_gram(a):       # (AT, ld, d2, srows, 1, out, ldo, Kp, HWq, B, bs, o
 
 
 _COSTS = {
-    "local_scores_t": _cost_scores, "local_pair3": _cost_pair3, "local_pair3_wgrad": _cost_pair3, "gemm_tn_cols": _cost_tn_cols, "gemm_tn_gram": _cost_tn_gram,
+    "local_scores_t": _cost_scores, "local_pair3": _cost_pair3, "local_pair3_wgrad": _cost_pair3, "local_sim_fwd": _cost_local_sim, "gemm_tn_cols": _cost_tn_cols, "gemm_tn_gram": _cost_tn_gram,
     "adam_step": lambda a: ("adam_kernel", 34.0 * a[5], "byte"),                                   # p, g, m, v read; p, m, v, bf16 copy written
     "scale_attn_bwd": lambda a: ("scale_attn_bwd_kernel", 2.0 * a[17] * (4 * (2 * a[18] + 2 * a[19]) + 2 * a[18]), "byte"),    # G, dG, H1, dH1 x 4 scales + eout, d_img_l rows
     "scale_attn_fwd": lambda a: ("scale_attn_fwd_kernel", 2.0 * a[8] * (4 * (a[9] + a[10]) + a[9]), "byte"),
@@ -422,6 +426,10 @@ def local_fast_path(HW: int, T: int) -> bool:
 
 def local_pair3_chunks(n: int):
     _chk(load_library().medmoe_local_pair3_chunks(_c.c_int(n)), "local_pair3_chunks")
+
+
+def local_sim_chunks(n: int):
+    _chk(load_library().medmoe_local_sim_chunks(_c.c_int(n)), "local_sim_chunks")
 
 
 def local_pair3_supported(HW: int, T: int) -> bool:

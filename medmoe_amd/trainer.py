@@ -200,13 +200,17 @@ class Trainer:
         return self.callback_metrics
 
     @torch.no_grad()
-    def validate(self, model, datamodule):
+    def validate(self, model, datamodule, step: str = "validation_step"):
+        """Mean `loss` over the validation batches -> val/loss.  A module that defines `validation_step` / `test_step` (the reference's
+        hooks, medmoe_module.py:114-134) is evaluated through them; any other through `model_step`."""
         model.eval()
+        step_fn = getattr(model, step, None)
         tot, n = 0.0, 0
         for i, batch in enumerate(datamodule.val_dataloader()):
             if self.limit_val_batches is not None and i >= self.limit_val_batches:
                 break
-            out = model.model_step(self._to_device(datamodule, model, batch))
+            b = self._to_device(datamodule, model, batch)
+            out = step_fn(b, i) if callable(step_fn) else model.model_step(b)
             tot += float(out["loss"]); n += 1
         val = tot / n if n else math.nan
         if self.world_size > 1:
@@ -220,4 +224,4 @@ class Trainer:
         """Lightning's `trainer.test(ckpt_path=best)` evaluates THAT checkpoint, not the last weights."""
         if ckpt_path:
             model.load_state_dict(torch.load(ckpt_path, map_location="cpu", weights_only=True)["state_dict"])
-        return self.validate(model, datamodule)
+        return self.validate(model, datamodule, step="test_step")

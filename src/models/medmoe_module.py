@@ -136,10 +136,9 @@ class MedMoEPretrainingLightningModule(_Base):
         self._fused_clip = float(gradient_clip_val) if gradient_clip_val else None
         self.model.engine.cfg.clip = self._fused_clip if self._fused_clip is not None else 0.0
 
-    def fused_training_step(self, batch: Dict[str, Any], optimizer_step: bool = True, zero_grad: bool = True, loss_scale: float = 1.0):
-        """One micro-batch through Engine.train_step; returns the reference's loss names (device scalars)."""
-        if not self.fused_step:
-            raise RuntimeError("fused_training_step: construct the module with fused_step=True (model.fused_step=true)")
+    def _fused_engine(self):
+        """The engine a fused step runs on: the SwinEngine around the reference's encoder (arch = swin_t) or the ViT Engine, its working
+        copies and learning rate brought up to date."""
         m = self.model
         if getattr(m, "swin", None) is not None:
             from medmoe_amd.swin_engine import SwinEngine
@@ -153,6 +152,11 @@ class MedMoEPretrainingLightningModule(_Base):
             eng = m.engine
         if self._fused_opt is not None:                              # the scheduler acts on this optimizer's lr; the engine applies it
             eng.cfg.lr = float(self._fused_opt.param_groups[0]["lr"])
+        return eng
+
+    @staticmethod
+    def _engine_batch(batch: Dict[str, Any]) -> Dict[str, torch.Tensor]:
+        """The module's batch (image, caption = dict(ids, attn_mask[, token_type]) or an ids tensor, label) as the engine takes it."""
         cap = batch["caption"]
         if isinstance(cap, dict):
             ids, mask, tt = cap["ids"], cap["attn_mask"], cap.get("token_type")
@@ -163,9 +167,38 @@ class MedMoEPretrainingLightningModule(_Base):
         eb = {"image": batch["image"].contiguous(), "ids": ids, "attn_mask": mask, "label": batch["label"]}
         if tt is not None:
             eb["token_type"] = tt
+        return eb
+
+    def fused_training_step(self, batch: Dict[str, Any], optimizer_step: bool = True, zero_grad: bool = True, loss_scale: float = 1.0):
+        """One micro-batch through Engine.train_step; returns the reference's loss names (device scalars)."""
+        if not self.fused_step:
+            raise RuntimeError("fused_training_step: construct the module with fused_step=True (model.fused_step=true)")
+        eng, eb = self._fused_engine(), self._engine_batch(batch)
         out = eng.train_step(eb, optimizer=optimizer_step, zero_grad=zero_grad, loss_scale=loss_scale)
         return {"loss": out["loss"], "l_loss": out["l_loss"], "g_loss": out["g_loss"], "classifier_loss": out["classifier_loss"],
                 "classifier_acc": out["classifier_acc"]}
+
+    def fused_eval_step(self, batch: Dict[str, Any]):
+        """One batch through Engine.eval_step - the losses of `fused_training_step` forward only, nothing of the model or the optimiser
+        state written; returns the reference's loss names (device scalars).  With vision.arch = swin_t the batch takes the `model_step`
+        route under no_grad: a SwinEngine.eval_step is a separate piece of work."""
+        if not self.fused_step:
+            raise RuntimeError("fused_eval_step: construct the module with fused_step=True (model.fused_step=true)")
+        if getattr(self.model, "swin", None) is not None:
+            with torch.no_grad():
+                return self.model_step(batch)
+        out = self._fused_engine().eval_step(self._engine_batch(batch))
+        return {"loss": out["loss"], "l_loss": out["l_loss"], "g_loss": out["g_loss"], "classifier_loss": out["classifier_loss"],
+                "classifier_acc": out["classifier_acc"]}
+
+    def validation_step(self, batch, batch_idx: int = 0):                                # :114-125
+        """The loss dict of a validation batch (`val/loss` is its "loss"): Engine.eval_step in fused mode, `model_step` otherwise."""
+        if self.fused_step:
+            return self.fused_eval_step(batch)
+        return self.model_step(batch)
+
+    def test_step(self, batch, batch_idx: int = 0):                                      # :127-134
+        return self.validation_step(batch, batch_idx)
 
     # ---- fused mode: the optimiser state lives in the engine's flat stores, not in a torch optimizer -----------------------------------
     def _fused_stores(self) -> Dict[str, Any]:
