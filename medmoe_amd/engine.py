@@ -17,7 +17,8 @@ import torch
 
 from . import ops
 from .local_generic import GenericLocalLoss
-from .local_transposed import TransposedLocalLoss, local_sim_forward, ragged_layout  # noqa: F401  (ragged_layout: the [region][word] path and the tests use it from here)
+from .local_ragged import RaggedLocalLoss
+from .local_transposed import TransposedLocalLoss, local_sim_forward, ragged_layout  # noqa: F401  (ragged_layout: the tests and tools use it from here)
 from .config import MedMoEConfig
 from .params import ParamStore
 
@@ -92,8 +93,8 @@ class Engine:
         self.ws: Dict[str, torch.Tensor] = {}
         self.rank, self.world = 0, 1
         self._seg = None; self._cap_host = None; self._cap_event = None; self.cap_lens = None
-        self._tl = None                                              # TransposedLocalLoss over this engine's workspace
-        self._tlg = None                                             # ... against the gathered captions (cfg.local_loss_global)
+        self._local = None                                           # THE local-loss object of the current (batch size, world, mode): _local_loss_object
+        self._gle = None                                             # GenericLocalLoss of eval_step at 256 regions (its forward launches only)
         self.dist = False        # take the data-parallel exchange steps (all-gather / reduce-scatter / bucketed all-reduce)
         if torch.distributed.is_available() and torch.distributed.is_initialized():
             self.rank, self.world = torch.distributed.get_rank(), torch.distributed.get_world_size()
@@ -111,14 +112,9 @@ class Engine:
             from .text_params import TextStore
             self.tstore = TextStore(cfg, self.device, self.params.text)
             self.params.text = self.tstore.as_dict()             # views of the flat buffers: an optimiser step updates them in place
-        self._tlw = None                                             # TransposedLocalLoss in word-gradient mode (own buffers)
-        self._glw = None                                             # GenericLocalLoss in word-gradient mode (other geometries)
-        self._gle = None                                             # GenericLocalLoss of eval_step at 256 regions (its forward launches only)
-        self._ev_g = None                                            # eval_step against the gathered captions: word norms, similarities
-        self.local_dense = False
         self.HWp, self.Tp, self.GW = ops.local_geometry(cfg.n_patch, cfg.max_len)
         # LDS-tiled pair kernels exist for 64 / 208 / 256 regions; any other geometry (576 regions of ViT-L/14 at 336 px) runs
-        # the generic GEMM formulation (_local_loss_generic)
+        # the generic GEMM formulation (medmoe_amd/local_generic.py)
         self.text_varlen = os.environ.get("MEDMOE_TEXT_VARLEN", "1") != "0" and not self.train_text
         self.local_fast = ops.local_fast_path(cfg.n_patch, cfg.max_len)
         # transposed pair matrices + one wave per (image, caption, word tile): geometries pair3.hip is instantiated for (196 / 64
@@ -128,6 +124,8 @@ class Engine:
         # the per-image Gram gradient from ONE operand: the backward pair launch stores a row weight per word instead of the U matrix
         # (MEDMOE_LOCAL_GRAM=0: the two-operand form, for A/B runs)
         self.local_gram = self.local_t and os.environ.get("MEDMOE_LOCAL_GRAM", "1") != "0"
+        # region columns stored per (word, image) in the transposed pair matrices (MEDMOE_PAIR_PITCH, for A/B runs; default HWp)
+        self.HWq = int(os.environ.get("MEDMOE_PAIR_PITCH", self.HWp))
         # gradient buckets in flat-buffer order: [embeddings | layer 0 | ... | layer L-1 | final LN + router + experts]
         off = self.params.offsets
         self.bucket_bounds = [0] + [off[f"vit.layer.{l}.attention_layernorm.weight"] for l in range(cfg.n_layer_v)] \
@@ -154,6 +152,7 @@ class Engine:
         c, dev = self.cfg, self.device
         self.B = B
         ws = self.ws = {}
+        self._local = self._gle = None                       # sized for the old batch: released with the old workspace
         Nt, Dv, P, L = c.n_tok_v, c.d_v, c.n_patch, c.n_layer_v
         M = B * Nt
         H = c.n_head_v
@@ -225,68 +224,8 @@ class Engine:
         if self.dist:
             buf("nb2", (Bg,), F32); buf("na2", (B,), F32); buf("S2", (B, Bg), F32); buf("dS2", (B, Bg), F32)
             buf("cb2", (Bg,), F32); buf("ca2", (B,), F32); buf("d_img_all", (Bg, Do), F32)
-        # local loss
-        HWp, Tp, GW = self.HWp, self.Tp, self.GW
-        Kmax = (B * Tp + 63) // 64 * 64      # widest ragged row: every caption in the longest class, rounded up to the GEMM k-step
-        buf("wn", (B, T), F32)
-        if not self.local_fast:
-            buf("wT", (Dt, Kmax))
+        # local loss: the similarity matrix and the heads' d loss / d sim; every other buffer belongs to the local-loss object
         buf("sim", (B, B), F32); buf("gsim", (B, B), F32)
-        buf("l_lse", (B * HWp, B), F32); ws["dC32"] = torch.zeros(B * HWp, Do, device=dev, dtype=F32)
-        if self.local_fast:
-            # the three ragged pair matrices [B*HWp, Kp] are sized from the batch's own sum of pad16(caption length) (plus 10 %
-            # head-room, grown when a later batch is longer) instead of the B*Tp worst case: 3 x 24 GB instead of 3 x 35 GB at
-            # B = 1024 with lengths uniform in 8..77 (_pair_buffers)
-            self._pair_cap = 0
-            ws["gmp"] = torch.zeros(B * HWp, GW, device=dev, dtype=BF)
-            buf("dGm", (B * HWp, HWp))
-            if self.local_t:       # plain Gram matrices [B][GR][GR] (zero outside [P][P]: written once here, the GEMM only fills [P][P])
-                GR = (P + 31) // 32 * 32
-                ws["gm3"] = torch.zeros(B * GR, GR, device=dev, dtype=BF)
-                arg = torch.arange(B * P, device=dev)
-                ws["gm3_crowmap"] = (arg // P * GR + arg % P).to(I32)
-                # region columns stored per (word, image) in the pair matrices: HWp (208 for 196 regions).  MEDMOE_PAIR_PITCH=224 makes
-                # every 64-byte wave segment 64-byte aligned (448-byte rows); measured on one box at batch 1024: pair launches 36.3 ->
-                # 37.1 ms and 7.7 % more GEMM work, step 234.6 -> 241.2 ms - not used
-                Q = self.HWq = int(os.environ.get("MEDMOE_PAIR_PITCH", HWp))
-                if Q % 8 or not P <= Q <= GR:
-                    raise ValueError(f"MEDMOE_PAIR_PITCH={Q}: need a multiple of 8 in [{P}, {GR}]")
-                buf("dGm32", (B, Q, Q), F32); buf("dGmq", (B * Q, Q)); ws["dC32q"] = torch.zeros(B * Q, Do, device=dev, dtype=F32)
-                ws["rowoff_q"] = (torch.arange(B + 1, device=dev) * Q).to(I32)
-                arq = torch.arange(B * Q, device=dev)
-                ws["ctx_xmap_q"] = (arq // Q * P + torch.clamp(arq % Q, max=P - 1)).to(I32)
-        else:       # generic path: word log-probabilities, weighted contexts and their gradients
-            buf("l_dS", (B * HWp, Kmax)); buf("l_A", (B * HWp, Kmax))
-            buf("l_LP", (B * HWp, Kmax)); buf("l_WC", (B, Kmax, Do), F32); buf("l_DWC", (B, Kmax, Do)); buf("l_DWCt", (B, Do, Kmax))
-            buf("l_stats", (B, Kmax, 4), F32); buf("l_sume", (B, B), F32); buf("dC32b", (B * HWp, Do), F32)
-            ws["l_members"] = torch.arange(B, device=dev, dtype=I32)
-            ws["l_col"] = (torch.arange(B, device=dev) * Tp).to(I32); ws["l_tp"] = torch.full((B,), Tp, device=dev, dtype=I32)
-            ws["l_trtab"] = torch.tensor([[b * Kmax * Do, b * Kmax * Do, Kmax, Do] for b in range(B)], device=dev, dtype=torch.int64)
-            # region rows without padding (576 = 36 x 16): the backward's per-image GEMMs on 256-row tiles, the context gradient through a
-            # residual epilogue (medmoe_amd/local_generic.py, the same form)
-            self.local_dense = HWp == P and Do >= 128 and Do % 64 == 0 and Kmax >= 128
-            if self.local_dense:
-                tl = [[b, m, (b + 1) * HWp, 0] for b in range(B) for m in range(b * HWp, (b + 1) * HWp, 256)]
-                ws["imgp_tiles256g"] = torch.tensor(tl, device=dev, dtype=I32); ws["imgp_tile256g_count"] = torch.tensor([len(tl)], device=dev, dtype=I32)
-                buf("l_X1", (B * HWp, Do))
-        # static per-image group tables
-        tl = []
-        for b in range(B):
-            for m in range(b * P, (b + 1) * P, 128):
-                tl.append([b, m, (b + 1) * P, 0])
-        ws["img_tiles"] = torch.tensor(tl, device=dev, dtype=I32); ws["img_tile_count"] = torch.tensor([len(tl)], device=dev, dtype=I32)
-        ar = torch.arange(B * P, device=dev)
-        ws["gm_crowmap"] = (ar // P * HWp + ar % P).to(I32)
-        tl = []
-        for b in range(B):
-            for m in range(b * HWp, (b + 1) * HWp, 128):
-                tl.append([b, m, (b + 1) * HWp, 0])
-        ws["imgp_tiles"] = torch.tensor(tl, device=dev, dtype=I32); ws["imgp_tile_count"] = torch.tensor([len(tl)], device=dev, dtype=I32)
-        tl = [[b, b * HWp, (b + 1) * HWp, 0] for b in range(B)] if HWp <= 256 else []      # one 256-row tile per image
-        ws["imgp_tiles256"] = torch.tensor(tl, device=dev, dtype=I32).reshape(-1, 4); ws["imgp_tile256_count"] = torch.tensor([len(tl)], device=dev, dtype=I32)
-        ws["imgp_row_off"] = (torch.arange(B + 1, device=dev) * HWp).to(I32)
-        arp = torch.arange(B * HWp, device=dev)
-        ws["ctx_xmap"] = (arp // HWp * P + torch.clamp(arp % HWp, max=P - 1)).to(I32)
 
     # ------------------------------------------------------------------------------------------
     # image tower forward (ViT blocks = transformer.py:98-114 pre-norm; embeddings build-defined)
@@ -685,215 +624,88 @@ class Engine:
                 ops.call("add_rowscaled", ws["d_txt_g"], txt_g, ws["ca2"], B, Do)
                 ws["d_txt_g"].add_(D_.scatter_key_grads(ws["d_txt_all"]))
 
-    def forward_backward_losses(self, labels: torch.Tensor, loss_scale: float = 1.0):
-        c, ws = self.cfg, self.ws
-        B, P, Do, T = self.B, c.n_patch, c.d_out, c.max_len
-        self.global_loss(loss_scale)
-        lp = ws["loss_parts"]
-        # ---- GLoRIA local (losses.py:961-1026) ----
-        HWp, Tp, GW = self.HWp, self.Tp, self.GW
-        ctx = ws["img_l"].view(B * P, Do)
-        self._d_words = None
+    def _local_loss_object(self):
+        """THE local-loss object (GLoRIA local loss, losses.py:961-1026) of this engine for the current batch size, created on first use,
+        and whether it scores this rank's images against the gathered captions of every rank (cfg.local_loss_global):
+        a trainable text tower takes the word-gradient variant - transposed pair matrices (medmoe_amd/local_transposed.py) where
+        pair3.hip has the geometry, else the generic GEMM formulation (local_generic.py); geometries without LDS-tiled pair kernels the
+        generic one; gathered captions and 196 / 64 regions the transposed one; 256 regions the [region][word] one (local_ragged.py).
+        Each owns its buffers; only ws["sim"] (for B captions) is the engine's."""
+        c, B = self.cfg, self.B
+        gather = self.dist and c.local_loss_global
+        word_grad, Bc = self.train_text, B
         if self.train_text:
-            if self.dist and c.local_loss_global:
+            if gather:
                 raise NotImplementedError("trainable text tower: the word gradient of the local loss is built for rank-local captions "
                                           "(local_loss_global gathers them)")
-            if self.local_t:
-                return self._local_loss_transposed_words(loss_scale)
-            return self._local_loss_generic_words(loss_scale)
-        if not self.local_fast:
-            return self._local_loss_generic(loss_scale)
-        if self.dist and c.local_loss_global:
+            kind, gather = (TransposedLocalLoss if self.local_t else GenericLocalLoss), False
+        elif not self.local_fast:
+            kind, gather = GenericLocalLoss, False
+        elif gather:
             if not self.local_t:
                 raise NotImplementedError("local_loss_global needs the transposed local-loss path (196 / 64 regions)")
-            return self._local_loss_global(loss_scale)
-        if self.local_t:
-            return self._local_loss_transposed(loss_scale)
-        # RAGGED pair matrices: the [B*HWp, B*Tp] score / gradient matrices are the largest tensors of the step
-        # (3 x 35 GB at B = 1024) and most of their columns are caption padding.  Captions are grouped into
-        # length classes (<= 16, 32, ... words); class c stores its members side by side, 16*c columns each, so a
-        # row is Kp = sum_i pad16(len_i) (rounded up to 64) columns instead of B*Tp.  Needs the lengths on the
-        # host: ONE small device-to-host copy per step (the only host sync of the step).
-        perm, col_of_cap, ntts, cap_of_chunk, classes, Kc, Kp = ragged_layout(self._cap_lens_host(), T, Tp)
-        meta = torch.from_numpy(np.concatenate((perm, col_of_cap, 16 * ntts, cap_of_chunk)).astype(np.int32)).to(self.device, non_blocking=True)
-        d_perm, d_col, d_tp, d_chunk = meta[:B], meta[B:2 * B], meta[2 * B:3 * B], meta[3 * B:]
-        self._pair_buffers(Kp)
-        rag = lambda name: ws[name].view(-1)[:B * HWp * Kp].view(B * HWp, Kp)
-        lA, ldS, lU = rag("l_A"), rag("l_dS"), rag("l_U")
-        wT = ws["wT"].view(-1)[:Do * Kp].view(Do, Kp)
-        if Kp > Kc:
-            for t_ in (lA, ldS, lU, wT):
-                t_[:, Kc:].zero_()
-        ops.call("words_prep_ragged", ws["words"], ws["wn"], wT, B, T, Tp, Do, d_col, d_tp, Kp)
-        ops.gemm_nt(ctx, ctx, ws["gmp"], c_rowmap=ws["gm_crowmap"], tiles=ws["img_tiles"], tile_count=ws["img_tile_count"],
-                    max_tiles=ws["img_tiles"].shape[0], stride_b=P * Do, M=B * P, N=P, col_perm=True)
-        for ntt, start, n_c, cbase in classes:
-            members = d_perm[start:start + n_c]
-            # all word-region scores of the class as ONE tiled GEMM with the word-softmax fused (A1 + row LSE); the
-            # A1 tiles live in the l_A buffer (each pair's tile is read before the same workgroup overwrites it)
-            ops.call("local_scores_ragged", ctx, ws["words"], self.cap_lens, lA, ws["l_lse"], B, B, P, T, Do, members, n_c, ntt, cbase, Kp)
-            # single pass over the (image, caption) pairs: sim AND the gradients for dL/dsim = 1 ...
-            ops.call("local_pair2_ragged", lA, ws["l_lse"], ws["gmp"], ws["wn"], self.cap_lens, None, ws["sim"], ldS, lU,
-                     B, B, P, T, c.temp1, c.temp2, 1e-8, members, n_c, ntt, cbase, Kp)
-        wl = c.w_local * loss_scale / B
-        self._head(ws["sim"], ws["gsim"], B, 1, wl, 0, lp[3:])
-        self._head(ws["sim"], ws["gsim"], 1, B, wl, 1, lp[3:])
-        # ... then the CE over the sim matrix supplies the per-pair factor
-        ops.call("scale_blocks_ragged", ldS, lU, ws["gsim"], B, B, HWp, d_chunk, Kp)
-        ops.gemm_nt(ldS, wT, ws["dC32"])                                                    # dC = dS . W
-        if Kp >= 128 and ws["imgp_tiles256"].shape[0]:                                      # dGm_b = U_b A_b^T
-            ops.gemm_nt(lU, lA, ws["dGm"], tiles=ws["imgp_tiles256"], tile_count=ws["imgp_tile256_count"], max_tiles=B,
-                        stride_b=HWp * Kp, M=B * HWp, N=HWp, tile_rows=256)
+            kind, Bc = TransposedLocalLoss, B * self.world
         else:
-            ops.gemm_nt(lU, lA, ws["dGm"], tiles=ws["imgp_tiles"], tile_count=ws["imgp_tile_count"],
-                        max_tiles=ws["imgp_tiles"].shape[0], stride_b=HWp * Kp, M=B * HWp, N=HWp)
-        ops.gemm_tn(ws["dGm"], ctx, ws["dC32"].view(B, HWp, Do), x_rowmap=ws["ctx_xmap"], row_off=ws["imgp_row_off"], n_groups=B,
-                    stride_w=HWp * Do, nsplit=1, M=B * HWp)                                  # dC_b += dGm_b . ctx_b
-        ops.call("unpad_cast", ws["dC32"], ws["d_img_l"], B, P, HWp, Do)
+            kind = TransposedLocalLoss if self.local_t else RaggedLocalLoss
+        loc = self._local
+        if type(loc) is not kind or (loc.B, loc.Bc) != (B, Bc):
+            self._local = None                                    # release before allocating
+            args = (B, c.n_patch, c.max_len, c.d_out, self.device)
+            sim = self.ws["sim"] if Bc == B else None
+            if kind is TransposedLocalLoss:
+                self._local = kind(*args, gram=self.local_gram, Bc=Bc, word_grad=word_grad, pitch=self.HWq, sim=sim)
+            elif kind is GenericLocalLoss:
+                self._local = kind(*args, word_grad=word_grad, sim=sim)
+            else:
+                self._local = kind(*args, sim=sim)
+        return self._local, gather
 
-    def _local_loss_transposed(self, loss_scale: float):
-        """GLoRIA local loss (losses.py:961-1026) on TRANSPOSED ragged pair matrices [Kp caption-word rows][B*HWp region columns]
-        (csrc/pair3.hip, medmoe_amd/local_transposed.py): forward launches -> head over the similarity matrix (cross-entropy or
-        Soft-GLoRIA) -> backward launches and the two wgrad-shaped GEMMs.  The pair matrices are views of l_dS / l_A (/ l_U)."""
+    def _local_heads(self, sim, gsim, w: float):
+        """The two heads of the local loss (_head) over the rows, then the columns of `sim`: w times their sum is added to loss_parts[3],
+        d loss / d sim is left in `gsim`."""
+        B, lp = self.B, self.ws["loss_parts"]
+        self._head(sim, gsim, B, 1, w, 0, lp[3:])
+        self._head(sim, gsim, 1, B, w, 1, lp[3:])
+
+    def _gathered_local_heads(self, sim, w: float):
+        """The rank's [B, B_g] block of similarities is all-gathered into the [B_g, B_g] matrix (rows = images in rank order, columns =
+        captions) and both cross-entropies run over it on every rank (1 M elements) -> d loss / d of the whole matrix."""
+        from . import dist as D_
+        c, Bg, lp = self.cfg, self.B * self.world, self.ws["loss_parts"]
+        S = D_.gather_rows(sim)
+        G = torch.empty_like(S)
+        ops.call("ce_strided", S, G, Bg, Bg, Bg, 1, 0, c.temp3, w, 0, lp[3:])
+        ops.call("ce_strided", S, G, Bg, Bg, 1, Bg, 0, c.temp3, w, 1, lp[3:])
+        return G
+
+    def forward_backward_losses(self, labels: torch.Tensor, loss_scale: float = 1.0):
+        """Global and local GLoRIA losses of ws["img_g"] / ws["img_l"] against ws["txt_g"] / ws["words"], forward and backward: the weighted
+        values in ws["loss_parts"], the gradients in ws["d_img_g"] / ws["d_img_l"] (and ws["d_txt_g"] / self._d_words with a trainable
+        text tower)."""
         c, ws, B = self.cfg, self.ws, self.B
-        lp = ws["loss_parts"]
-        if self._tl is None or self._tl.B != B or self._tl.ws is not ws:
-            self._tl = TransposedLocalLoss(B, c.n_patch, c.max_len, c.d_out, self.HWp, self.Tp, self.HWq, self.device, ws,
-                                           self._pair_buffers, self.local_gram)
-        self._tl.forward(ws["img_l"].view(B * c.n_patch, c.d_out), ws["words"], self.cap_lens, self._cap_lens_host(), c.temp1, c.temp2)
-        wl = c.w_local * loss_scale / B
-        self._head(ws["sim"], ws["gsim"], B, 1, wl, 0, lp[3:])
-        self._head(ws["sim"], ws["gsim"], 1, B, wl, 1, lp[3:])
-        self._tl.backward(ws["gsim"], ws["d_img_l"])
+        self.global_loss(loss_scale)
+        loc, gather = self._local_loss_object()
+        ctx = ws["img_l"].view(B * c.n_patch, c.d_out)
+        if gather:
+            return self._local_loss_global(loc, ctx, loss_scale)
+        lens = (self.cap_lens, self._cap_lens_host()) if loc.host_lens else (self.cap_lens,)     # the ONE host sync of the step, where needed
+        sim = loc.forward(ctx, ws["words"], *lens, c.temp1, c.temp2)
+        self._local_heads(sim, ws["gsim"], c.w_local * loss_scale / B)
+        self._d_words = loc.backward(ws["gsim"], out=ws["d_img_l"])
 
-    def _local_loss_transposed_words(self, loss_scale: float):
-        """The same loss with the word embeddings differentiated too (trainable text tower): `TransposedLocalLoss` in its word-gradient mode
-        (row-major pair matrices of its own; d words = dS . ctx + the word-norm term, medmoe_amd/local_transposed.py)."""
-        c, ws, B = self.cfg, self.ws, self.B
-        lp = ws["loss_parts"]
-        if self._tlw is None or self._tlw.B != B:
-            self._tlw = TransposedLocalLoss.standalone(B, c.n_patch, c.max_len, c.d_out, self.device, word_grad=True)
-        tl = self._tlw
-        sim = tl.forward(ws["img_l"].view(B * c.n_patch, c.d_out), ws["words"], self.cap_lens, self._cap_lens_host(), c.temp1, c.temp2)
-        ws["sim"].copy_(sim)
-        wl = c.w_local * loss_scale / B
-        self._head(ws["sim"], ws["gsim"], B, 1, wl, 0, lp[3:])
-        self._head(ws["sim"], ws["gsim"], 1, B, wl, 1, lp[3:])
-        self._d_words = tl.backward(ws["gsim"], ws["d_img_l"])
-
-    def _local_loss_generic_words(self, loss_scale: float):
-        """The word-gradient loss at a geometry without the transposed pair kernels (576 / 256 regions, any other): `GenericLocalLoss` in its
-        word-gradient mode (own buffers; d words = dS^T ctx + the cosine term, medmoe_amd/local_generic.py)."""
-        c, ws, B = self.cfg, self.ws, self.B
-        lp = ws["loss_parts"]
-        if self._glw is None or self._glw.B != B:
-            self._glw = GenericLocalLoss(B, c.n_patch, c.max_len, c.d_out, self.device, word_grad=True)
-        gl = self._glw
-        sim = gl.forward(ws["img_l"].view(B * c.n_patch, c.d_out), ws["words"], self.cap_lens, c.temp1, c.temp2)
-        ws["sim"].copy_(sim)
-        wl = c.w_local * loss_scale / B
-        self._head(ws["sim"], ws["gsim"], B, 1, wl, 0, lp[3:])
-        self._head(ws["sim"], ws["gsim"], 1, B, wl, 1, lp[3:])
-        d_ctx, self._d_words = gl.backward(ws["gsim"])
-        ws["d_img_l"].view(B * c.n_patch, c.d_out).copy_(d_ctx)
-
-    def _local_loss_global(self, loss_scale: float):
+    def _local_loss_global(self, loc, ctx, loss_scale: float):
         """cfg.local_loss_global under data parallelism: this rank's images against the captions of every rank (the
         variant the reference does not have - its local loss stays rank-local, losses.py:961-1026).  Words and caption lengths are
-        all-gathered (the text tower is frozen: no gradient goes back), the rank's [B, B_g] block of similarities is all-gathered into
-        the [B_g, B_g] matrix, both cross-entropies run over it on every rank (1 M elements), and the rank back-propagates its own
-        rows.  Gradients are averaged over ranks afterwards, so the rows carry W / B_g = 1 / B."""
+        all-gathered (the text tower is frozen: no gradient goes back), the heads run over the gathered similarities, and the rank
+        back-propagates its own rows.  Gradients are averaged over ranks afterwards, so the rows carry W / B_g = 1 / B."""
         from . import dist as D_
         c, ws, B, W = self.cfg, self.ws, self.B, self.world
-        Bg = B * W
-        lp = ws["loss_parts"]
         words_all = D_.gather_rows(ws["words"])
         caps_all = D_.gather_rows(self.cap_lens)
-        caps_host = caps_all.cpu().numpy().astype(np.int64)
-        if self._tlg is None or self._tlg.B != B or self._tlg.Bc != Bg:
-            self._tlg = TransposedLocalLoss.standalone(B, c.n_patch, c.max_len, c.d_out, self.device, self.local_gram, Bc=Bg)
-        sim = self._tlg.forward(ws["img_l"].view(B * c.n_patch, c.d_out), words_all, caps_all, caps_host, c.temp1, c.temp2)
-        S = D_.gather_rows(sim)                                       # [B_g, B_g]: rows = images in rank order, columns = captions
-        G = torch.empty_like(S)
-        wl = c.w_local * loss_scale / Bg
-        ops.call("ce_strided", S, G, Bg, Bg, Bg, 1, 0, c.temp3, wl, 0, lp[3:])
-        ops.call("ce_strided", S, G, Bg, Bg, 1, Bg, 0, c.temp3, wl, 1, lp[3:])
+        sim = loc.forward(ctx, words_all, caps_all, caps_all.cpu().numpy().astype(np.int64), c.temp1, c.temp2)
+        G = self._gathered_local_heads(sim, c.w_local * loss_scale / (B * W))
         r0 = D_.label_offset(B)
-        self._tlg.backward((G[r0:r0 + B] * float(W)).contiguous(), ws["d_img_l"])
-
-    def _pair_buffers(self, Kp: int):
-        """(Re)allocate the ragged pair matrices for rows of Kp columns (capacity grows by 10 % steps, never above B*Tp)."""
-        if Kp <= self._pair_cap:
-            return
-        ws, B = self.ws, self.B
-        Kmax = (B * self.Tp + 63) // 64 * 64
-        cap = min(Kmax, (int(Kp * 1.1) + 63) // 64 * 64)
-        for name in ("l_A", "l_dS", "l_U", "wT", "words_r", "l_stats3", "l_d2"):
-            ws.pop(name, None)                                 # release before allocating: the old and new sets must not coexist
-        rows = B * (max(self.HWp, self.HWq) if self.local_t else self.HWp)
-        for name in (("l_A", "l_dS") if (self.local_t and self.local_gram) else ("l_A", "l_dS", "l_U")):
-            ws[name] = torch.empty((rows, cap), device=self.device, dtype=BF)
-        ws["wT"] = torch.empty((self.cfg.d_t, cap), device=self.device, dtype=BF)
-        if self.local_t:
-            ws["words_r"] = torch.empty((cap, self.cfg.d_t), device=self.device, dtype=BF)
-            ws["l_stats3"] = torch.empty((B, cap, 2), device=self.device, dtype=torch.float32)
-            if self.local_gram:
-                ws["l_d2"] = torch.empty((B, cap), device=self.device, dtype=torch.float32)
-        self._pair_cap = cap
-
-    def _local_generic_forward(self):
-        """The forward launches of `_local_loss_generic`: word softmax, region attention, weighted contexts, cosines -> ws["sim"]."""
-        c, ws = self.cfg, self.ws
-        B, P, Do, T = self.B, c.n_patch, c.d_out, c.max_len
-        HWp, Tp = self.HWp, self.Tp
-        Kp = ws["l_A"].shape[1]                                   # B*Tp rounded up to the GEMM k-step
-        ctx = ws["img_l"].view(B * P, Do)
-        lp_, LA, DA, wT = ws["l_LP"], ws["l_A"], ws["l_dS"], ws["wT"]
-        if Kp > B * Tp:
-            for t_ in (lp_, LA, DA, wT):
-                t_[:, B * Tp:].zero_()
-            ws["l_DWC"][:, B * Tp:].zero_()
-        ops.call("words_prep_ragged", ws["words"], ws["wn"], wT, B, T, Tp, Do, ws["l_col"], ws["l_tp"], Kp)
-        ops.call("local_scores_ragged", ctx, ws["words"], self.cap_lens, lp_, ws["l_lse"], B, B, P, T, Do, ws["l_members"], B, Tp // 16, 0, Kp)
-        ops.call("local_gen_fwd_a", lp_, self.cap_lens, LA, B, B, P, HWp, T, Tp, c.temp1, Kp)
-        ws["l_WC"].zero_()
-        ops.gemm_tn(LA, ctx, ws["l_WC"], x_rowmap=ws["ctx_xmap"], row_off=ws["imgp_row_off"], n_groups=B, stride_w=Kp * Do, nsplit=1,
-                    M=B * HWp)                                    # wctx_b = A_b^T ctx_b
-        ops.call("local_gen_cos", ws["l_WC"], ws["words"], ws["wn"], self.cap_lens, ws["sim"], ws["l_stats"], ws["l_sume"], B, B, T, Tp, Do,
-                 c.temp2, 1e-8, Kp)
-
-    def _local_loss_generic(self, loss_scale: float):
-        """GLoRIA local loss for a geometry without LDS-tiled pair kernels (loss.hip "GENERIC-GEOMETRY"): the reference's own
-        formulation - weighted context = bmm(ctx, attn) (losses.py:732), cosine against the word (:690-695, :1002) - as grouped
-        GEMMs over the uniform pair matrices [B*HWp, B*Tp], plus four elementwise kernels."""
-        c, ws = self.cfg, self.ws
-        B, P, Do, T = self.B, c.n_patch, c.d_out, c.max_len
-        HWp, Tp = self.HWp, self.Tp
-        Kp = ws["l_A"].shape[1]                                   # B*Tp rounded up to the GEMM k-step
-        ctx = ws["img_l"].view(B * P, Do)
-        lp_, LA, DA, wT = ws["l_LP"], ws["l_A"], ws["l_dS"], ws["wT"]
-        lp = ws["loss_parts"]
-        self._local_generic_forward()
-        wl = c.w_local * loss_scale / B
-        self._head(ws["sim"], ws["gsim"], B, 1, wl, 0, lp[3:])
-        self._head(ws["sim"], ws["gsim"], 1, B, wl, 1, lp[3:])
-        ops.call("local_gen_dwctx", ws["l_WC"], ws["words"], ws["wn"], self.cap_lens, ws["gsim"], ws["l_stats"], ws["l_sume"], ws["l_DWC"],
-                 B, B, T, Tp, Do, c.temp2, 1e-8, Kp)
-        ops.call("transpose_many", ws["l_DWC"], ws["l_DWCt"], ws["l_trtab"], B, ((Kp + 63) // 64) * ((Do + 63) // 64))
-        if self.local_dense:
-            grp = dict(tiles=ws["imgp_tiles256g"], tile_count=ws["imgp_tile256g_count"], max_tiles=ws["imgp_tiles256g"].shape[0], M=B * HWp,
-                       tile_rows=256)
-            ops.gemm_nt(ctx, ws["l_DWC"], DA, stride_b=Kp * Do, N=Kp, **grp)                                # dA_b = ctx_b dwctx_b^T
-            ops.gemm_nt(LA, ws["l_DWCt"], ws["l_X1"], stride_b=Do * Kp, N=Do, **grp)                        # d ctx_b (direct) = A_b dwctx_b
-            ops.call("local_gen_bwd_s", lp_, LA, DA, self.cap_lens, B, B, P, HWp, T, Tp, c.temp1, Kp)       # dS over dA in place
-            ops.gemm_nt(DA, wT, ws["d_img_l"].view(B * P, Do), residual=ws["l_X1"])                         # d ctx = dS . W + the direct part
-            return
-        grp = dict(tiles=ws["imgp_tiles"], tile_count=ws["imgp_tile_count"], max_tiles=ws["imgp_tiles"].shape[0], M=B * HWp)
-        ops.gemm_nt(ctx, ws["l_DWC"], DA, a_rowmap=ws["ctx_xmap"], stride_b=Kp * Do, N=Kp, **grp)          # dA_b = ctx_b dwctx_b^T
-        ops.gemm_nt(LA, ws["l_DWCt"], ws["dC32b"], stride_b=Do * Kp, N=Do, **grp)                           # d ctx_b (direct) = A_b dwctx_b
-        ops.call("local_gen_bwd_s", lp_, LA, DA, self.cap_lens, B, B, P, HWp, T, Tp, c.temp1, Kp)           # dS over dA in place
-        ops.gemm_nt(DA, wT, ws["dC32"])                                                                     # d ctx += dS . W
-        ops.call("unpad_cast2", ws["dC32"], ws["dC32b"], ws["d_img_l"], B, P, HWp, Do)
+        self._d_words = loc.backward((G[r0:r0 + B] * float(W)).contiguous(), out=ws["d_img_l"])
 
     # ------------------------------------------------------------------------------------------
     # backward through MoE and the ViT
@@ -1135,43 +947,31 @@ class Engine:
                 "g_loss": lp[2] / c.w_global, "l_loss": lp[3] / c.w_local}
 
     def _local_loss_eval(self):
-        """GLoRIA local loss value (losses.py:961-1026) of ws["img_l"] against ws["words"] into loss_parts[3]; ws["gsim"] is the heads' scratch."""
+        """GLoRIA local loss value (losses.py:961-1026) of ws["img_l"] against ws["words"] into loss_parts[3]; ws["gsim"] is the heads' scratch.
+        The transposed object lends medmoe_local_sim_fwd its Gram matrices, tile tables and word norms - its pair matrices are not touched
+        (nor allocated, if no training step came before)."""
         c, ws, B = self.cfg, self.ws, self.B
         P, T, Do = c.n_patch, c.max_len, c.d_out
-        lp = ws["loss_parts"]
         ctx = ws["img_l"].view(B * P, Do)
-        gather = self.dist and c.local_loss_global
-        if gather and not self.local_t:
-            raise NotImplementedError("local_loss_global needs the transposed local-loss path (196 / 64 regions)")
-        if self.local_t:
-            tabs = dict(P=P, gm3=ws["gm3"], gm3_crowmap=ws["gm3_crowmap"], img_tiles=ws["img_tiles"], img_tile_count=ws["img_tile_count"])
-            if gather:
-                # this rank's images against the captions of every rank, both cross-entropies over the gathered [B_g, B_g] matrix
-                # (the heads of _local_loss_global)
-                from . import dist as D_
-                Bg = B * self.world
-                words_all = D_.gather_rows(ws["words"])
-                caps_all = D_.gather_rows(self.cap_lens)
-                if self._ev_g is None or self._ev_g[0].shape[0] != Bg or self._ev_g[1].shape[0] != B:
-                    self._ev_g = (torch.empty(Bg, T, device=self.device, dtype=F32), torch.empty(B, Bg, device=self.device, dtype=F32))
-                sim = local_sim_forward(ctx, words_all, caps_all, caps_all.cpu().numpy().astype(np.int64), c.temp1, c.temp2,
-                                        wn=self._ev_g[0], sim=self._ev_g[1], **tabs)
-                S = D_.gather_rows(sim)
-                G = torch.empty_like(S)
-                wl = c.w_local / Bg
-                ops.call("ce_strided", S, G, Bg, Bg, Bg, 1, 0, c.temp3, wl, 0, lp[3:])
-                ops.call("ce_strided", S, G, Bg, Bg, 1, Bg, 0, c.temp3, wl, 1, lp[3:])
-                return
-            local_sim_forward(ctx, ws["words"], self.cap_lens, self._cap_lens_host(), c.temp1, c.temp2, wn=ws["wn"], sim=ws["sim"], **tabs)
-        elif not self.local_fast:
-            self._local_generic_forward()
-        else:       # 256 regions: training uses the LDS-tiled pair kernels, whose forward and backward are one launch
-            if self._gle is None or self._gle.B != B:
-                self._gle = GenericLocalLoss(B, P, T, Do, self.device)
-            ws["sim"].copy_(self._gle.forward(ctx, ws["words"], self.cap_lens, c.temp1, c.temp2))
-        wl = c.w_local / B
-        self._head(ws["sim"], ws["gsim"], B, 1, wl, 0, lp[3:])
-        self._head(ws["sim"], ws["gsim"], 1, B, wl, 1, lp[3:])
+        loc, gather = self._local_loss_object()
+        words, caps = ws["words"], self.cap_lens
+        if gather:      # this rank's images against the captions of every rank, the heads of _local_loss_global
+            from . import dist as D_
+            words, caps = D_.gather_rows(words), D_.gather_rows(caps)
+        if isinstance(loc, TransposedLocalLoss):
+            caps_host = caps.cpu().numpy().astype(np.int64) if gather else self._cap_lens_host()
+            sim = local_sim_forward(ctx, words, caps, caps_host, c.temp1, c.temp2, P=P, gm3=loc.gm3, gm3_crowmap=loc.gm3_crowmap,
+                                    img_tiles=loc.img_tiles, img_tile_count=loc.img_tile_count, wn=loc.wn, sim=loc.sim)
+        elif isinstance(loc, GenericLocalLoss):
+            sim = loc.forward(ctx, words, caps, c.temp1, c.temp2)
+        else:           # 256 regions: training uses the LDS-tiled pair kernels, whose forward and backward are one launch
+            if self._gle is None:
+                self._gle = GenericLocalLoss(B, P, T, Do, self.device, sim=ws["sim"])
+            sim = self._gle.forward(ctx, words, caps, c.temp1, c.temp2)
+        if gather:
+            self._gathered_local_heads(sim, c.w_local / (B * self.world))
+        else:
+            self._local_heads(sim, ws["gsim"], c.w_local / B)
 
     def _forward_both(self, b):
         if self.overlap_wgrad and b["image"].is_cuda and self.B * self.cfg.n_tok_v <= 131072:

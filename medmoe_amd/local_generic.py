@@ -1,9 +1,10 @@
 """GLoRIA local loss (reference losses.py:961-1026) for ANY number of regions (the reference's Swin stage 0 has 3136; the LDS-tiled pair
 kernels hold 64 / 196 / 256 / 576): the reference's own formulation - weighted context = bmm(ctx, attn) (losses.py:732), cosine against the word
 (:690-695, :1002) - as grouped GEMMs over uniform pair matrices [B*HWp, B*Tp] plus four elementwise kernels (loss.hip "GENERIC-GEOMETRY").
-The same launch sequence as `Engine._local_loss_generic`, with its own buffers, so that `src.losses.GLORIALocalContrastiveLoss` can run it
-behind torch autograd for the Swin tower's 56 x 56 local features.  With `word_grad=True` the backward also differentiates the word
-embeddings (trainable text tower): the SwinEngine and the ViT Engine use it at geometries without the transposed pair kernels."""
+One implementation, with buffers of its own: `Engine.train_step` runs it at 576 regions (ViT-L/14 at 336 px), `src.losses.
+GLORIALocalContrastiveLoss` behind torch autograd and the SwinEngine for the Swin tower's 56 x 56 local features.  With `word_grad=True` the
+backward also differentiates the word embeddings (trainable text tower): the SwinEngine and the ViT Engine use it at geometries without
+the transposed pair kernels."""
 from typing import Optional
 
 import torch
@@ -14,11 +15,14 @@ BF, F32, I32 = torch.bfloat16, torch.float32, torch.int32
 
 
 class GenericLocalLoss:
-    def __init__(self, B: int, HW: int, T: int, D: int, device, word_grad: bool = False):
+    host_lens = False                                             # forward needs the caption lengths on the device only: no host synchronisation
+
+    def __init__(self, B: int, HW: int, T: int, D: int, device, word_grad: bool = False, sim: Optional[torch.Tensor] = None):
+        """sim: write the similarities into this fp32 [B, B] tensor of the caller's."""
         if T > 80 or D % 64:
             raise ValueError("GenericLocalLoss: at most 80 words per caption, embedding width a multiple of 64")
         dev = torch.device(device)
-        self.B, self.HW, self.T, self.D, self.dev = B, HW, T, D, dev
+        self.B, self.Bc, self.HW, self.T, self.D, self.dev = B, B, HW, T, D, dev
         HWp, Tp = (HW + 15) // 16 * 16, (T + 15) // 16 * 16
         Kp = (B * Tp + 63) // 64 * 64
         self.HWp, self.Tp, self.Kp = HWp, Tp, Kp
@@ -26,7 +30,7 @@ class GenericLocalLoss:
         self.lp, self.A, self.dS, self.wT = z(B * HWp, Kp), z(B * HWp, Kp), z(B * HWp, Kp), z(D, Kp)
         self.WC, self.DWC, self.DWCt = z(B, Kp, D, dt=F32), z(B, Kp, D), z(B, D, Kp)
         self.stats, self.sume, self.lse = z(B, Kp, 4, dt=F32), z(B, B, dt=F32), z(B * HWp, B, dt=F32)
-        self.wn, self.sim = z(B, T, dt=F32), z(B, B, dt=F32)
+        self.wn, self.sim = z(B, T, dt=F32), (z(B, B, dt=F32) if sim is None else sim)
         self.members = torch.arange(B, device=dev, dtype=I32)
         self.col = (torch.arange(B, device=dev) * Tp).to(I32); self.tp = torch.full((B,), Tp, device=dev, dtype=I32)
         self.trtab = torch.tensor([[b * Kp * D, b * Kp * D, Kp, D] for b in range(B)], device=dev, dtype=torch.int64)
@@ -86,10 +90,12 @@ class GenericLocalLoss:
         v = torch.as_strided(self.A, (B, T, HW), (HWp * Kp + Tp, 1, Kp))
         return v.float()
 
-    def backward(self, gsim: torch.Tensor, generation: Optional[int] = None):
+    def backward(self, gsim: torch.Tensor, generation: Optional[int] = None, out: Optional[torch.Tensor] = None):
         """gsim fp32 [B, B] = dL/dsim -> d ctx bf16 [B*HW, D]; word_grad instances return (d ctx, d words fp32 [B, T, D]) - the word gradient
         runs after d ctx and only reads, so d ctx is the same in both modes.  `generation`: the value of self.generation right after the
-        forward this backward belongs to - the pair matrices are consumed in place, a backward that arrives after ANOTHER forward is refused."""
+        forward this backward belongs to - the pair matrices are consumed in place, a backward that arrives after ANOTHER forward is refused.
+        out: bf16 [B, HW, D] of the caller's that receives d ctx; the call then returns d words alone (None unless word_grad), as the
+        other local-loss objects do."""
         if generation is not None and generation != self.generation:
             raise RuntimeError("GenericLocalLoss: backward of an earlier forward - the instance keeps ONE forward's pair matrices")
         B, HW, T, D, HWp, Tp, Kp = self.B, self.HW, self.T, self.D, self.HWp, self.Tp, self.Kp
@@ -97,22 +103,24 @@ class GenericLocalLoss:
         ops.call("local_gen_dwctx", self.WC, self.words, self.wn, self.cap, gsim, self.stats, self.sume, self.DWC, B, B, T, Tp, D,
                  self.t2, 1e-8, Kp)
         ops.call("transpose_many", self.DWC, self.DWCt, self.trtab, B, ((Kp + 63) // 64) * ((D + 63) // 64))
+        dctx = torch.empty(B * HW, D, device=self.dev, dtype=BF) if out is None else out.view(B * HW, D)
         if self.dense:
             grp = dict(tiles=self.tiles256, tile_count=self.tile256_count, max_tiles=self.tiles256.shape[0], M=B * HWp, tile_rows=256)
             ops.gemm_nt(self.ctx, self.DWC, self.dS, stride_b=Kp * D, N=Kp, **grp)                             # dA_b = ctx_b dwctx_b^T
             ops.gemm_nt(self.A, self.DWCt, self.X1, stride_b=D * Kp, N=D, **grp)                               # d ctx_b (direct) = A_b dwctx_b
             ops.call("local_gen_bwd_s", self.lp, self.A, self.dS, self.cap, B, B, HW, HWp, T, Tp, self.t1, Kp) # dS over dA in place
-            dctx = torch.empty(B * HW, D, device=self.dev, dtype=BF)
             ops.gemm_nt(self.dS, self.wT, dctx, residual=self.X1)                                              # d ctx = dS . W + the direct part
-            return (dctx, self._word_grad(gsim)) if self.word_grad else dctx
-        grp = dict(tiles=self.tiles, tile_count=self.tile_count, max_tiles=self.tiles.shape[0], M=B * HWp)
-        ops.gemm_nt(self.ctx, self.DWC, self.dS, a_rowmap=self.xmap, stride_b=Kp * D, N=Kp, **grp)            # dA_b = ctx_b dwctx_b^T
-        ops.gemm_nt(self.A, self.DWCt, self.dC32b, stride_b=D * Kp, N=D, **grp)                                # d ctx_b (direct) = A_b dwctx_b
-        ops.call("local_gen_bwd_s", self.lp, self.A, self.dS, self.cap, B, B, HW, HWp, T, Tp, self.t1, Kp)     # dS over dA in place
-        ops.gemm_nt(self.dS, self.wT, self.dC32)                                                               # d ctx += dS . W
-        dctx = torch.empty(B * HW, D, device=self.dev, dtype=BF)
-        ops.call("unpad_cast2", self.dC32, self.dC32b, dctx, B, HW, HWp, D)
-        return (dctx, self._word_grad(gsim)) if self.word_grad else dctx
+        else:
+            grp = dict(tiles=self.tiles, tile_count=self.tile_count, max_tiles=self.tiles.shape[0], M=B * HWp)
+            ops.gemm_nt(self.ctx, self.DWC, self.dS, a_rowmap=self.xmap, stride_b=Kp * D, N=Kp, **grp)        # dA_b = ctx_b dwctx_b^T
+            ops.gemm_nt(self.A, self.DWCt, self.dC32b, stride_b=D * Kp, N=D, **grp)                            # d ctx_b (direct) = A_b dwctx_b
+            ops.call("local_gen_bwd_s", self.lp, self.A, self.dS, self.cap, B, B, HW, HWp, T, Tp, self.t1, Kp) # dS over dA in place
+            ops.gemm_nt(self.dS, self.wT, self.dC32)                                                           # d ctx += dS . W
+            ops.call("unpad_cast2", self.dC32, self.dC32b, dctx, B, HW, HWp, D)
+        d_words = self._word_grad(gsim) if self.word_grad else None
+        if out is not None:
+            return d_words
+        return (dctx, d_words) if self.word_grad else dctx
 
     def _word_grad(self, gsim: torch.Tensor) -> torch.Tensor:
         """d loss / d words fp32 [B, T, D] from the pair matrices the backward left: dS (over dA) and WC / stats / sume of the forward."""

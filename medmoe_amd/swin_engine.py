@@ -99,9 +99,7 @@ class SwinEngine:
         lp = ws["loss_parts"]
         loc = self._local(B, HW, c.max_len, D)
         sim = loc.forward(local.view(B * HW, D), ws["words"], eng.cap_lens, c.temp1, c.temp2)
-        wl = c.w_local * loss_scale / B
-        eng._head(sim, self._gsim, B, 1, wl, 0, lp[3:])
-        eng._head(sim, self._gsim, 1, B, wl, 1, lp[3:])
+        eng._local_heads(sim, self._gsim, c.w_local * loss_scale / B)
         d_local = loc.backward(self._gsim)
         text_done = None
         if self.train_text:

@@ -211,7 +211,7 @@ class _GloriaLocalFn(torch.autograd.Function):
             tl = _TL_CACHE.get(key)
             if tl is None:
                 _TL_CACHE.clear()                                 # one geometry at a time: the pair matrices are large
-                tl = _TL_CACHE[key] = TransposedLocalLoss.standalone(B, HW, T, D, dev, word_grad=want_w)
+                tl = _TL_CACHE[key] = TransposedLocalLoss(B, HW, T, D, dev, word_grad=want_w)
             cap_host = cap.cpu().numpy() if torch.is_tensor(cap_lens) else [int(v) for v in cap_lens]
             att = torch.zeros(B, T, HW, device=dev)
             sim = tl.forward(ctx16, w16, cap, cap_host, temp1, temp2, att=att)

@@ -204,9 +204,13 @@ def test_an_engine_that_only_evaluates_allocates_no_pair_matrices():
     cfg, eng = _engine("cfg0")
     out = eng.eval_step(bench.synthetic_batch(cfg, 4, 9, eng.device))
     assert 0 < float(out["loss"]) < 100
-    assert eng.local_t and eng._pair_cap == 0 and not {"l_A", "l_dS", "l_U"} & set(eng.ws)
+    from medmoe_amd.local_transposed import TransposedLocalLoss
+    loc = eng._local                                                  # the engine's one local-loss object; no second formulation exists
+    assert eng.local_t and type(loc) is TransposedLocalLoss and eng._gle is None
+    assert loc.cap == 0 and not loc.pair and not {"l_A", "l_dS", "l_U"} & set(eng.ws)
     eng.train_step(bench.synthetic_batch(cfg, 4, 9, eng.device), optimizer=False)      # training on the same engine still sizes them
-    assert eng._pair_cap > 0 and "l_A" in eng.ws
+    assert eng._local is loc and loc.cap > 0 and "l_A" in loc.pair and "l_dS" in loc.pair
+    assert not {"l_A", "l_dS", "l_U"} & set(eng.ws)
 
 
 # --------------------------------------------------------------------------------------------------------------------------------------

@@ -141,7 +141,8 @@ def test_engine_trains_the_text_tower_at_generic_geometries(cfg_name):
     ref = O.model_step(batch, pr, ocfg, vocab)
     out = eng.train_step({k: v.cuda() for k, v in batch.items()}, optimizer=False)
     torch.cuda.synchronize()
-    assert eng._glw is not None and eng._tlw is None and eng._d_words is not None
+    from medmoe_amd.local_generic import GenericLocalLoss
+    assert type(eng._local) is GenericLocalLoss and eng._local.word_grad and eng._d_words is not None
     for k in ("g_loss", "l_loss"):
         assert abs(out[k].item() - ref[k].item()) < 1e-2 * abs(ref[k].item()), (k, out[k].item(), ref[k].item())
     P, Do, Hh = cfg.n_patch, cfg.d_out, int(cfg.n_patch ** 0.5)

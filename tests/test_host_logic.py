@@ -132,6 +132,46 @@ def test_engine_launch_sequence_region_word_layout(stub, monkeypatch):
     assert n.count("medmoe_attn_fwd") == cfg.n_layer_v + cfg.n_layer_t and n.count("medmoe_text_pack") == 0      # padded text tower
 
 
+_HOST_QUERIES = {"medmoe_local_geometry", "medmoe_local_fast_path", "medmoe_local_pair3_supported"}
+# (config, batch, environment, freeze_text): every local-loss formulation the engine can select on one rank
+_SEQUENCE_CASES = {
+    "tiny-transposed": ("tiny", 8, {}, True),
+    "cfg0-transposed": ("cfg0", 4, {}, True),
+    "tiny-ragged": ("tiny", 8, {"MEDMOE_LOCAL_PAIR3": "0"}, True),
+    "tinyL-ragged": ("tinyL", 8, {}, True),
+    "tinyL336-generic": ("tinyL336", 8, {}, True),
+    "tiny-transposed-words": ("tiny", 8, {}, False),
+    "tinyL-generic-words": ("tinyL", 8, {}, False),
+    "tinyL336-generic-words": ("tinyL336", 8, {}, False),
+}
+_SEQUENCE_IDS = [f"{k}:train_step" for k in _SEQUENCE_CASES] + [f"{k}:eval_step" for k, v in _SEQUENCE_CASES.items() if v[3]]
+
+
+@pytest.mark.parametrize("case", _SEQUENCE_IDS)
+def test_engine_launch_sequences_are_the_recorded_ones(stub, monkeypatch, case):
+    """The COMPLETE ordered list of entry points a step launches (the three host queries aside) equals the list recorded in
+    tests/golden/engine_launch_sequences.json, for every local-loss formulation in train_step and eval_step."""
+    import json
+    from medmoe_amd.config import config_by_name
+    from medmoe_amd.engine import Engine
+    key, step = case.split(":")
+    name, B, env, freeze_text = _SEQUENCE_CASES[key]
+    for k in ("MEDMOE_LOCAL_PAIR3", "MEDMOE_LOCAL_GRAM", "MEDMOE_PAIR_PITCH", "MEDMOE_TEXT_VARLEN", "MEDMOE_GRAPH", "MEDMOE_WGRAD_STAGED"):
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    cfg = config_by_name(name)
+    cfg.freeze_text = freeze_text
+    eng = Engine(cfg, "cpu")
+    batch = O.synthetic_batch(O.config_by_name(name), B, min_len=4)
+    del stub.calls[:]
+    getattr(eng, step)(batch)
+    got = [n for n in stub.calls if n not in _HOST_QUERIES]
+    with open(os.path.join(ROOT, "tests", "golden", "engine_launch_sequences.json")) as f:
+        want = json.load(f)[case]
+    assert got == want, next((i, a, b) for i, (a, b) in enumerate(zip(got + [None], want + [None])) if a != b)
+
+
 def test_segment_map_matches_oracle():
     from medmoe_amd.engine import VocabTables
     rng = np.random.default_rng(0)

@@ -56,7 +56,7 @@ def part_step(a):
     b = bench.synthetic_batch(cfg, a.batch, 777, eng.device)
     torch.cuda.reset_peak_memory_stats()
     ms = timed(lambda: eng.eval_step(b), a.warmup, a.iters, a.repeats)
-    return {"part": "eval_step", **stats(ms), "peak_mem_gb": round(torch.cuda.max_memory_allocated() / 2 ** 30, 3), "pair_cap": getattr(eng, "_pair_cap", None)}
+    return {"part": "eval_step", **stats(ms), "peak_mem_gb": round(torch.cuda.max_memory_allocated() / 2 ** 30, 3), "pair_cap": eng._local.cap}
 
 
 def part_local(a):
@@ -74,14 +74,14 @@ def part_local(a):
     ws, B, P, T, Do = eng.ws, a.batch, cfg.n_patch, cfg.max_len, cfg.d_out
     ctx, caps_host = ws["img_l"].view(B * P, Do), eng._cap_lens_host()
     sim_new = torch.empty(B, B, device=eng.device)
-    new = lambda: local_sim_forward(ctx, ws["words"], eng.cap_lens, caps_host, cfg.temp1, cfg.temp2, P=P, gm3=ws["gm3"],
-                                    gm3_crowmap=ws["gm3_crowmap"], img_tiles=ws["img_tiles"], img_tile_count=ws["img_tile_count"],
-                                    wn=ws["wn"], sim=sim_new)
-    tl = TransposedLocalLoss(B, P, T, Do, eng.HWp, eng.Tp, eng.HWq, eng.device, ws, eng._pair_buffers, eng.local_gram)
+    tl = TransposedLocalLoss(B, P, T, Do, eng.device, gram=eng.local_gram, pitch=eng.HWq)
+    new = lambda: local_sim_forward(ctx, ws["words"], eng.cap_lens, caps_host, cfg.temp1, cfg.temp2, P=P, gm3=tl.gm3,
+                                    gm3_crowmap=tl.gm3_crowmap, img_tiles=tl.img_tiles, img_tile_count=tl.img_tile_count,
+                                    wn=tl.wn, sim=sim_new)
     old = lambda: tl.forward(ctx, ws["words"], eng.cap_lens, caps_host, cfg.temp1, cfg.temp2)
     new(); old()
     torch.cuda.synchronize()
-    diff = float((sim_new - ws["sim"]).abs().max())
+    diff = float((sim_new - tl.sim).abs().max())
     t_new, t_old = [], []
     for _ in range(a.repeats):                                   # alternating: both see the same neighbours on a shared host
         t_new += timed(new, a.warmup, a.iters, 1)
