@@ -7,7 +7,8 @@ used by losses.py:503-524) plus DDP's gradient all-reduce (configs/trainer/ddp.y
     message is latency-bound (<= 0.8 MB/rank), so one hop on the xGMI mesh instead of two;
   * the backward of the gathered keys is ONE reduce-scatter (BackpropType.GLOBAL semantics of
     torch.distributed.nn.functional.all_gather: every rank's gradient for my slice is summed);
-  * gradients: one all-reduce over the single flat fp32 gradient buffer (ParamStore.g32).
+  * gradients: one all-reduce over the single flat fp32 gradient buffer of a store (flat.FlatArena.g32: ParamStore, and
+    one more for TextStore / each FlatStore of the Swin encoder).
 """
 import torch
 import torch.distributed as dist

@@ -912,11 +912,7 @@ class Engine:
                 from . import dist as D_
                 D_.allreduce_mean_(self.tstore.g32)
         if optimizer:
-            if self.train_text:                                   # ONE clip norm over both towers' gradients, as clip_grad_norm_ over all parameters
-                self.params.adam_step(extra_normsq=self.tstore.sumsq())
-                self.tstore.adam_step(self.params.normsq)
-            else:
-                self.params.adam_step()
+            self.optimizer_step()
         lp = self.ws["loss_parts"]
         c = self.cfg
         # loss_parts hold the WEIGHTED global/local parts; report the reference's unweighted names too
@@ -924,6 +920,19 @@ class Engine:
         cls = lp[0] * loss_scale
         return {"loss": c.w_cls * cls + lp[2] + lp[3], "classifier_loss": cls, "classifier_acc": lp[1],
                 "g_loss": lp[2] / c.w_global, "l_loss": lp[3] / c.w_local}
+
+    def optimizer_step(self, lr: Optional[float] = None):
+        """clip_grad_norm_(cfg.clip) + torch.optim.Adam(lr, weight_decay), fused, on the gradients the stores hold; the working copies
+        follow.  ONE clip norm over both towers' gradients when the text tower trains, as clip_grad_norm_ over all parameters computes it."""
+        c, image, text = self.cfg, self.params, self.tstore if self.train_text else None
+        lr = c.lr if lr is None else lr
+        text_part = text.sumsq() if text is not None else None
+        total = image.sumsq()
+        if text is not None:
+            total.add_(text_part)
+        image.adam_step(total, lr, c.weight_decay, c.clip)
+        if text is not None:
+            text.adam_step(total, lr, c.weight_decay, c.clip)
 
     # ------------------------------------------------------------------------------------------
     # evaluation (medmoe_module.py:114-134 validation_step / test_step: model_step without a backward)
@@ -1026,7 +1035,7 @@ class Engine:
                     self.backward(b["label"], loss_scale)
             st["bwd"].replay()
         if optimizer:
-            self.params.adam_step()
+            self.optimizer_step()
         lp, c = self.ws["loss_parts"], self.cfg
         cls = lp[0] * loss_scale
         return {"loss": c.w_cls * cls + lp[2] + lp[3], "classifier_loss": cls, "classifier_acc": lp[1],

@@ -1,10 +1,12 @@
 """Parameter storage for the MedMoE hot path on one MI355X.
 
-Trainable (image tower + MoE) parameters live in ONE flat fp32 master buffer with matching
-flat fp32 grad / Adam-m / Adam-v buffers (a single fused clip+Adam launch, a single RCCL
-all-reduce), plus a flat bf16 working copy in the reference's nn.Linear [out,in] layout and a
+Trainable (image tower + MoE) parameters live in ONE flat arena (`flat.FlatArena`: fp32 master with
+matching flat fp32 grad / Adam-m / Adam-v buffers - a single fused clip+Adam launch, a single RCCL
+all-reduce - plus a flat bf16 working copy in the reference's nn.Linear [out,in] layout and a
 second bf16 buffer holding every GEMM weight TRANSPOSED ([in,out]) so dgrad is the same NT MFMA
-kernel as the forward.  Expert weights are stacked [E, ...] for the grouped GEMMs.
+kernel as the forward).  Expert weights are stacked [E, ...] for the grouped GEMMs.  This class holds
+what is specific to the tower: the spec list (its order IS the layout), the seeded init, the 8-bit
+expert copies and the reference-style names.
 
 Names follow the reference modules (transformer.py / multi_head_attention.py / mlp.py /
 swin.py) so state_dicts map 1:1; `load_named` / `export_named` translate the per-expert
@@ -17,15 +19,13 @@ import torch
 
 from . import ops
 from .config import MedMoEConfig
+from .flat import FlatArena
 
-_ALIGN = 8
 
-
-class ParamStore:
+class ParamStore(FlatArena):
     def __init__(self, cfg: MedMoEConfig, device, seed: int = 0, std: float = 0.02):
         cfg.validate()
         self.cfg = cfg
-        self.device = torch.device(device)
         self.specs: List[Tuple[str, Tuple[int, ...], str]] = []   # (name, shape, kind) kind: w|wt|v
         c = cfg
         pp = c.patch_dim_pad           # padded to the GEMM k-step; the pad columns stay zero (zero im2col columns -> zero grads)
@@ -54,41 +54,11 @@ class ParamStore:
         add("moe.attn0.weight", (E, Dh, Do), "wt"); add("moe.attn0.bias", (E, Dh), "v")
         add("moe.attn2.weight", (E, Dh), "v"); add("moe.attn2.bias", (E,), "v")
 
-        self.offsets: Dict[str, int] = {}
-        off = 0
-        for name, shape, _ in self.specs:
-            self.offsets[name] = off
-            n = 1
-            for d in shape:
-                n *= d
-            off += (n + _ALIGN - 1) // _ALIGN * _ALIGN
-        self.numel = off
-        dev = self.device
-        self.p32 = torch.zeros(off, device=dev, dtype=torch.float32)
-        self.g32 = torch.zeros(off, device=dev, dtype=torch.float32)
-        self.m = torch.zeros(off, device=dev, dtype=torch.float32)
-        self.v = torch.zeros(off, device=dev, dtype=torch.float32)
-        self.p16 = torch.zeros(off, device=dev, dtype=torch.bfloat16)
-        self.p16t = torch.zeros(off, device=dev, dtype=torch.bfloat16)
-        self.shapes = {n: s for n, s, _ in self.specs}
         self.kinds = {n: k for n, _, k in self.specs}
         # transpose table: one entry per 2-D matrix (per expert for stacked weights)
-        rows = []
-        for name, shape, kind in self.specs:
-            if kind != "wt":
-                continue
-            o = self.offsets[name]
-            if len(shape) == 2:
-                rows.append([o, o, shape[0], shape[1]])
-            else:
-                for e in range(shape[0]):
-                    oo = o + e * shape[1] * shape[2]
-                    rows.append([oo, oo, shape[1], shape[2]])
-        self.tr_table = torch.tensor(rows, device=dev, dtype=torch.int64)
-        self.tr_max_tiles = max(((r[2] + 63) // 64) * ((r[3] + 63) // 64) for r in rows)
-        self.normsq = torch.zeros(1, device=dev, dtype=torch.float32)
-        self.norm_scratch = torch.zeros(2049, device=dev, dtype=torch.float32)      # per-block partials + arrival counter (medmoe_sumsq_det)
-        self.step_count = 0
+        super().__init__(device, [(n, s) for n, s, _ in self.specs], gemm=[(n, len(s) == 3) for n, s, k in self.specs if k == "wt"])
+        self.adam_state()
+        dev = self.device
         # fp8 expert weights (BASELINE configs[4]): e4m3 copies [E,N,K] + transposes [E,K,N] + per-output-channel scales [E,N] of
         # the five expert projections, re-derived from the fp32 master after every update (requantise_experts)
         self.fp8: Dict[str, Tuple[torch.Tensor, ...]] = {}
@@ -110,22 +80,6 @@ class ParamStore:
         self.text: Dict[str, torch.Tensor] = {}
         self._init_text(seed + 1, std)
 
-    # -- views ---------------------------------------------------------------------------------
-    def _view(self, flat, name, transposed=False):
-        shape = self.shapes[name]
-        n = 1
-        for d in shape:
-            n *= d
-        t = flat[self.offsets[name]: self.offsets[name] + n]
-        if transposed:
-            shape = shape[:-2] + (shape[-1], shape[-2])
-        return t.view(shape)
-
-    def f32(self, name): return self._view(self.p32, name)
-    def grad(self, name): return self._view(self.g32, name)
-    def w16(self, name): return self._view(self.p16, name)
-    def w16t(self, name): return self._view(self.p16t, name, transposed=True)
-
     # -- init / sync ---------------------------------------------------------------------------
     def _init_random(self, seed, std):
         g = torch.Generator(device="cpu").manual_seed(seed)
@@ -139,7 +93,7 @@ class ParamStore:
             else:
                 val = torch.randn(shape, generator=g) * std     # init rule multimodal_transformer.py:298-312
             self.f32(name).copy_(val.to(self.device))
-        self.sync_working_copies()
+        self.refresh()
 
     def _init_text(self, seed, std):
         c, dev = self.cfg, self.device
@@ -169,13 +123,11 @@ class ParamStore:
             return w
         return torch.cat([w, w.new_zeros(c.d_v, c.patch_dim_pad - c.patch_dim)], 1)
 
-    def sync_working_copies(self):
-        """fp32 master -> bf16 [out,in] copy and the transposed bf16 copy (+ the e4m3 expert copies)."""
-        ops.call("cast_bf16", self.p32, self.p16, self.numel)
-        ops.call("transpose_many", self.p16, self.p16t, self.tr_table, self.tr_table.shape[0], self.tr_max_tiles)
+    def after_update(self):
         self.requantise_experts()
 
     def requantise_experts(self):
+        """The 8-bit expert copies from the fp32 master (after every refresh() / adam_step(): FlatArena's hook)."""
         for name, copies in self.fp8.items():
             Eg, N, K = self.shapes[name]
             if self.cfg.expert_mx:
@@ -215,7 +167,7 @@ class ParamStore:
             self.f32("moe.attn2.weight")[e].copy_(named[f"moe.experts.{e}.attn_proj.2.weight"].to(dev).reshape(-1))
             self.f32("moe.attn2.bias")[e].copy_(named[f"moe.experts.{e}.attn_proj.2.bias"].to(dev).reshape(()))
         self.load_named_text(named)
-        self.sync_working_copies()
+        self.refresh()
 
     def load_named_text(self, named: Dict[str, torch.Tensor]):
         """`text.<name>` entries of a reference-style dict into the frozen text tower (in place: views handed out earlier stay valid)."""
@@ -235,7 +187,7 @@ class ParamStore:
         c = self.cfg
         out = {}
         for name in self.shapes:
-            v = self._view(flat, name)
+            v = self.view(flat, name)
             if name.startswith("moe.proj."):
                 s = int(name.split(".")[2]); leaf = name.split(".")[3]
                 for e in range(c.n_expert):
@@ -258,21 +210,3 @@ class ParamStore:
     def export_named(self, flat=None) -> Dict[str, torch.Tensor]:
         """Reference-style names -> fp32 CPU tensors (flat = p32 for weights, g32 for grads)."""
         return {k: v.detach().float().cpu().contiguous() for k, v in self.named_views(flat).items()}
-
-    # -- optimiser ------------------------------------------------------------------------------
-    def zero_grad(self):
-        self.g32.zero_()
-
-    def adam_step(self, lr=None, grad_scale: float = 1.0, extra_normsq=None):
-        """clip_grad_norm_(clip) + torch.optim.Adam step, fused, then refresh the bf16 copies.  extra_normsq: the squared gradient norm of
-        parameters that live in another store (the trainable text tower) - the clip coefficient is formed from the norm over ALL of them, and
-        self.normsq holds that total afterwards."""
-        c = self.cfg
-        self.step_count += 1
-        ops.call("sumsq_det", self.g32, self.numel, self.normsq, self.norm_scratch)     # fixed order: identical on every rank
-        if extra_normsq is not None:
-            self.normsq.add_(extra_normsq)
-        ops.call("adam_step", self.p32, self.g32, self.m, self.v, self.p16, self.numel, c.lr if lr is None else lr,
-                 0.9, 0.999, 1e-8, c.weight_decay, self.step_count, self.normsq, c.clip, grad_scale)
-        ops.call("transpose_many", self.p16, self.p16t, self.tr_table, self.tr_table.shape[0], self.tr_max_tiles)
-        self.requantise_experts()

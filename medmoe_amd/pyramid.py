@@ -120,7 +120,7 @@ class GroupedPyramidExperts:
         self.Dh = sh["moe.experts.0.attn_proj.0.weight"][0]
         self.Ds = [sh[f"moe.experts.0.proj_convs.{s}.0.weight"][1] for s in range(4)]
         Do, Dh = self.Do, self.Dh
-        v = store._view
+        v = store.view
         self.wp = [v(store.p16, f"moe.stack.proj{s}.weight", (E, Do, self.Ds[s])) for s in range(4)]
         self.wpt = [v(store.p16t, f"moe.stack.proj{s}.weight", (E, self.Ds[s], Do)) for s in range(4)]
         self.bp = [v(store.p32, f"moe.stack.proj{s}.bias", (E, Do)) for s in range(4)]
@@ -132,7 +132,7 @@ class GroupedPyramidExperts:
         self._tab_key, self._tab_bufs = None, []
 
     def _grads(self):
-        st, E, Do, Dh, v = self.store, self.E, self.Do, self.Dh, self.store._view
+        st, E, Do, Dh, v = self.store, self.E, self.Do, self.Dh, self.store.view
         return dict(wp=[v(st.g32, f"moe.stack.proj{s}.weight", (E, Do, self.Ds[s])) for s in range(4)],
                     bp=[v(st.g32, f"moe.stack.proj{s}.bias", (E, Do)) for s in range(4)],
                     w0=v(st.g32, "moe.stack.attn_proj.0.weight", (E, Dh, Do)), b0=v(st.g32, "moe.stack.attn_proj.0.bias", (E, Dh)),

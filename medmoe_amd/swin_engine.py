@@ -154,7 +154,7 @@ class SwinEngine:
         st_t.adam_step(self._normsq, lr, c.weight_decay, c.clip)
         st_m.adam_step(self._normsq, lr, c.weight_decay, c.clip)
         if self.train_text:
-            self.eng.tstore.adam_step(self._normsq, lr)
+            self.eng.tstore.adam_step(self._normsq, lr, c.weight_decay, c.clip)
         self.enc.tower.refresh(cast=False)                          # patch-embedding pad form, bias tables
 
     def eval_step(self, batch: Dict[str, torch.Tensor]):

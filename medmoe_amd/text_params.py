@@ -11,15 +11,13 @@ from typing import Dict, List, Tuple
 
 import torch
 
-from . import ops
 from .config import MedMoEConfig
+from .flat import FlatArena
 
-_ALIGN = 8
 
-
-class TextStore:
+class TextStore(FlatArena):
     def __init__(self, cfg: MedMoEConfig, device, init: Dict[str, torch.Tensor]):
-        self.cfg, self.device = cfg, torch.device(device)
+        self.cfg = cfg
         c = cfg
         D, ff = c.d_t, c.ff_t
         specs: List[Tuple[str, Tuple[int, ...], str]] = [("word_embeddings", (c.vocab, D), "v"), ("position_embeddings", (c.max_len, D), "v"),
@@ -34,48 +32,16 @@ class TextStore:
                       (b + "feedforward.model.2.weight", (D, ff), "wt"), (b + "feedforward.model.2.bias", (D,), "v"),
                       (b + "feedforward_layernorm.weight", (D,), "v"), (b + "feedforward_layernorm.bias", (D,), "v")]
         self.specs = specs
-        self.shapes = {n: s for n, s, _ in specs}
         self.kinds = {n: k for n, _, k in specs}
-        self.offsets: Dict[str, int] = {}
-        off = 0
-        for name, shape, _ in specs:
-            self.offsets[name] = off
-            n = 1
-            for d in shape:
-                n *= d
-            off += (n + _ALIGN - 1) // _ALIGN * _ALIGN
-        self.numel = off
+        super().__init__(device, [(n, s) for n, s, _ in specs], gemm=[(n, False) for n, _, k in specs if k == "wt"])
+        self.adam_state()
         dev = self.device
-        z = lambda dt: torch.zeros(off, device=dev, dtype=dt)
-        self.p32, self.g32, self.m, self.v = z(torch.float32), z(torch.float32), z(torch.float32), z(torch.float32)
-        self.p16, self.p16t = z(torch.bfloat16), z(torch.bfloat16)
-        rows = [[self.offsets[n], self.offsets[n], s[0], s[1]] for n, s, k in specs if k == "wt"]
-        self.tr_table = torch.tensor(rows, device=dev, dtype=torch.int64)
-        self.tr_max_tiles = max(((r[2] + 63) // 64) * ((r[3] + 63) // 64) for r in rows)
-        self.normsq = torch.zeros(1, device=dev, dtype=torch.float32)
-        self.norm_scratch = torch.zeros(2049, device=dev, dtype=torch.float32)
-        self.step_count = 0
         missing = [n for n in self.shapes if n not in init]
         if missing:
             raise KeyError(f"TextStore: no initial value for {missing[:3]} ...")
         for name in self.shapes:
             self.f32(name).copy_(init[name].to(dev).float().reshape(self.shapes[name]))
-        self.sync_working_copies()
-
-    def _view(self, flat, name, transposed=False):
-        shape = self.shapes[name]
-        n = 1
-        for d in shape:
-            n *= d
-        t = flat[self.offsets[name]: self.offsets[name] + n]
-        if transposed:
-            shape = (shape[1], shape[0])
-        return t.view(shape)
-
-    def f32(self, name): return self._view(self.p32, name)
-    def grad(self, name): return self._view(self.g32, name)
-    def w16(self, name): return self._view(self.p16, name)
-    def w16t(self, name): return self._view(self.p16t, name, transposed=True)
+        self.refresh()
 
     def as_dict(self) -> Dict[str, torch.Tensor]:
         """name -> the tensor the forward pass reads: bf16 [out, in] views for the GEMM weights, fp32 views for embeddings, biases, LayerNorms."""
@@ -92,28 +58,8 @@ class TextStore:
             if tuple(v.shape) != tuple(self.shapes[kk]):
                 raise ValueError(f"{k}: shape {tuple(v.shape)} != {tuple(self.shapes[kk])}")
             self.f32(kk).copy_(v.to(self.device).float())
-        self.sync_working_copies()
+        self.refresh()
 
     def export_named(self, flat=None) -> Dict[str, torch.Tensor]:
         flat = self.p32 if flat is None else flat
-        return {"text." + n: self._view(flat, n).detach().float().cpu().contiguous() for n in self.shapes}
-
-    def sync_working_copies(self):
-        ops.call("cast_bf16", self.p32, self.p16, self.numel)
-        ops.call("transpose_many", self.p16, self.p16t, self.tr_table, self.tr_table.shape[0], self.tr_max_tiles)
-
-    def zero_grad(self):
-        self.g32.zero_()
-
-    def sumsq(self) -> torch.Tensor:
-        """Sum of squares of the gradient in a fixed order (identical on every rank): the text tower's share of the global clip norm."""
-        ops.call("sumsq_det", self.g32, self.numel, self.normsq, self.norm_scratch)
-        return self.normsq
-
-    def adam_step(self, normsq_total: torch.Tensor, lr=None, grad_scale: float = 1.0):
-        """clip (against the norm over BOTH towers' gradients, as clip_grad_norm_ over all parameters computes it) + Adam, fused."""
-        c = self.cfg
-        self.step_count += 1
-        ops.call("adam_step", self.p32, self.g32, self.m, self.v, self.p16, self.numel, c.lr if lr is None else lr,
-                 0.9, 0.999, 1e-8, c.weight_decay, self.step_count, normsq_total, c.clip, grad_scale)
-        ops.call("transpose_many", self.p16, self.p16t, self.tr_table, self.tr_table.shape[0], self.tr_max_tiles)
+        return {"text." + n: self.view(flat, n).detach().float().cpu().contiguous() for n in self.shapes}

@@ -163,7 +163,7 @@ class MedMoE(nn.Module):
                     self.engine.tstore.load_named(text)
                 else:
                     p.load_named_text(text)
-            p.sync_working_copies()
+            p.refresh()
         # the flat parameter itself: legacy checkpoints hold it under `weights`; otherwise present the (just updated) buffer so that the
         # default loader finds its key
         if prefix + "weights" not in state_dict:
@@ -189,7 +189,7 @@ class MedMoE(nn.Module):
             p.p32 = w.data
             self._synced_version = -1
         if w._version != self._synced_version:
-            p.sync_working_copies()
+            p.refresh()
             self._synced_version = w._version
 
     def encode_image(self, images: torch.Tensor):

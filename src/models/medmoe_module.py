@@ -202,7 +202,7 @@ class MedMoEPretrainingLightningModule(_Base):
 
     # ---- fused mode: the optimiser state lives in the engine's flat stores, not in a torch optimizer -----------------------------------
     def _fused_stores(self) -> Dict[str, Any]:
-        """name -> flat store holding Adam moments (`m`, `v`, `step_count`) of the fused step."""
+        """name -> flat store (`medmoe_amd.flat.FlatArena`) holding Adam's state of the fused step."""
         m = self.model
         if getattr(m, "swin", None) is not None:
             enc = m.swin._encoder()
@@ -223,10 +223,11 @@ class MedMoEPretrainingLightningModule(_Base):
             return
         state = {}
         for name, st in self._fused_stores().items():
-            if getattr(st, "m", None) is None:
+            if not st.has_adam_state():
                 continue                                             # no optimiser step taken yet
-            state[name] = {"step": int(st.step_count), "numel": int(st.m.numel()), "exp_avg": st.m.detach().cpu().clone(),
-                           "exp_avg_sq": st.v.detach().cpu().clone()}
+            m, v = st.adam_state()
+            state[name] = {"step": int(st.step_count), "numel": int(m.numel()), "exp_avg": m.detach().cpu().clone(),
+                           "exp_avg_sq": v.detach().cpu().clone()}
         checkpoint["fused_adam"] = state
 
     def on_load_checkpoint(self, checkpoint: Dict[str, Any]) -> None:
@@ -238,11 +239,10 @@ class MedMoEPretrainingLightningModule(_Base):
             if name not in stores:
                 raise KeyError(f"checkpoint holds fused Adam state for {name!r}; this module has {sorted(stores)}")
             st = stores[name]
-            if getattr(st, "m", None) is None:
-                st.m, st.v = torch.zeros_like(st.p32), torch.zeros_like(st.p32)
-            if int(rec["numel"]) != st.m.numel():
-                raise ValueError(f"fused Adam state {name!r}: {rec['numel']} elements in the checkpoint, {st.m.numel()} in this model")
-            st.m.copy_(rec["exp_avg"]); st.v.copy_(rec["exp_avg_sq"])
+            m, v = st.adam_state()
+            if int(rec["numel"]) != m.numel():
+                raise ValueError(f"fused Adam state {name!r}: {rec['numel']} elements in the checkpoint, {m.numel()} in this model")
+            m.copy_(rec["exp_avg"]); v.copy_(rec["exp_avg_sq"])
             st.step_count = int(rec["step"])
 
     def configure_optimizers(self):                                                      # :148-169

@@ -39,6 +39,7 @@ def test_product_path_does_not_import_oracle():
 class _StubLib:
     def __init__(self):
         self.calls = []
+        self.args = []                                              # per call: the arguments as the library would receive them
 
     def __getattr__(self, name):
         if not name.startswith("medmoe_"):
@@ -46,6 +47,7 @@ class _StubLib:
 
         def f(*a):
             self.calls.append(name)
+            self.args.append(a)
             if name == "medmoe_local_geometry":
                 HW, T = a[0].value, a[1].value
                 a[2]._obj.value = (HW + 15) // 16 * 16; a[3]._obj.value = (T + 15) // 16 * 16
@@ -170,6 +172,99 @@ def test_engine_launch_sequences_are_the_recorded_ones(stub, monkeypatch, case):
     with open(os.path.join(ROOT, "tests", "golden", "engine_launch_sequences.json")) as f:
         want = json.load(f)[case]
     assert got == want, next((i, a, b) for i, (a, b) in enumerate(zip(got + [None], want + [None])) if a != b)
+
+
+def _layout_tool():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("record_store_layouts", os.path.join(ROOT, "tools", "record_store_layouts.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_store_layouts_are_the_recorded_ones(stub):
+    """numel, the ordered offsets, shapes, the transpose table and every accessor's view (shape, storage offset) of ParamStore (tiny, tiny2,
+    fp8 and MXFP8 experts), TextStore, the grouped pyramid FlatStore and a Swin tower's FlatStore equal tests/golden/store_layouts.json,
+    which tools/record_store_layouts.py wrote before the three stores shared one arena: the layout travels in checkpoints (flat Adam state)
+    and in Engine.bucket_bounds."""
+    import json
+    got = json.loads(json.dumps(_layout_tool().record()))
+    with open(os.path.join(ROOT, "tests", "golden", "store_layouts.json")) as f:
+        want = json.load(f)
+    assert list(got) == list(want)
+    for label in want:
+        g, w = got[label], want[label]
+        assert set(g) == set(w), label
+        for key in w:
+            if key != "entries":
+                assert g[key] == w[key], (label, key)
+        if "entries" in w:
+            assert len(g["entries"]) == len(w["entries"]), label
+            for a, b in zip(g["entries"], w["entries"]):
+                assert a == b, (label, a, b)
+
+
+_TAIL = {"tiny": [], "tinyL8": ["medmoe_quant_weights_e4m3"] * 5, "tinyL8mx": ["medmoe_quant_weights_mx"] * 5}
+
+
+def _step_stores():
+    """(label, store built lazily?, store, launches that follow the transposes)"""
+    from medmoe_amd.config import config_by_name
+    from medmoe_amd.flat import FlatStore
+    from medmoe_amd.params import ParamStore
+    from medmoe_amd.text_params import TextStore
+    tool = _layout_tool()
+    out = []
+    for name, tail in _TAIL.items():
+        out.append((f"ParamStore:{name}", False, ParamStore(config_by_name(name), "cpu"), tail))
+    out.append(("TextStore:tiny", False, TextStore(config_by_name("tiny"), "cpu", out[0][2].text), []))
+    out.append(("FlatStore:grouped-pyramid", True, tool.build_stores()["FlatStore:grouped-pyramid"], []))
+    out.append(("FlatStore:no-gemm", True, FlatStore({"a": torch.zeros(5, 3), "b": torch.zeros(7)}, "cpu"), []))
+    return out
+
+
+def test_store_step_and_refresh_launches(stub):
+    """Every store kind: zero_grad(); sumsq(); adam_step(...) launches medmoe_sumsq_det, medmoe_adam_step, then medmoe_transpose_many iff the
+    store has a transpose table, then the weight quantiser iff it keeps 8-bit expert copies; step_count goes up by one; refresh() launches
+    medmoe_cast_bf16 and the same tail.  A FlatStore holds no Adam state until its first step; ParamStore / TextStore allocate it eagerly."""
+    for label, lazy, st, tail in _step_stores():
+        assert (st.tr_table is None) == (label == "FlatStore:no-gemm"), label
+        tail = (["medmoe_transpose_many"] if st.tr_table is not None else []) + tail
+        assert st.has_adam_state() == (not lazy), label
+        count = st.step_count
+        del stub.calls[:]
+        st.zero_grad()
+        total = st.sumsq()
+        st.adam_step(total, 1e-4, 0.0, 0.25)
+        assert stub.calls == ["medmoe_sumsq_det", "medmoe_adam_step"] + tail, label
+        assert st.step_count == count + 1 and st.has_adam_state(), label
+        m, v = st.adam_state()
+        assert m is st.m and v is st.v and m.shape == st.p32.shape and m.data_ptr() != v.data_ptr(), label
+        del stub.calls[:]
+        st.refresh()
+        assert stub.calls == ["medmoe_cast_bf16"] + tail, label
+
+
+def test_one_clip_norm_over_both_towers_launch_order(stub):
+    """Trainable text tower, optimizer=True: the step ends with sumsq_det (text), sumsq_det (image), [the add], adam_step + transpose_many
+    (image), adam_step + transpose_many (text) - the order recorded in engine_launch_sequences.json - and both Adam launches read the
+    image store's norm buffer, which holds the total."""
+    import json
+    from medmoe_amd.config import config_by_name
+    from medmoe_amd.engine import Engine
+    cfg = config_by_name("tiny")
+    cfg.freeze_text = False
+    eng = Engine(cfg, "cpu")
+    eng.train_step(O.synthetic_batch(O.config_by_name("tiny"), 8, min_len=4))
+    names, args = stub.calls[-6:], stub.args[-6:]
+    assert names == ["medmoe_sumsq_det", "medmoe_sumsq_det", "medmoe_adam_step", "medmoe_transpose_many", "medmoe_adam_step", "medmoe_transpose_many"]
+    with open(os.path.join(ROOT, "tests", "golden", "engine_launch_sequences.json")) as f:
+        assert json.load(f)["tiny-transposed-words:train_step"][-6:] == names
+    p, t = eng.params, eng.tstore
+    assert [a[0] for a in args] == [t.g32.data_ptr(), p.g32.data_ptr(), p.p32.data_ptr(), p.p16.data_ptr(), t.p32.data_ptr(), t.p16.data_ptr()]
+    assert args[0][2] == t.normsq.data_ptr() and args[1][2] == p.normsq.data_ptr()
+    assert args[2][12] == p.normsq.data_ptr() and args[4][12] == p.normsq.data_ptr()
+    assert p.step_count == 1 and t.step_count == 1
 
 
 def test_segment_map_matches_oracle():
