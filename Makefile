@@ -9,7 +9,7 @@ FLAGS := --offload-arch=$(ARCH) -O3 -fPIC -std=c++17 -Iinclude -I$(CSRC) -Wno-un
 
 all: $(LIB)
 
-build/%.o: $(CSRC)/%.hip $(CSRC)/common.h
+build/%.o: $(CSRC)/%.hip $(CSRC)/common.h $(CSRC)/philox.h
 	@mkdir -p build
 	$(HIPCC) $(FLAGS) -c $< -o $@
 

@@ -316,6 +316,21 @@ int medmoe_quant_weights_mx(const float* w, void* q, void* sq, void* qT, void* s
    bit-identical to medmoe_quant_rows_mx of C.  strideSb: scale bytes per group. */
 int medmoe_gemm_mx_grouped(const void* Aq, const void* sa, const void* Bq, const void* sb, const float* bias, void* C, int ldc, const void* residual, const void* aux, void* Cq, void* Csq, const int* tiles, const int* tile_count, int max_tiles, int N, int K, long long strideB, long long strideSb, long long strideBias, int epi, hipStream_t stream);
 
+/* Dropout of the trainable text tower (csrc/dropout.hip, csrc/philox.h).  The keep mask is a pure function of (seed, step, site, element):
+   Philox4x32-10 with key = the two halves of `seed`, counter = (group lo, group hi, site, step), one call per group of 4 consecutive
+   elements along the fastest axis (element (row, col) of [rows][cols_padded]: group row * cols_padded / 4 + col / 4, word col % 4);
+   an element survives iff its word >= thresh = floor(p * 2^32) and is scaled by `scale` = 1 / (1 - p).  step, site and thresh are
+   32-bit values.  No kernel stores a mask except medmoe_dropout_mask (tests, debugging): out_u8[rows][cols] = 1 where kept. */
+int medmoe_dropout_mask(unsigned char* out_u8, long long rows, int cols, int cols_padded, long long seed, long long step, long long site, long long thresh, hipStream_t stream);
+/* y = keep * x * scale over [rows][cols] (cols % 4 == 0), bf16 or (is_f32) fp32; y may be x */
+int medmoe_dropout_apply(const void* x, void* y, long long rows, int cols, int is_f32, long long seed, long long step, long long site, long long thresh, float scale, hipStream_t stream);
+/* x1 = residual + keep * z * scale (bf16, stored for medmoe_layernorm_bwd), y = LayerNorm(x1) with medmoe_layernorm_fwd's layout and statistics */
+int medmoe_dropout_add_layernorm_fwd(const void* z, const void* residual, const float* gamma, const float* beta, void* x1, void* y, float* mean, float* rstd, int rows, int D, float eps, long long seed, long long step, long long site, long long thresh, float scale, hipStream_t stream);
+/* medmoe_attn_fwd / medmoe_attn_bwd for N <= 80, head_dim 64 (anything else: MM_ERR_SHAPE) with dropout on the probabilities: lse is of the
+   undropped softmax, out = (keep * P * scale) V; the mask row of query q of (b, h) is (b * H + h) * N + q, its key axis padded to a multiple of 4 */
+int medmoe_attn_drop_fwd(const void* qkv, void* out, float* lse, const unsigned char* key_mask, int B, int N, int H, int head_dim, long long seed, long long step, long long site, long long thresh, float scale, hipStream_t stream);
+int medmoe_attn_drop_bwd(const void* qkv, const void* out, const void* dout, const float* lse, const unsigned char* key_mask, void* dqkv, float* delta, int B, int N, int H, int head_dim, long long seed, long long step, long long site, long long thresh, float scale, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,12 @@ class MedMoEConfig:
     last_n_layers: int = 4
     freeze_text: bool = True      # configs/model/med-moe.yaml:35 freeze_bert: true (the experiment); False = the text tower trains too
                                   # (text_encoder.py:27-30): padded text pass with saved activations, text backward, word gradients of the local loss
+    # train-mode dropout of the TRAINABLE text tower (Hugging Face BertConfig hidden_dropout_prob / attention_probs_dropout_prob; BERT's
+    # default for both is 0.1): after the embedding LayerNorm, on the attention probabilities, after the attention output projection and
+    # after FC2.  The masks are a function of (dropout_seed, step, site, element) regenerated in the backward kernels (csrc/philox.h)
+    text_hidden_dropout: float = 0.0
+    text_attn_dropout: float = 0.0
+    dropout_seed: int = 0
     # MoE (swin.py:82-92)
     n_expert: int = 4
     top_k: int = 1
@@ -77,6 +83,9 @@ class MedMoEConfig:
         return [max(1, (L * (s + 1)) // 4) for s in range(4)]
 
     def validate(self):
+        for key in ("text_hidden_dropout", "text_attn_dropout"):
+            if not 0.0 <= float(getattr(self, key)) < 1.0:
+                raise ValueError(f"{key} must be in [0, 1), got {getattr(self, key)}")
         if self.expert_fp8 and self.expert_mx:
             raise ValueError("expert_fp8 and expert_mx are two formats of the same weights: set one")
         if self.expert_mx and (self.d_v % 32 or self.d_out % 64):

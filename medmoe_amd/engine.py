@@ -81,9 +81,22 @@ class VocabTables:
 
 class Engine:
     def __init__(self, cfg: MedMoEConfig, device="cuda:0", seed: int = 0, vocab: Optional[VocabTables] = None):
+        cfg.validate()
+        # train-mode dropout of the trainable text tower (cfg.text_hidden_dropout / cfg.text_attn_dropout): acts in the padded text pass of
+        # train_step and in backward_text only; the mask is a function of (cfg.dropout_seed, self.dropout_step, site, element)
+        self.text_dropout = cfg.text_hidden_dropout > 0.0 or cfg.text_attn_dropout > 0.0
+        self.dropout_step = 0                                        # one per train_step call, counted on the host; travels with the checkpoint
+        self._text_drop_step = None                                  # the step whose masks the last text pass applied (None: it applied none)
+        if self.text_dropout and cfg.freeze_text:
+            raise NotImplementedError("text_hidden_dropout / text_attn_dropout > 0 (model.model.text.hidden_dropout_prob / "
+                                      "attention_probs_dropout_prob) with freeze_text=True (text.freeze_bert: true): dropout is built for the "
+                                      "trainable tower's padded pass, not for the packed frozen one")
+        if self.text_dropout and os.environ.get("MEDMOE_GRAPH", "0") == "1":
+            raise NotImplementedError("text_hidden_dropout / text_attn_dropout > 0 (model.model.text.hidden_dropout_prob / "
+                                      "attention_probs_dropout_prob) with MEDMOE_GRAPH=1: the dropout step counter is a by-value launch "
+                                      "argument, a replayed graph would repeat one step's masks")
         if not torch.cuda.is_available():
             raise RuntimeError("medmoe_amd.Engine needs a GPU: the HIP path is the only path")
-        cfg.validate()
         self.cfg = cfg
         self.device = torch.device(device)
         torch.cuda.set_device(self.device)
@@ -215,6 +228,8 @@ class Engine:
             buf("t_dH", (Mt, Dt)); buf("t_da", (Mt, Dt)); buf("t_db", (Mt, Dt)); buf("t_dc", (Mt, Dt)); buf("t_datt", (Mt, Dt))
             buf("t_dz", (Mt, c.ff_t)); buf("t_dqkv", (Mt, 3 * Dt)); buf("t_delta", (B * Ht * T,), F32); buf("t_dxemb", (Mt, Dt), F32)
             buf("d_txt_g", (B, Dt), F32); buf("cb", (B * self.world,), F32)
+            if c.text_hidden_dropout > 0.0:      # a GEMM output before its dropout + residual + LayerNorm launch; d z = keep * d x1 / (1 - p) in the backward
+                buf("t_z", (Mt, Dt)); buf("t_dzd", (Mt, Dt))
             if self.dist:
                 buf("d_txt_all", (B * self.world, Dt), F32); buf("cb1", (B * self.world,), F32)
         # global loss
@@ -345,15 +360,17 @@ class Engine:
     # text tower forward (frozen; transformer.py:116-130 post-norm; text_encoder.py:92-144)
     # ------------------------------------------------------------------------------------------
     def forward_text(self, ids: torch.Tensor, attn_mask: torch.Tensor, token_type: Optional[torch.Tensor] = None,
-                     embedded: Optional[torch.Tensor] = None):
-        """`embedded` [B, T, d_t] bf16: use these rows as the encoder's input instead of the embedding front-end's output (the
+                     embedded: Optional[torch.Tensor] = None, training: bool = False):
+        """`training`: the pass of a training step - a trainable tower then applies its dropout (cfg.text_hidden_dropout / text_attn_dropout) with
+        the masks of self.dropout_step; evaluation passes never do.
+        `embedded` [B, T, d_t] bf16: use these rows as the encoder's input instead of the embedding front-end's output (the
         reference's TransformerEncoder fixture is fed to the post-norm blocks this way, tests/test_ref_fixtures_gpu.py)."""
         c, ws, t = self.cfg, self.ws, self.params.text
         B, T = ids.shape
         if B != self.B or T != c.max_len:
             raise ValueError("forward_text: call forward_image first with the same batch; T must equal cfg.max_len")
         if self.train_text and embedded is None:
-            return self._forward_text_train(ids, attn_mask, token_type)
+            return self._forward_text_train(ids, attn_mask, token_type, training)
         Dt, H = c.d_t, c.n_head_t
         ids32 = ids.to(I32).contiguous()
         tt32 = token_type.to(I32).contiguous() if token_type is not None else None
@@ -420,9 +437,16 @@ class Engine:
         else:
             ops.call("text_aggregate", h[0], h[1], h[2], h[3], len(hs), seg, ws["words"], ws["words32"], ws["txt_g"], B, T, Dt)
 
-    def _forward_text_train(self, ids, attn_mask, token_type):
+    def _drop_rng(self, site: int, p: float):
+        return ops.dropout_rng(self.cfg.dropout_seed, self._text_drop_step, site, p)
+
+    def _forward_text_train(self, ids, attn_mask, token_type, training: bool = False):
         """The text pass of a TRAINABLE tower (cfg.freeze_text = False): all B x T positions (key-masked attention, as the reference computes
-        them, text_encoder.py:92-117), every layer's activations kept in the workspace for `backward_text`."""
+        them, text_encoder.py:92-117), every layer's activations kept in the workspace for `backward_text`.
+        `training` with a dropout probability > 0: BertModel's four train-mode dropouts - after the embedding LayerNorm, on the attention
+        probabilities (medmoe_attn_drop_fwd), after the output projection and after FC2 (each fused with the residual add and the LayerNorm
+        that follow: medmoe_dropout_add_layernorm_fwd on the GEMM's output without residual).  No mask is stored: `backward_text`
+        regenerates them from (cfg.dropout_seed, the step, the site)."""
         c, ws, t = self.cfg, self.ws, self.params.text
         B, T = ids.shape
         Dt, H, L, last = c.d_t, c.n_head_t, c.n_layer_t, c.last_n_layers
@@ -432,13 +456,45 @@ class Engine:
         tt32 = token_type.to(I32).contiguous() if token_type is not None else None
         km = attn_mask.to(torch.uint8).contiguous()
         self._tt_state = (ids32, tt32, km)
+        drop = training and self.text_dropout
+        self._text_drop_step = self.dropout_step if drop else None
+        ph, pa = (c.text_hidden_dropout, c.text_attn_dropout) if drop else (0.0, 0.0)
         x = ws["t_x0"]
         ops.call("text_embed_ln", ids32, tt32, t["word_embeddings"], t["position_embeddings"], t["token_type_embeddings"],
                  t["emb_layernorm.weight"], t["emb_layernorm.bias"], x, B, T, Dt, c.vocab, c.eps_t)
+        if ph > 0.0:
+            ops.dropout_apply(x, x, self._drop_rng(ops.DROPOUT_SITE_EMBED, ph))
         for l in range(L):
             b = f"layer.{l}."
             st1, st2 = ws[f"t_st1{l}"], ws[f"t_st2{l}"]
             ops.gemm_nt(x, t[b + "attention.input_proj.weight"], ws[f"t_qkv{l}"], bias=t[b + "attention.input_proj.bias"])
+            if drop:
+                if pa > 0.0:
+                    ops.attn_drop_fwd(ws[f"t_qkv{l}"], ws[f"t_att{l}"], ws[f"t_lse{l}"], km, B, T, H, self._drop_rng(4 * l, pa))
+                else:
+                    ops.attn_fwd(ws[f"t_qkv{l}"], ws[f"t_att{l}"], ws[f"t_lse{l}"], km, B, T, H)
+                if ph > 0.0:
+                    ops.gemm_nt(ws[f"t_att{l}"], t[b + "attention.output_proj.weight"], ws["t_z"], bias=t[b + "attention.output_proj.bias"])
+                    ops.dropout_add_layernorm_fwd(ws["t_z"], x, t[b + "attention_layernorm.weight"], t[b + "attention_layernorm.bias"],
+                                                  ws[f"t_x1{l}"], ws[f"t_r{l}"], st1[0], st1[1], c.eps_t, self._drop_rng(4 * l + 1, ph))
+                else:
+                    ops.gemm_nt(ws[f"t_att{l}"], t[b + "attention.output_proj.weight"], ws[f"t_x1{l}"], bias=t[b + "attention.output_proj.bias"],
+                                residual=x)
+                    ops.layernorm_fwd(ws[f"t_x1{l}"], t[b + "attention_layernorm.weight"], t[b + "attention_layernorm.bias"], ws[f"t_r{l}"],
+                                      st1[0], st1[1], c.eps_t)
+                ops.gemm_nt(ws[f"t_r{l}"], t[b + "feedforward.model.0.weight"], ws[f"t_h{l}"], bias=t[b + "feedforward.model.0.bias"],
+                            aux=ws[f"t_dg{l}"], epi=ops.EPI_GELU_DAUX)
+                if ph > 0.0:
+                    ops.gemm_nt(ws[f"t_h{l}"], t[b + "feedforward.model.2.weight"], ws["t_z"], bias=t[b + "feedforward.model.2.bias"])
+                    ops.dropout_add_layernorm_fwd(ws["t_z"], ws[f"t_r{l}"], t[b + "feedforward_layernorm.weight"], t[b + "feedforward_layernorm.bias"],
+                                                  ws[f"t_x2{l}"], ws[f"t_x{l + 1}"], st2[0], st2[1], c.eps_t, self._drop_rng(4 * l + 2, ph))
+                else:
+                    ops.gemm_nt(ws[f"t_h{l}"], t[b + "feedforward.model.2.weight"], ws[f"t_x2{l}"], bias=t[b + "feedforward.model.2.bias"],
+                                residual=ws[f"t_r{l}"])
+                    ops.layernorm_fwd(ws[f"t_x2{l}"], t[b + "feedforward_layernorm.weight"], t[b + "feedforward_layernorm.bias"], ws[f"t_x{l + 1}"],
+                                      st2[0], st2[1], c.eps_t)
+                x = ws[f"t_x{l + 1}"]
+                continue
             ops.attn_fwd(ws[f"t_qkv{l}"], ws[f"t_att{l}"], ws[f"t_lse{l}"], km, B, T, H)
             ops.gemm_nt(ws[f"t_att{l}"], t[b + "attention.output_proj.weight"], ws[f"t_x1{l}"], bias=t[b + "attention.output_proj.bias"], residual=x)
             ops.layernorm_fwd(ws[f"t_x1{l}"], t[b + "attention_layernorm.weight"], t[b + "attention_layernorm.bias"], ws[f"t_r{l}"], st1[0], st1[1], c.eps_t)
@@ -468,6 +524,10 @@ class Engine:
         ids32, tt32, km = self._tt_state
         w16t, grad, f32 = ts.w16t, ts.grad, ts.f32
         dH = ws["t_dH"]
+        # the masks of the forward pass just run (None: it applied none): d z = keep * d x1 / (1 - p) feeds the two GEMMs of a hidden site, the
+        # residual branch takes d x1 unchanged
+        drop = self._text_drop_step is not None
+        ph, pa = (c.text_hidden_dropout, c.text_attn_dropout) if drop else (0.0, 0.0)
         ops.call("text_aggregate_bwd", d_words, d_txt_g, self._seg_used, dH, B, T, Dt)
         dy, d1, d2 = ws["t_da"], ws["t_db"], ws["t_dc"]
         dy.copy_(dH)                                                 # the last layer's output is always among the summed states
@@ -477,20 +537,28 @@ class Engine:
             # y = LN2(x2), x2 = r + FC2(GELU(FC1(r)))
             ops.layernorm_bwd(dy, ws[f"t_x2{l}"], st2[0], st2[1], f32(b + "feedforward_layernorm.weight"), d1,
                               grad(b + "feedforward_layernorm.weight"), grad(b + "feedforward_layernorm.bias"))
-            ops.gemm_tn(d1, ws[f"t_h{l}"], grad(b + "feedforward.model.2.weight"), db=grad(b + "feedforward.model.2.bias"))
-            ops.gemm_nt(d1, w16t(b + "feedforward.model.2.weight"), ws["t_dz"], aux=ws[f"t_dg{l}"], epi=ops.EPI_MUL_AUX)
+            dz = ops.dropout_apply(d1, ws["t_dzd"], self._drop_rng(4 * l + 2, ph)) if ph > 0.0 else d1
+            ops.gemm_tn(dz, ws[f"t_h{l}"], grad(b + "feedforward.model.2.weight"), db=grad(b + "feedforward.model.2.bias"))
+            ops.gemm_nt(dz, w16t(b + "feedforward.model.2.weight"), ws["t_dz"], aux=ws[f"t_dg{l}"], epi=ops.EPI_MUL_AUX)
             ops.gemm_tn(ws["t_dz"], ws[f"t_r{l}"], grad(b + "feedforward.model.0.weight"), db=grad(b + "feedforward.model.0.bias"))
             ops.gemm_nt(ws["t_dz"], w16t(b + "feedforward.model.0.weight"), d2, residual=d1)                  # d r = d x2 + dz W1
             # r = LN1(x1), x1 = x + out_proj(attention(qkv(x)))
             ops.layernorm_bwd(d2, ws[f"t_x1{l}"], st1[0], st1[1], f32(b + "attention_layernorm.weight"), d1,
                               grad(b + "attention_layernorm.weight"), grad(b + "attention_layernorm.bias"))
-            ops.gemm_tn(d1, ws[f"t_att{l}"], grad(b + "attention.output_proj.weight"), db=grad(b + "attention.output_proj.bias"))
-            ops.gemm_nt(d1, w16t(b + "attention.output_proj.weight"), ws["t_datt"])
-            ops.attn_bwd(ws[f"t_qkv{l}"], ws[f"t_att{l}"], ws["t_datt"], ws[f"t_lse{l}"], km, ws["t_dqkv"], ws["t_delta"], B, T, H)
+            dz = ops.dropout_apply(d1, ws["t_dzd"], self._drop_rng(4 * l + 1, ph)) if ph > 0.0 else d1
+            ops.gemm_tn(dz, ws[f"t_att{l}"], grad(b + "attention.output_proj.weight"), db=grad(b + "attention.output_proj.bias"))
+            ops.gemm_nt(dz, w16t(b + "attention.output_proj.weight"), ws["t_datt"])
+            if pa > 0.0:
+                ops.attn_drop_bwd(ws[f"t_qkv{l}"], ws[f"t_att{l}"], ws["t_datt"], ws[f"t_lse{l}"], km, ws["t_dqkv"], ws["t_delta"], B, T, H,
+                                  self._drop_rng(4 * l, pa))
+            else:
+                ops.attn_bwd(ws[f"t_qkv{l}"], ws[f"t_att{l}"], ws["t_datt"], ws[f"t_lse{l}"], km, ws["t_dqkv"], ws["t_delta"], B, T, H)
             ops.gemm_tn(ws["t_dqkv"], ws[f"t_x{l}"], grad(b + "attention.input_proj.weight"), db=grad(b + "attention.input_proj.bias"))
             ops.gemm_nt(ws["t_dqkv"], w16t(b + "attention.input_proj.weight"), dy, residual=d1)               # d x = d x1 + dqkv Wqkv
             if l >= self._text_first_sel:                          # hidden_states[l] is one of the summed states too
                 dy.add_(dH)
+        if ph > 0.0:                                              # hidden_states[0] is the embedding output AFTER its dropout
+            ops.dropout_apply(dy, dy, self._drop_rng(ops.DROPOUT_SITE_EMBED, ph))
         g_word = grad("word_embeddings")
         ops.call("text_embed_ln_bwd", ids32, tt32, f32("word_embeddings"), f32("position_embeddings"), f32("token_type_embeddings"),
                  f32("emb_layernorm.weight"), dy, ws["t_dxemb"], grad("emb_layernorm.weight"), grad("emb_layernorm.bias"), g_word, B, T, Dt,
@@ -888,13 +956,13 @@ class Engine:
             main, side = torch.cuda.current_stream(), self._side_stream()
             ev = torch.cuda.Event(); ev.record(main); side.wait_event(ev)
             with torch.cuda.stream(side):
-                self.forward_text(batch["ids"], batch["attn_mask"], batch.get("token_type"))
+                self.forward_text(batch["ids"], batch["attn_mask"], batch.get("token_type"), training=True)
                 done = torch.cuda.Event(); done.record(side)
             self.forward_image(batch["image"])
             main.wait_event(done)
         else:
             self.forward_image(batch["image"])
-            self.forward_text(batch["ids"], batch["attn_mask"], batch.get("token_type"))
+            self.forward_text(batch["ids"], batch["attn_mask"], batch.get("token_type"), training=True)
         self.forward_backward_losses(batch["label"], loss_scale)
         if self.dist:
             from . import dist as D_
@@ -911,6 +979,7 @@ class Engine:
             if self.dist and optimizer:                           # the text tower's gradient: one more all-reduce (not overlapped)
                 from . import dist as D_
                 D_.allreduce_mean_(self.tstore.g32)
+        self.dropout_step += 1                                      # the next call draws new masks (evaluation never advances it)
         if optimizer:
             self.optimizer_step()
         lp = self.ws["loss_parts"]

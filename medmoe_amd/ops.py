@@ -315,6 +315,92 @@ def attn_bwd(qkv, out, dout, lse, key_mask, dqkv, delta, B, N, H):
 
 
 # ---------------------------------------------------------------------------------------------
+# dropout of the trainable text tower (csrc/dropout.hip): the mask is a function of (seed, step, site, element), see csrc/philox.h
+# ---------------------------------------------------------------------------------------------
+DROPOUT_SITE_EMBED = 0xFFFFFFFF      # the embedding LayerNorm's output; a layer's sites are 4 * layer + {0 attention probabilities, 1 after out_proj, 2 after FC2}
+
+
+def dropout_thresh(p: float) -> int:
+    """floor(p * 2^32): an element survives iff its 32-bit random word is >= this (p * 2^32 is exact in a double)."""
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"dropout probability must be in [0, 1), got {p}")
+    return int(p * 4294967296.0)
+
+
+def dropout_rng(seed: int, step: int, site: int, p: float):
+    """The five by-value launch arguments every dropout kernel takes: (seed, step, site, thresh, scale = 1 / (1 - p))."""
+    seed &= 0xFFFFFFFFFFFFFFFF
+    if seed >= 1 << 63:
+        seed -= 1 << 64              # the same 64 bits as a signed C long long
+    return (seed, step & 0xFFFFFFFF, site & 0xFFFFFFFF, dropout_thresh(p), 1.0 / (1.0 - p))
+
+
+def dropout_mask(out, rows, cols, cols_padded, rng):
+    """out[rows, cols] uint8 = 1 where the element survives (tests / debugging: no product path stores a mask)."""
+    _need(out, torch.uint8, "out")
+    if out.numel() != rows * cols or not out.is_contiguous() or cols_padded % 4 or cols_padded < cols:
+        raise ValueError("dropout_mask: out must be contiguous [rows, cols], cols_padded a multiple of 4 and >= cols")
+    call("dropout_mask", out, rows, cols, cols_padded, *rng[:4])
+    return out
+
+
+def dropout_apply(x, y, rng):
+    """y = keep * x / (1 - p) over the rows of a contiguous [rows, cols] bf16 / fp32 tensor (cols % 4 == 0); y may be x."""
+    if x.dtype not in (torch.bfloat16, torch.float32) or y.dtype != x.dtype:
+        raise TypeError("dropout_apply: x and y must both be bf16 or both fp32")
+    _require_gpu(x, "dropout_apply"); _require_gpu(y, "dropout_apply")
+    cols = x.shape[-1]
+    if not x.is_contiguous() or not y.is_contiguous() or y.numel() != x.numel() or cols % 4:
+        raise ValueError("dropout_apply: x / y must be contiguous, equally sized, with a last dimension that is a multiple of 4")
+    call("dropout_apply", x, y, x.numel() // cols, cols, 1 if x.dtype == torch.float32 else 0, *rng)
+    return y
+
+
+def dropout_add_layernorm_fwd(z, residual, gamma, beta, x1, y, mean, rstd, eps, rng):
+    """x1 = residual + keep * z / (1 - p); y = LayerNorm(x1); mean / rstd as layernorm_fwd leaves them (layernorm_bwd runs on x1)."""
+    for t, nm in ((z, "z"), (residual, "residual"), (x1, "x1"), (y, "y")):
+        _need(t, torch.bfloat16, nm)
+        if not t.is_contiguous() or t.numel() != z.numel():
+            raise ValueError(f"dropout_add_layernorm_fwd: {nm} must be contiguous and sized like z")
+    for t, nm in ((gamma, "gamma"), (beta, "beta"), (mean, "mean"), (rstd, "rstd")):
+        _need(t, torch.float32, nm)
+    D = z.shape[-1]
+    rows = z.numel() // D
+    if gamma.numel() != D or beta.numel() != D or mean.numel() < rows or rstd.numel() < rows:
+        raise ValueError("dropout_add_layernorm_fwd: gamma / beta must hold D values, mean / rstd one per row")
+    call("dropout_add_layernorm_fwd", z, residual, gamma, beta, x1, y, mean, rstd, rows, D, eps, *rng)
+    return y
+
+
+def _attn_drop_check(name, qkv, out, lse, key_mask, B, N, H):
+    _need(qkv, torch.bfloat16, "qkv"); _need(out, torch.bfloat16, "out"); _need(lse, torch.float32, "lse")
+    D = H * 64
+    if qkv.numel() != B * N * 3 * D or out.numel() != B * N * D or lse.numel() != B * H * N:
+        raise ValueError(f"{name}: buffer sizes do not match (B,N,H)")
+    if key_mask is not None:
+        _need(key_mask, torch.uint8, "key_mask")
+        if key_mask.numel() != B * N:
+            raise ValueError(f"{name}: key_mask must be [B,N]")
+
+
+def attn_drop_fwd(qkv, out, lse, key_mask, B, N, H, rng, head_dim=64):
+    """attn_fwd for N <= 80 with dropout on the probabilities (lse: of the undropped softmax)."""
+    _attn_drop_check("attn_drop_fwd", qkv, out, lse, key_mask, B, N, H)
+    call("attn_drop_fwd", qkv, out, lse, key_mask, B, N, H, head_dim, *rng)
+    return out
+
+
+def attn_drop_bwd(qkv, out, dout, lse, key_mask, dqkv, delta, B, N, H, rng, head_dim=64):
+    """attn_bwd for N <= 80 under the forward's dropout mask, regenerated from the same (seed, step, site): one kernel."""
+    _attn_drop_check("attn_drop_bwd", qkv, out, lse, key_mask, B, N, H)
+    _need(dout, torch.bfloat16, "dout"); _need(dqkv, torch.bfloat16, "dqkv"); _need(delta, torch.float32, "delta")
+    if dqkv.numel() != qkv.numel() or dout.numel() != out.numel() or delta.numel() != lse.numel():
+        raise ValueError("attn_drop_bwd: buffer sizes do not match (B,N,H)")
+    call("attn_drop_bwd", qkv, out, dout, lse, key_mask, dqkv, delta, B, N, H, head_dim, *rng)
+    return dqkv
+
+
+# ---------------------------------------------------------------------------------------------
 # generic caller for the remaining entry points: sig chars  p=pointer(tensor|None) i=int l=int64 f=float d=double
 # ---------------------------------------------------------------------------------------------
 _SIGS = {
@@ -340,6 +426,8 @@ _SIGS = {
     "text_pack": "pppppii", "segment_map": "pippppiiii", "text_aggregate_bwd": "ppppiii", "text_embed_ln_bwd": "pppppppppppiiiif", "text_embed_ln_packed": "ppppppppiiiifpp", "text_aggregate_packed": "ppppipppppiii",
     "layernorm_fwd_rows": "ppppppiifip", "attn_fwd_varlen": "ppppiiii",
     "win_attn_fwd": "ppppiiiiii", "win_attn_bwd": "ppppppiiiiii", "patch_merge": "ppiiiii", "drop_path": "ppppil",
+    "dropout_mask": "pliillll", "dropout_apply": "ppliillllf", "dropout_add_layernorm_fwd": "ppppppppiifllllf",
+    "attn_drop_fwd": "ppppiiiillllf", "attn_drop_bwd": "pppppppiiiillllf",
     "sumsq": "plp", "sumsq_det": "plpp", "adam_step": "pppppldddddipff", "cast_bf16": "ppl", "transpose_many": "pppii",
 }
 
@@ -416,6 +504,9 @@ _COSTS = {
     "adam_step": lambda a: ("adam_kernel", 34.0 * a[5], "byte"),                                   # p, g, m, v read; p, m, v, bf16 copy written
     "scale_attn_bwd": lambda a: ("scale_attn_bwd_kernel", 2.0 * a[17] * (4 * (2 * a[18] + 2 * a[19]) + 2 * a[18]), "byte"),    # G, dG, H1, dH1 x 4 scales + eout, d_img_l rows
     "scale_attn_fwd": lambda a: ("scale_attn_fwd_kernel", 2.0 * a[8] * (4 * (a[9] + a[10]) + a[9]), "byte"),
+    "dropout_add_layernorm_fwd": lambda a: ("dropout_add_layernorm_fwd_kernel", 8.0 * a[8] * a[9], "byte"),    # z, residual read; x1, y written
+    "attn_drop_fwd": lambda a: ("attn_drop_fwd_kernel", 4.0 * a[5] * a[5] * 64 * a[4] * a[6], "flop"),
+    "attn_drop_bwd": lambda a: ("attn_drop_bwd_kernel", 10.0 * a[8] * a[8] * 64 * a[7] * a[9], "flop"),
     "layernorm_fwd_rows": lambda a: ("layernorm_fwd_kernel", 4.0 * (ROWS_HINT or a[6]) * a[7], "byte"),
 }
 

@@ -64,8 +64,9 @@ class SwinEngine:
         masks = torch.floor(torch.rand(len(rates), B, device=self.device) + keep)
         return [None if r == 0.0 else masks[i] for i, r in enumerate(rates)]
 
-    def forward(self, batch: Dict[str, torch.Tensor], drop_path=None):
-        """Both towers' forward.  Returns the encoder's output dict; the text outputs are in the engine's workspace."""
+    def forward(self, batch: Dict[str, torch.Tensor], drop_path=None, training: bool = False):
+        """Both towers' forward.  Returns the encoder's output dict; the text outputs are in the engine's workspace.
+        `training`: the text pass of a training step (a trainable tower applies its dropout, Engine.forward_text)."""
         eng, enc = self.eng, self.enc
         images = batch["image"]
         B = images.shape[0]
@@ -75,7 +76,7 @@ class SwinEngine:
         side = eng._side_stream()
         ev = torch.cuda.Event(); ev.record(main); side.wait_event(ev)
         with torch.cuda.stream(side):                               # the text tower is independent of the image encoder
-            eng.forward_text(batch["ids"], batch["attn_mask"], batch.get("token_type"))
+            eng.forward_text(batch["ids"], batch["attn_mask"], batch.get("token_type"), training=training)
             done = torch.cuda.Event(); done.record(side)
         out = enc.forward(images.contiguous(), drop_path=drop_path, drop_path_rate=self.drop_path_rate)
         main.wait_event(done)
@@ -88,7 +89,8 @@ class SwinEngine:
         B = batch["image"].shape[0]
         if self.train_text and zero_grad:
             eng.tstore.zero_grad()
-        out = self.forward(batch, self._drop_path_masks(B))
+        out = self.forward(batch, self._drop_path_masks(B), training=True)
+        eng.dropout_step += 1                                       # as Engine.train_step: one per call, the text pass above used the old value
         ws = eng.ws
         local = out["local_feat"]                                   # bf16 [B, 3136, 768]
         HW, D = local.shape[1], local.shape[2]

@@ -53,7 +53,7 @@ def config_from_hydra(vision: Any, text: Any) -> MedMoEConfig:
     if name:
         c = config_by_name(name)
         c.freeze_text = bool(_get(text, "freeze_bert", True))
-        return c
+        return _text_dropout(c, text)
     c = MedMoEConfig(**_ARCH[_get(vision, "arch", "vit_b16")])
     c.n_expert = int(_get(vision, "num_experts", 6))          # swin.py:83 default K=6 modalities
     c.top_k = int(_get(vision, "top_k", 1))
@@ -69,6 +69,14 @@ def config_from_hydra(vision: Any, text: Any) -> MedMoEConfig:
                                   f"or mxfp8 (e4m3 with one power-of-two scale per block of 32, the block-scaled MFMA)")
     c.expert_fp8 = dt == "fp8"
     c.expert_mx = dt == "mxfp8"
+    return _text_dropout(c, text)
+
+
+def _text_dropout(c: MedMoEConfig, text: Any) -> MedMoEConfig:
+    """Hugging Face's BertConfig names (both 0.1 there; 0.0 here unless set): train-mode dropout of a trainable text tower."""
+    c.text_hidden_dropout = float(_get(text, "hidden_dropout_prob", 0.0))
+    c.text_attn_dropout = float(_get(text, "attention_probs_dropout_prob", 0.0))
+    c.dropout_seed = int(_get(text, "dropout_seed", 0))
     return c
 
 

@@ -229,8 +229,12 @@ class MedMoEPretrainingLightningModule(_Base):
             state[name] = {"step": int(st.step_count), "numel": int(m.numel()), "exp_avg": m.detach().cpu().clone(),
                            "exp_avg_sq": v.detach().cpu().clone()}
         checkpoint["fused_adam"] = state
+        # the text tower's dropout masks are a function of (seed, step, site, element): the step counter resumes where it stopped
+        checkpoint["text_dropout_step"] = int(self.model.engine.dropout_step)
 
     def on_load_checkpoint(self, checkpoint: Dict[str, Any]) -> None:
+        if self.fused_step and "text_dropout_step" in checkpoint:
+            self.model.engine.dropout_step = int(checkpoint["text_dropout_step"])
         state = checkpoint.get("fused_adam") if self.fused_step else None
         if not state:
             return
