@@ -9,7 +9,7 @@ FLAGS := --offload-arch=$(ARCH) -O3 -fPIC -std=c++17 -Iinclude -I$(CSRC) -Wno-un
 
 all: $(LIB)
 
-build/%.o: $(CSRC)/%.hip $(CSRC)/common.h $(CSRC)/philox.h
+build/%.o: $(CSRC)/%.hip $(CSRC)/common.h $(CSRC)/philox.h $(CSRC)/det_plan.h
 	@mkdir -p build
 	$(HIPCC) $(FLAGS) -c $< -o $@
 
@@ -17,7 +17,14 @@ $(LIB): $(OBJS)
 	@mkdir -p medmoe_amd/lib
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(OBJS)
 
+# host-only check of the staged wgrad plans (det_plan.h: range enumeration, slots, scratch sizes) under the sanitizers
+CXX ?= c++
+check-plan: tools/det_plan_check.cpp $(CSRC)/det_plan.h
+	@mkdir -p build
+	$(CXX) -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I$(CSRC) $< -o build/det_plan_check
+	build/det_plan_check
+
 clean:
 	rm -rf build $(LIB)
 
-.PHONY: all clean
+.PHONY: all clean check-plan

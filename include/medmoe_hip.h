@@ -57,9 +57,12 @@ int medmoe_gemm_nt_tiles256(const void* A, int lda, const void* B, int ldb, void
 /* wgrad dW += G^T X (+ bias grad), replaces autograd of the same Linear layers */
 int medmoe_gemm_tn(const void* G, int ldg, const void* X, int ldx, float* dW, int ldw, float* db, int M, int Nn, int Kk, const int* x_rowmap, const int* g_rowmap, const int* row_off, int n_groups, long long strideW, long long strideDb, int nsplit, hipStream_t stream);
 /* the plain wgrad (no row maps, no groups) in two stages when the shape allows (Nn, Kk multiples of 256, M % 32 == 0, M >= 4096): the
-   workgroups STORE their partial 256 x 256 tiles into `scratch` (scratch_floats >= tiles x row ranges x 65536; owned by the caller, one per
-   stream) and a second kernel sums them into dW in a fixed order - no fp32 atomics on dW (deterministic, and ~20 us cheaper per launch than
-   64 MB of memory-side atomics).  Any other shape, or scratch too small / null: medmoe_gemm_tn with nsplit 16 */
+   workgroups STORE their partial 256 x 256 tiles into `scratch` (scratch_floats >= slots x 65536, slots = tiles x row ranges <= 256; owned by
+   the caller, one per stream) and a second kernel sums them into dW in a fixed order - no fp32 atomics on dW (deterministic, and ~20 us
+   cheaper per launch than 64 MB of memory-side atomics).  db: with scratch_floats >= slots x (65536 + 512) every partial tile also stores its
+   512 column sums of G behind the tiles and the summing kernel (tn_reduce_det_kernel then) adds them to db in range order - no atomics at
+   all; with a scratch between the two sizes dW is staged and db keeps its atomicAdd (counted by medmoe_nondet_launches).  256 x (65536 + 512)
+   floats serve every shape.  Any other shape, or scratch below slots x 65536 / null: medmoe_gemm_tn with nsplit 16 */
 int medmoe_gemm_tn_staged(const void* G, int ldg, const void* X, int ldx, float* dW, int ldw, float* db, int M, int Nn, int Kk, float* scratch, long long scratch_floats, hipStream_t stream);
 
 /* cross entropy over rows/columns of a similarity matrix + gradient (losses.py:789-794,1017-1021,582-584) */
@@ -330,6 +333,41 @@ int medmoe_dropout_add_layernorm_fwd(const void* z, const void* residual, const 
    undropped softmax, out = (keep * P * scale) V; the mask row of query q of (b, h) is (b * H + h) * N + q, its key axis padded to a multiple of 4 */
 int medmoe_attn_drop_fwd(const void* qkv, void* out, float* lse, const unsigned char* key_mask, int B, int N, int H, int head_dim, long long seed, long long step, long long site, long long thresh, float scale, hipStream_t stream);
 int medmoe_attn_drop_bwd(const void* qkv, const void* out, const void* dout, const float* lse, const unsigned char* key_mask, void* dqkv, float* delta, int B, int N, int H, int head_dim, long long seed, long long step, long long site, long long thresh, float scale, hipStream_t stream);
+
+/* ---- deterministic mode (MedMoEConfig.deterministic): the same results as the entry points they are named after, up to summation order, with
+   no sum whose order depends on which workgroup or wave arrives first.  Two forms: STAGED - partial results leave with plain stores into a
+   scratch buffer of the caller's (one per stream: launches that may overlap must not share it) and a second kernel adds them in index order;
+   SINGLE WRITER - the launch is shaped so that one workgroup adds to an output element.  A scratch that is too small is MM_ERR_ARG, never a
+   fall-back to the atomic form.  No process-global switch: the caller chooses the entry point. */
+/* medmoe_gemm_tn (dW and db): staged on the four-wave kernel for plain rows / one row map / router groups with Kk % 256 == 0, Nn % 128 == 0
+   (plain: % 256, M % 32 == 0, M >= 4096) and at least 2048 rows per group - a group's ranges are enumerated from row_off on the device by the
+   GEMM and by the summing kernel alike; every other shape: one workgroup per (group, 128 x 128 tile).  scratch_floats >=
+   medmoe_gemm_tn_det_scratch(M, Nn, Kk, x_rowmap != NULL, g_rowmap != NULL, row_off != NULL, n_groups) (0: the shape needs none) */
+int medmoe_gemm_tn_det(const void* G, int ldg, const void* X, int ldx, float* dW, int ldw, float* db, int M, int Nn, int Kk, const int* x_rowmap, const int* g_rowmap, const int* row_off, int n_groups, long long strideW, long long strideDb, float* scratch, long long scratch_floats, hipStream_t stream);
+long long medmoe_gemm_tn_det_scratch(int M, int Nn, int Kk, int x_mapped, int g_mapped, int grouped, int n_groups);
+/* medmoe_gemm_tn_cols, staged when a tile has more than one row range; scratch_floats >= medmoe_gemm_tn_cols_det_scratch(M, Nn, Kk, n_groups) */
+int medmoe_gemm_tn_cols_det(const void* G, int ldg, const void* X, int ldx, float* dW, int ldw, int M, int Nn, int Kk, int n_groups, long long gcol_stride, long long xcol_stride, long long strideW, int g_chunk_w, long long g_chunk_stride, float* scratch, long long scratch_floats, hipStream_t stream);
+long long medmoe_gemm_tn_cols_det_scratch(int M, int Nn, int Kk, int n_groups);
+/* medmoe_gemm_tn_gram with a single writer per output tile (no split over the rows) */
+int medmoe_gemm_tn_gram_det(const void* A, int lda, const float* w, long long w_gstride, int w_ld, float* dW, int ldw, int M, int Nn, int n_groups, long long col_stride, long long strideW, hipStream_t stream);
+/* medmoe_layernorm_bwd, dgamma / dbeta staged per workgroup; scratch_floats >= medmoe_layernorm_bwd_det_scratch(D) */
+int medmoe_layernorm_bwd_det(const void* dy, const void* x, const float* mean, const float* rstd, const float* gamma, const void* add, void* dx, float* dgamma, float* dbeta, int rows, int D, float* scratch, long long scratch_floats, hipStream_t stream);
+long long medmoe_layernorm_bwd_det_scratch(int D);
+/* medmoe_scale_attn_bwd, dw2 / db2 / dgate staged per wave (a wave's rows lie in one slot); row_off [E + 1]: medmoe_dispatch's first slot row
+   of every expert; scratch_floats >= medmoe_scale_attn_bwd_det_scratch(R, P, Dh) */
+int medmoe_scale_attn_bwd_det(const void* d_img_l, const float* d_img_g, const void* G, const void* H1, const float* wts, const float* w2, const void* expert_out, const int* expert_of_slot, const int* item_of_slot, const float* gates, int k, int P, void* dG, void* dH1, float* dw2, float* db2, float* dgate, int R, int Do, int Dh, const int* row_off, int E, float* scratch, long long scratch_floats, hipStream_t stream);
+long long medmoe_scale_attn_bwd_det_scratch(int R, int P, int Dh);
+/* medmoe_router_bwd with the cross-entropy and the accuracy summed in sample order; parts: 2 * B floats */
+int medmoe_router_bwd_det(const float* probs, const float* h, const float* w2, const int* idx, const float* dgates, const int* labels, const float* dprobs_ext, float ce_scale, float* dlogits, float* dh, float* loss_acc, int B, int Hd, int E, int k, float* parts, hipStream_t stream);
+/* the three loss heads with loss_acc += the rows' terms in row order; parts: `rows` floats */
+int medmoe_ce_strided_det(const float* X, float* dX, int rows, int cols, long long rs, long long cs, int label_off, float xscale, float w, int accumulate, float* loss_acc, float* parts, hipStream_t stream);
+int medmoe_soft_xent_strided_det(const float* X, float* dX, const float* soft, int rows, int cols, long long rs, long long cs, float xscale, float t1, float t2, float w, int accumulate, float* loss_acc, float* parts, hipStream_t stream);
+int medmoe_hardneg_strided_det(const float* X, float* dX, int rows, int cols, long long rs, long long cs, float margin, float w, int accumulate, float* loss_acc, float* parts, hipStream_t stream);
+/* medmoe_cos_scale_bwd with cb summed by one thread per column in row order */
+int medmoe_cos_scale_bwd_det(float* dC, const float* C, const float* na, const float* nb, float* ca, float* cb, int M, int N, float eps, hipStream_t stream);
+/* how many launches of this process took an order-dependent form so far (an atomic epilogue with more than one writer per element, an atomic
+   loss sum): counted on the host, one add per such launch.  A deterministic step leaves it unchanged. */
+long long medmoe_nondet_launches(void);
 
 #ifdef __cplusplus
 }

@@ -32,6 +32,9 @@ class MedMoEConfig:
     text_hidden_dropout: float = 0.0
     text_attn_dropout: float = 0.0
     dropout_seed: int = 0
+    # deterministic mode (trainer.deterministic): no launch of a step whose result depends on the order in which workgroups or waves arrive -
+    # staged or single-writer forms of every weight-gradient GEMM, LayerNorm / scale-attention parameter gradient and loss sum
+    deterministic: bool = False
     # MoE (swin.py:82-92)
     n_expert: int = 4
     top_k: int = 1

@@ -129,6 +129,34 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 bool mm_launch_scores512(const void* ctx, const void* words, const int* cap_lens, void* a1, float* lse, int B, int Bc, int HW, int T,
                          int D, const int* cap_list, int n_cap, int ntt, long long col_base, long long ldp, hipStream_t stream);
 
+// launches that took an order-dependent form (medmoe_nondet_launches, defined in gemm.hip): host-side, one add per such launch.  One
+// counter for all the library's translation units (a file-level static could not be shared), hidden: not part of the ABI.
+extern __attribute__((visibility("hidden"))) long long g_mm_nondet;
+
+// dst[c] += rec[first*stride + c] + rec[(first+1)*stride + c] + ... (count records) for the float4 column group `c4` of this thread, summed in
+// a FIXED order whatever finished first: row ty of the 16-row block takes records ty, ty + 16, ..., the 16 rows meet in LDS in row order.
+// Call from a (64, 16) block; every thread of the block must call it (barriers inside).
+__device__ __forceinline__ float4 det_sum_records(const float* __restrict__ rec, long long stride, int count, int c4, bool on,
+                                                  float4 (*red)[64]) {
+  float4 s = {0.f, 0.f, 0.f, 0.f};
+  if (on)
+    for (int r = threadIdx.y; r < count; r += 16) {
+      const float4 v = *(const float4*)(rec + (long long)r * stride + c4 * 4);
+      s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+    }
+  red[threadIdx.y][threadIdx.x] = s;
+  __syncthreads();
+  float4 t = {0.f, 0.f, 0.f, 0.f};
+  if (threadIdx.y == 0)
+#pragma unroll
+    for (int w = 0; w < 16; ++w) { const float4 v = red[w][threadIdx.x]; t.x += v.x; t.y += v.y; t.z += v.z; t.w += v.w; }
+  __syncthreads();
+  return t;
+}
+
+// loss.hip: out[seg] += parts[seg * n + 0] + ... + parts[seg * n + n - 1] for seg < nseg, in a fixed order (one workgroup per segment)
+void mm_launch_det_sum(const float* parts, int n, int nseg, float* out, hipStream_t stream);
+
 static inline int mm_check_launch() {
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? MM_OK : MM_ERR_LAUNCH;

@@ -560,6 +560,7 @@ extern "C" int medmoe_text_embed_ln_bwd(const int* ids, const int* type_ids, con
   if (!ids || !word || !pos || !type || !gamma || !dy || !dx || !dgamma || !dbeta || !g_word) return MM_ERR_ARG;
   if (B <= 0 || T <= 0 || D <= 0 || (D % 4) || D > 2048 || vocab <= 0) return MM_ERR_SHAPE;
   const int rows = B * T;
+  ++g_mm_nondet;                                    // word rows shared by tokens and dgamma / dbeta meet in atomics
   hipLaunchKernelGGL(text_embed_ln_bwd_kernel, dim3(min((rows + 3) / 4, 256 * 4)), dim3(256), 0, stream, ids, type_ids, word, pos, type, gamma,
                      (const bf16_t*)dy, dx, dgamma, dbeta, g_word, rows, T, D, vocab, eps);
   return mm_check_launch();

@@ -13,6 +13,7 @@
 // ds_read_b64_tr_b16 transposed LDS reads (the contraction index is the ROW of both operands);
 // a 32x32 accumulator register is two 128-B row segments = the full-rate float-atomic shape.
 #include "common.h"
+#include "det_plan.h"
 #include <utility>
 
 #define BM 128
@@ -1504,7 +1505,8 @@ struct GemmTNArgs {
   long long gcol_stride, xcol_stride;      // COLG build: group g reads the columns G + g * gcol_stride, X + g * xcol_stride (all M rows)
   long long g_chunk_stride; int g_chunk_w;  // COLG build, g_chunk_w > 0: G column c lives at (c / g_chunk_w) * g_chunk_stride + c % g_chunk_w
   const float* gscale; long long gscale_gstride; int gscale_ld;   // SCALE build: G row m of group g is multiplied by gscale[g * gscale_gstride + m * gscale_ld]
-  float* partial;   // plain gemm_tn4w build, non-null: every workgroup STORES its 256 x 256 fp32 tile at partial + id * 65536 (accumulator order) instead of adding it to dW atomically; tn_reduce_kernel sums the row ranges
+  float* partial;   // gemm_tn4w builds, non-null: every workgroup STORES its 256 x 256 fp32 tile at partial + id * 65536 (accumulator order) instead of adding it to dW atomically; tn_reduce_kernel / tn_reduce_det_kernel sum the row ranges
+  float* db_partial = nullptr;   // with partial: the waves' column sums of G go to db_partial + id * 512 (plain stores) instead of atomics on db
 };
 
 template <bool MAPPED>
@@ -2423,28 +2425,18 @@ __global__ __launch_bounds__(256) void gemm_tn4w_kernel(GemmTNArgs p) {
   const int wm = wid & 1, wn = wid >> 1;          // wave tile: G columns wm*128.., X columns wn*128..
   int id = xcd_remap(blockIdx.x, gridDim.x);      // split-major ids: the tiles of one M range (same G / X rows) sit on one XCD
   const int ntile = p.tiles_n * p.tiles_k;
-  int group = 0, ms, me, pid = 0;
+  int group = 0, ms, me;
   if (MAPPED && p.row_off) {
     // ranges of p.nsplit ROWS each, enumerated over the groups on the device (the group sizes are only known here): every
     // workgroup gets the same amount of work however unequal the groups are; the tiles of one range are adjacent ids
+    // (det_plan::tn_group_range: tn_reduce_det_kernel and the host check walk the same enumeration)
     const int tile = id % ntile;
-    int rid = id / ntile;
-    const int R = p.nsplit;
-    ms = -1; me = -1;
-    for (int gq = 0; gq < p.n_groups; ++gq) {
-      const int a = p.row_off[gq], b = p.row_off[gq + 1];
-      const int nr = (b - a + R - 1) / R;
-      if (rid < nr) { group = gq; ms = a + rid * R; me = min(b, ms + R); break; }
-      rid -= nr;
-    }
-    if (ms < 0) return;
+    if (!det_plan::tn_group_range(p.row_off, p.n_groups, p.nsplit, id / ntile, group, ms, me)) return;
     id = tile;
   } else {
     if (COLG) { group = id / (ntile * p.nsplit); id -= group * ntile * p.nsplit; }
-    pid = id;                                     // = split * ntile + tile: the slot of this workgroup's partial tile (staged plain build)
     const int split = id / ntile; id -= split * ntile;
-    const int chunk = (((p.M + 31) / 32 + p.nsplit - 1) / p.nsplit) * 32;
-    ms = split * chunk; me = min(p.M, ms + chunk);
+    det_plan::tn_split_range(p.M, p.nsplit, split, ms, me);
   }
   const int tile_n = id / p.tiles_k, tile_k = id - tile_n * p.tiles_k;
   if (ms >= me) return;
@@ -2703,11 +2695,14 @@ __global__ __launch_bounds__(256) void gemm_tn4w_kernel(GemmTNArgs p) {
 
   float* dW = p.dW + ((MAPPED || COLG) ? (long long)group * p.strideW : 0ll);
   const int kcol = lane & 31;
-  bool staged = false;
-  if constexpr (!MAPPED && !COLG) staged = p.partial != nullptr;
+  const bool staged = p.partial != nullptr;
+  // the slot of this workgroup's partial tile is its (remapped) id: split * ntile + tile in the plain build, range * ntile + tile in the
+  // MAPPED one, (group * nsplit + split) * ntile + tile in the COLG one - recomputed here, not kept across the k-loop
+  const int pid = staged ? xcd_remap(blockIdx.x, gridDim.x) : 0;
   if (staged) {
     // STAGED: 256 whole-wave 256-byte stores in accumulator order [wave][tn][tk][r][lane] - plain stores leave a CU five times faster than
-    // the same bytes as fp32 atomics (which execute at the memory side, ~1.3 TB/s chip-wide: 64 MB per launch whatever the row count)
+    // the same bytes as fp32 atomics (which execute at the memory side, ~1.3 TB/s chip-wide: 64 MB per launch whatever the row count).
+    // MAPPED / COLG: rows and columns past Nn / Kk are stored too (whatever they hold); the summing kernel never reads them back into dW.
     float* part = p.partial + ((long long)pid << 16) + (wid << 14) + lane;
 #pragma unroll
     for (int tn = 0; tn < 4; ++tn)
@@ -2729,11 +2724,14 @@ __global__ __launch_bounds__(256) void gemm_tn4w_kernel(GemmTNArgs p) {
     }
   }
   if (do_db) {
+    const bool db_staged = staged && p.db_partial != nullptr;
 #pragma unroll
     for (int tn = 0; tn < 4; ++tn) {
       const float v = colsum[tn] + __shfl_xor(colsum[tn], 32, 64);
       const int n = n0 + wm * 128 + tn * 32 + kcol;
-      if (h == 0 && (!(MAPPED || COLG) || n < p.Nn)) atomicAdd(p.db + ((MAPPED || COLG) ? (long long)group * p.strideDb : 0ll) + n, v);
+      if (db_staged) {                // [slot][wave][tn][column]: the two waves that took turns on the same G columns keep separate sums
+        if (h == 0) p.db_partial[((long long)pid << 9) + (wid << 7) + tn * 32 + kcol] = v;
+      } else if (h == 0 && (!(MAPPED || COLG) || n < p.Nn)) atomicAdd(p.db + ((MAPPED || COLG) ? (long long)group * p.strideDb : 0ll) + n, v);
     }
   }
 }
@@ -2764,9 +2762,64 @@ __global__ __launch_bounds__(256) void tn_reduce_kernel(const float* __restrict_
   *d = o;
 }
 
+// The summing kernel of every other staged launch (deterministic mode): dW[group] tile += the partial tiles of its slots, walked in slot
+// order, and db[group] += the slots' column sums (wave wn = 0, then wn = 1 of each slot).  64 blocks per (group, 256 x 256 tile), a float4
+// per thread; rows >= Nn and columns >= Kk of a tile are never written (Kk % 8 == 0: a float4 is inside or outside as a whole).
+//   mode 0: slot = (group * nsplit + sp) * ntile + tile for sp < nvalid (plain / row-mapped ranges: group 0; COLG: column groups)
+//   mode 1: the ranges of R rows enumerated from row_off exactly as gemm_tn4w_kernel<true> enumerates them - a group's ranges are adjacent
+struct TnReduceArgs {
+  const float* partial; const float* db_partial; float* dW; float* db; const int* row_off;
+  long long strideW, strideDb;
+  int ldw, Nn, Kk, tiles_n, tiles_k, mode, nsplit, nvalid, n_groups, R, vec;
+};
+__global__ __launch_bounds__(256) void tn_reduce_det_kernel(TnReduceArgs p) {
+  const int ntile = p.tiles_n * p.tiles_k;
+  const int gt = blockIdx.x >> 6;
+  const int group = gt / ntile, tile = gt - group * ntile;
+  int first, count;
+  if (p.mode == 0) { first = group * p.nsplit; count = p.nvalid; }
+  else det_plan::tn_group_ranges(p.row_off, group, p.R, first, count);
+  const int e4 = (((blockIdx.x & 63) << 8) + threadIdx.x) << 2;
+  float4 s = {0.f, 0.f, 0.f, 0.f};
+  for (int sp = 0; sp < count; ++sp) {
+    const float4 v = *(const float4*)(p.partial + ((long long)((first + sp) * ntile + tile) << 16) + e4);
+    s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+  }
+  const int lane = e4 & 63, r = (e4 >> 6) & 15, tk = (e4 >> 10) & 3, tn = (e4 >> 12) & 3, wid = e4 >> 14;
+  const int wm = wid & 1, wn = wid >> 1, h = lane >> 5, kcol = lane & 31;
+  const int tile_n = tile / p.tiles_k, tile_k = tile - tile_n * p.tiles_k;
+  const int n = tile_n * 256 + wm * 128 + tn * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+  const int k = tile_k * 256 + wn * 128 + tk * 32 + kcol;
+  if (count > 0 && n < p.Nn && k < p.Kk) {
+    float* d = p.dW + (long long)group * p.strideW + (long long)n * p.ldw + k;
+    if (p.vec) {
+      float4 o = *(float4*)d;
+      o.x += s.x; o.y += s.y; o.z += s.z; o.w += s.w;
+      *(float4*)d = o;
+    } else { d[0] += s.x; d[1] += s.y; d[2] += s.z; d[3] += s.w; }
+  }
+  if (p.db && tile_k == 0 && (blockIdx.x & 63) == 0 && count > 0) {
+    const int c = threadIdx.x;                    // column of the tile: wave half wm = c >> 7, then [tn][kcol]
+    const int nn = tile_n * 256 + c;
+    float a = 0.f;
+    for (int sp = 0; sp < count; ++sp) {
+      const float* q = p.db_partial + ((long long)((first + sp) * ntile + tile) << 9) + ((c >> 7) << 7) + (c & 127);
+      a += q[0];
+      a += q[256];
+    }
+    if (nn < p.Nn) p.db[(long long)group * p.strideDb + nn] += a;
+  }
+}
+
+static inline bool tn_vec_ok(const float* dW, int ldw, long long strideW) {
+  return ((unsigned long long)dW & 15) == 0 && (ldw % 4) == 0 && (strideW % 4) == 0;
+}
+
 // Plain wgrad dW[Nn, Kk] += G^T X (db += column sums of G) in the staged form when it applies - plain rows, Nn and Kk multiples of 256,
 // M % 32 == 0 and >= 4096, `scratch` holding tiles x row ranges partial tiles of 65536 floats - else exactly medmoe_gemm_tn(nsplit 16).
-// The caller owns `scratch` and must not share it between launches that may run concurrently (one per stream).
+// db leaves through the scratch as well (512 floats per partial tile behind the tiles, summed in range order) when the scratch has that
+// room; without it db keeps its atomics.  The caller owns `scratch` and must not share it between launches that may run concurrently
+// (one per stream).
 extern "C" int medmoe_gemm_tn_staged(const void* G, int ldg, const void* X, int ldx, float* dW, int ldw, float* db, int M, int Nn, int Kk,
                                      float* scratch, long long scratch_floats, hipStream_t stream) {
   if (!G || !X || !dW) return MM_ERR_ARG;
@@ -2785,10 +2838,19 @@ extern "C" int medmoe_gemm_tn_staged(const void* G, int ldg, const void* X, int 
     p.n_groups = 1;
     if (p.nsplit >= 2 && (long long)ntile * p.nsplit * 65536 <= scratch_floats) {
       p.partial = scratch;
-      const int chunk = (((M + 31) / 32 + p.nsplit - 1) / p.nsplit) * 32;
+      const int chunk = det_plan::tn_chunk(M, p.nsplit);
       const int nvalid = (M + chunk - 1) / chunk;
+      const long long slots = (long long)ntile * p.nsplit;
+      if (db && slots * (65536 + 512) <= scratch_floats) p.db_partial = scratch + slots * 65536;
+      if (db && !p.db_partial) ++g_mm_nondet;       // db still meets in atomics
       hipLaunchKernelGGL(gemm_tn4w_kernel<false>, dim3(ntile * p.nsplit), dim3(256), 0, stream, p);
-      hipLaunchKernelGGL(tn_reduce_kernel, dim3(ntile * 64), dim3(256), 0, stream, scratch, dW, ldw, ntile, p.tiles_k, nvalid);
+      if (p.db_partial) {
+        TnReduceArgs q{scratch, p.db_partial, dW, db, nullptr, 0, 0, ldw, Nn, Kk, p.tiles_n, p.tiles_k, 0, p.nsplit, nvalid, 1, 0, 1};
+        q.vec = tn_vec_ok(dW, ldw, 0);
+        hipLaunchKernelGGL(tn_reduce_det_kernel, dim3(ntile * 64), dim3(256), 0, stream, q);
+      } else {
+        hipLaunchKernelGGL(tn_reduce_kernel, dim3(ntile * 64), dim3(256), 0, stream, scratch, dW, ldw, ntile, p.tiles_k, nvalid);
+      }
       return mm_check_launch();
     }
   }
@@ -2800,9 +2862,9 @@ extern "C" int medmoe_gemm_tn_staged(const void* G, int ldg, const void* X, int 
 // this is the plain wgrad for operands whose M * ld exceeds 4 GB (the transposed local-loss matrices).
 // g_chunk_w > 0: G's Nn columns are stored in chunks of g_chunk_w columns (a multiple of 8), chunk j at G + j * g_chunk_stride (the
 // image-major pair matrices seen as ONE [M][B * HWp] operand: full 256-column tiles across images).
-extern "C" int medmoe_gemm_tn_cols(const void* G, int ldg, const void* X, int ldx, float* dW, int ldw, int M, int Nn, int Kk,
-                                   int n_groups, long long gcol_stride, long long xcol_stride, long long strideW, int g_chunk_w,
-                                   long long g_chunk_stride, hipStream_t stream) {
+static int tn_cols_impl(const void* G, int ldg, const void* X, int ldx, float* dW, int ldw, int M, int Nn, int Kk,
+                        int n_groups, long long gcol_stride, long long xcol_stride, long long strideW, int g_chunk_w,
+                        long long g_chunk_stride, bool det, float* scratch, long long scratch_floats, hipStream_t stream) {
   if (!G || !X || !dW) return MM_ERR_ARG;
   if (M < 32 || (M % 32) || Nn <= 0 || Kk <= 0 || (Nn % 8) || (Kk % 8) || (ldg % 8) || (ldx % 8) || n_groups < 1) return MM_ERR_SHAPE;
   if ((gcol_stride % 8) || (xcol_stride % 8) || gcol_stride < 0 || xcol_stride < 0) return MM_ERR_SHAPE;
@@ -2821,16 +2883,48 @@ extern "C" int medmoe_gemm_tn_cols(const void* G, int ldg, const void* X, int ld
   p.gscale = nullptr; p.partial = nullptr; p.gscale_gstride = 0; p.gscale_ld = 0;
   const long long ntile = (long long)p.tiles_n * p.tiles_k * n_groups;
   p.nsplit = (int)max(1ll, min(256ll / ntile, (long long)M / g_tn_min_rows));
+  if (det && p.nsplit > 1) {
+    // STAGED: every (group, range, tile) stores its partial tile, tn_reduce_det_kernel walks a group's ranges in order
+    if (!scratch || ntile * p.nsplit * 65536 > scratch_floats) return MM_ERR_ARG;
+    p.partial = scratch;
+    const int chunk = det_plan::tn_chunk(M, p.nsplit);
+    hipLaunchKernelGGL((gemm_tn4w_kernel<false, true>), dim3((unsigned)(ntile * p.nsplit)), dim3(256), 0, stream, p);
+    TnReduceArgs q{scratch, nullptr, dW, nullptr, nullptr, strideW, 0, ldw, Nn, Kk, p.tiles_n, p.tiles_k, 0, p.nsplit, (M + chunk - 1) / chunk,
+                   n_groups, 0, tn_vec_ok(dW, ldw, strideW) ? 1 : 0};
+    hipLaunchKernelGGL(tn_reduce_det_kernel, dim3((unsigned)(ntile * 64)), dim3(256), 0, stream, q);
+    return mm_check_launch();
+  }
+  if (p.nsplit > 1) ++g_mm_nondet;
   hipLaunchKernelGGL((gemm_tn4w_kernel<false, true>), dim3((unsigned)(ntile * p.nsplit)), dim3(256), 0, stream, p);
   return mm_check_launch();
+}
+
+extern "C" int medmoe_gemm_tn_cols(const void* G, int ldg, const void* X, int ldx, float* dW, int ldw, int M, int Nn, int Kk,
+                                   int n_groups, long long gcol_stride, long long xcol_stride, long long strideW, int g_chunk_w,
+                                   long long g_chunk_stride, hipStream_t stream) {
+  return tn_cols_impl(G, ldg, X, ldx, dW, ldw, M, Nn, Kk, n_groups, gcol_stride, xcol_stride, strideW, g_chunk_w, g_chunk_stride, false,
+                      nullptr, 0, stream);
+}
+
+// medmoe_gemm_tn_cols without order-dependent sums: with more than one row range per tile the partial tiles go through `scratch`
+// (medmoe_gemm_tn_cols_det_scratch floats; the caller's, one per stream) and are summed in range order.
+extern "C" int medmoe_gemm_tn_cols_det(const void* G, int ldg, const void* X, int ldx, float* dW, int ldw, int M, int Nn, int Kk,
+                                       int n_groups, long long gcol_stride, long long xcol_stride, long long strideW, int g_chunk_w,
+                                       long long g_chunk_stride, float* scratch, long long scratch_floats, hipStream_t stream) {
+  return tn_cols_impl(G, ldg, X, ldx, dW, ldw, M, Nn, Kk, n_groups, gcol_stride, xcol_stride, strideW, g_chunk_w, g_chunk_stride, true,
+                      scratch, scratch_floats, stream);
+}
+
+extern "C" long long medmoe_gemm_tn_cols_det_scratch(int M, int Nn, int Kk, int n_groups) {
+  return det_plan::cols_scratch_floats(M, Nn, Kk, n_groups, g_tn_min_rows);
 }
 
 // dW[g][Nn][Nn] += A_g^T diag(w_g) A_g: weighted Gram products of the column blocks A_g = A + g*col_stride of one [M][lda] bf16 matrix,
 // w_g[m] = w[g * w_gstride + m * w_ld] fp32 (every weight of rows 0..M-1 finite: it multiplies even all-zero rows).  The product
 // w * A is rounded to bf16 before it is multiplied, as a stored copy would be.  fp32 atomics: zero dW first.  M % 32 == 0, Nn % 8 == 0.
 // (The dGm of the GLoRIA local loss, sum over words of d2 a a^T per image, without the U = d2 * A matrix - losses.py:698-736 backward.)
-extern "C" int medmoe_gemm_tn_gram(const void* A, int lda, const float* w, long long w_gstride, int w_ld, float* dW, int ldw, int M,
-                                   int Nn, int n_groups, long long col_stride, long long strideW, hipStream_t stream) {
+static int tn_gram_impl(const void* A, int lda, const float* w, long long w_gstride, int w_ld, float* dW, int ldw, int M,
+                        int Nn, int n_groups, long long col_stride, long long strideW, bool det, hipStream_t stream) {
   if (!A || !w || !dW) return MM_ERR_ARG;
   if (M < 32 || (M % 32) || Nn <= 0 || (Nn % 8) || (lda % 8) || n_groups < 1 || Nn > lda || w_ld < 1 || w_gstride < 0) return MM_ERR_SHAPE;
   if ((col_stride % 8) || col_stride < 0 || 32ll * lda * 2 + 1024 >= (1ll << 32) || 64ll * w_ld * 4 >= (1ll << 32)) return MM_ERR_SHAPE;
@@ -2844,9 +2938,22 @@ extern "C" int medmoe_gemm_tn_gram(const void* A, int lda, const float* w, long 
   p.g_chunk_w = 0; p.g_chunk_stride = 0;
   p.gscale = w; p.gscale_gstride = w_gstride; p.gscale_ld = w_ld;
   const long long ntile = (long long)p.tiles_n * p.tiles_k * n_groups;
-  p.nsplit = (int)max(1ll, min(256ll / ntile, (long long)M / g_tn_min_rows));
+  p.nsplit = det ? 1 : (int)max(1ll, min(256ll / ntile, (long long)M / g_tn_min_rows));   // det: ONE workgroup adds to an output tile
+  if (p.nsplit > 1) ++g_mm_nondet;
   hipLaunchKernelGGL((gemm_tn4w_kernel<false, true, true>), dim3((unsigned)(ntile * p.nsplit)), dim3(256), 0, stream, p);
   return mm_check_launch();
+}
+
+extern "C" int medmoe_gemm_tn_gram(const void* A, int lda, const float* w, long long w_gstride, int w_ld, float* dW, int ldw, int M,
+                                   int Nn, int n_groups, long long col_stride, long long strideW, hipStream_t stream) {
+  return tn_gram_impl(A, lda, w, w_gstride, w_ld, dW, ldw, M, Nn, n_groups, col_stride, strideW, false, stream);
+}
+
+// medmoe_gemm_tn_gram with a single writer per output tile (no split over the rows): the atomics of a tile all come from one workgroup,
+// in program order.  The per-image Gram gradients are B groups of one tile: the groups fill the chip.
+extern "C" int medmoe_gemm_tn_gram_det(const void* A, int lda, const float* w, long long w_gstride, int w_ld, float* dW, int ldw, int M,
+                                       int Nn, int n_groups, long long col_stride, long long strideW, hipStream_t stream) {
+  return tn_gram_impl(A, lda, w, w_gstride, w_ld, dW, ldw, M, Nn, n_groups, col_stride, strideW, true, stream);
 }
 
 extern "C" int medmoe_gemm_tn(const void* G, int ldg, const void* X, int ldx, float* dW, int ldw,
@@ -2868,6 +2975,7 @@ extern "C" int medmoe_gemm_tn(const void* G, int ldg, const void* X, int ldx, fl
     const int ntile = p.tiles_n * p.tiles_k;
     p.nsplit = max(1, min(256 / ntile, M / g_tn_min_rows));   // ~256 workgroups, at least g_tn_min_rows / 32 sub-steps each
     p.n_groups = 1;
+    if (p.nsplit > 1) ++g_mm_nondet;
     if (g_use_tn4w) hipLaunchKernelGGL(gemm_tn4w_kernel<false>, dim3(ntile * p.nsplit), dim3(256), 0, stream, p);
     else hipLaunchKernelGGL(gemm_tn512_kernel<false>, dim3(ntile * p.nsplit), dim3(512), 0, stream, p);
     return mm_check_launch();
@@ -2879,6 +2987,7 @@ extern "C" int medmoe_gemm_tn(const void* G, int ldg, const void* X, int ldx, fl
     // groups are unequal (router imbalance): ranges of ~g_tn_rows rows, several waves of workgroups, so that a large
     // group's work spreads over the chip (3 ranges per group measured slower than 50)
     p.n_groups = n_groups;
+    ++g_mm_nondet;                                  // several row ranges add to one tile
     if (g_use_tn4w && row_off) {
       // equal ranges of R rows over all groups, enumerated on the device.  tools/tn_rows_sweep4w.py (768x768 tiles, 8 groups,
       // us per launch; balanced / 2-of-8 groups): M = 401408: R 1024 887 / 860, 2048 635 / 651, 4096 540 / 547, 8192 502 / 629,
@@ -2896,8 +3005,62 @@ extern "C" int medmoe_gemm_tn(const void* G, int ldg, const void* X, int ldx, fl
     return mm_check_launch();
   }
   p.tiles_n = (Nn + 127) / 128; p.tiles_k = (Kk + 127) / 128; p.nsplit = nsplit; p.n_groups = n_groups;
+  if (nsplit > 1) ++g_mm_nondet;                    // nsplit == 1: one workgroup per (group, tile), its atomics arrive in program order
   const int grid = p.tiles_n * p.tiles_k * nsplit * n_groups;
   if (x_rowmap || g_rowmap) hipLaunchKernelGGL(gemm_tn_kernel<true>, dim3(grid), dim3(256), 0, stream, p);
   else hipLaunchKernelGGL(gemm_tn_kernel<false>, dim3(grid), dim3(256), 0, stream, p);
   return mm_check_launch();
 }
+
+// medmoe_gemm_tn without order-dependent sums (deterministic mode).  Shapes of the four-wave kernel - plain or ONE row-mapped operand or
+// router groups (row_off), Kk % 256 == 0, Nn % 128 == 0 (plain: % 256), at least 2048 rows per group - run STAGED: every (range, tile)
+// stores its partial tile and its column sums of G into `scratch`, tn_reduce_det_kernel adds a tile's ranges in range order (the ranges
+// of a group are enumerated from row_off on the device by both kernels).  Every other shape runs gemm_tn_kernel with ONE workgroup per
+// (group, tile).  scratch: medmoe_gemm_tn_det_scratch floats, the caller's, never shared by launches that may overlap (one per stream);
+// too small is an error, not a fall-back.
+extern "C" int medmoe_gemm_tn_det(const void* G, int ldg, const void* X, int ldx, float* dW, int ldw, float* db, int M, int Nn, int Kk,
+                                  const int* x_rowmap, const int* g_rowmap, const int* row_off, int n_groups, long long strideW,
+                                  long long strideDb, float* scratch, long long scratch_floats, hipStream_t stream) {
+  if (!G || !X || !dW) return MM_ERR_ARG;
+  if (M <= 0 || Nn <= 0 || Kk <= 0 || (Nn % 8) || (Kk % 8) || (ldg % 8) || (ldx % 8)) return MM_ERR_SHAPE;
+  if (n_groups < 1 || (n_groups > 1 && !row_off)) return MM_ERR_ARG;
+  GemmTNArgs p;
+  p.G = (const bf16_t*)G; p.X = (const bf16_t*)X; p.dW = dW; p.db = db;
+  p.x_rowmap = x_rowmap; p.g_rowmap = g_rowmap; p.row_off = row_off; p.strideW = strideW; p.strideDb = strideDb;
+  p.M = M; p.Nn = Nn; p.Kk = Kk; p.ldg = ldg; p.ldx = ldx; p.ldw = ldw; p.gcol_stride = 0; p.xcol_stride = 0; p.g_chunk_w = 0; p.g_chunk_stride = 0;
+  p.gscale = nullptr; p.partial = nullptr; p.gscale_gstride = 0; p.gscale_ld = 0; p.n_groups = n_groups;
+  const bool fit32 = (long long)M * ldg * 2 < (1ll << 32) && (long long)M * ldx * 2 < (1ll << 32);
+  const det_plan::TnPlan pl = det_plan::tn_plan(M, Nn, Kk, x_rowmap != nullptr, g_rowmap != nullptr, row_off != nullptr, n_groups, fit32,
+                                               g_tn_min_rows, g_tn_rows4w);
+  if (pl.kind == det_plan::TN_SMALL) {
+    p.tiles_n = (Nn + 127) / 128; p.tiles_k = (Kk + 127) / 128; p.nsplit = 1;
+    const int grid = p.tiles_n * p.tiles_k * n_groups;
+    if (x_rowmap || g_rowmap) hipLaunchKernelGGL(gemm_tn_kernel<true>, dim3(grid), dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL(gemm_tn_kernel<false>, dim3(grid), dim3(256), 0, stream, p);
+    return mm_check_launch();
+  }
+  if (!scratch || pl.scratch_floats > scratch_floats) return MM_ERR_ARG;
+  p.tiles_n = pl.tiles_n; p.tiles_k = pl.tiles_k; p.nsplit = pl.nsplit;
+  const int ntile = pl.tiles_n * pl.tiles_k;
+  p.partial = scratch;
+  if (db) p.db_partial = scratch + (long long)pl.slots * 65536;
+  TnReduceArgs q{scratch, p.db_partial, dW, db, row_off, strideW, strideDb, ldw, Nn, Kk, pl.tiles_n, pl.tiles_k, 0, pl.nsplit, pl.nvalid,
+                 n_groups, 0, tn_vec_ok(dW, ldw, strideW) ? 1 : 0};
+  if (pl.kind == det_plan::TN_PLAIN) hipLaunchKernelGGL(gemm_tn4w_kernel<false>, dim3(pl.slots), dim3(256), 0, stream, p);
+  else {
+    if (pl.kind == det_plan::TN_GROUPS) { q.mode = 1; q.R = pl.nsplit; }     // nsplit: the ROWS per range in this form
+    hipLaunchKernelGGL(gemm_tn4w_kernel<true>, dim3(pl.slots), dim3(256), 0, stream, p);
+  }
+  hipLaunchKernelGGL(tn_reduce_det_kernel, dim3((unsigned)(n_groups * ntile * 64)), dim3(256), 0, stream, q);
+  return mm_check_launch();
+}
+
+extern "C" long long medmoe_gemm_tn_det_scratch(int M, int Nn, int Kk, int x_mapped, int g_mapped, int grouped, int n_groups) {
+  return det_plan::tn_plan(M, Nn, Kk, x_mapped != 0, g_mapped != 0, grouped != 0, n_groups, true, g_tn_min_rows, g_tn_rows4w).scratch_floats;
+}
+
+// launches so far that took an order-dependent form (an atomic epilogue with more than one writer per element, an atomic loss sum):
+// a host-side count, one add per such launch in the extern "C" dispatch functions of gemm / moe / norm / loss / optim / embed.hip -
+// deterministic mode must leave it where it is.  Library-internal (hidden); the ABI is medmoe_nondet_launches().
+__attribute__((visibility("hidden"))) long long g_mm_nondet = 0;
+extern "C" long long medmoe_nondet_launches() { return g_mm_nondet; }

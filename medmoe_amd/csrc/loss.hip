@@ -14,7 +14,7 @@
 __global__ __launch_bounds__(256) void ce_strided_kernel(const float* __restrict__ X, float* __restrict__ dX, int rows,
                                                          int cols, long long rs, long long cs, int label_off,
                                                          float xscale, float w, int accumulate,
-                                                         float* __restrict__ loss_acc) {
+                                                         float* __restrict__ loss_acc, float* __restrict__ parts = nullptr) {
   __shared__ float red[4];
   __shared__ float bc;
   const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -37,7 +37,9 @@ __global__ __launch_bounds__(256) void ce_strided_kernel(const float* __restrict
   __syncthreads();
   s = bc;
   const int lab = label_off + r;
-  if (tid == 0 && loss_acc) atomicAdd(loss_acc, w * (m + __logf(s) - x[(long long)lab * cs] * xscale));
+  // parts (deterministic mode): the row's term is STORED at parts[r]; det_sum_kernel adds the rows in order
+  if (tid == 0 && parts) parts[r] = w * (m + __logf(s) - x[(long long)lab * cs] * xscale);
+  else if (tid == 0 && loss_acc) atomicAdd(loss_acc, w * (m + __logf(s) - x[(long long)lab * cs] * xscale));
   if (dX) {
     float* d = dX + (long long)r * rs;
     for (int c = tid; c < cols; c += 256) {
@@ -52,8 +54,42 @@ extern "C" int medmoe_ce_strided(const float* X, float* dX, int rows, int cols, 
                                  hipStream_t stream) {
   if (!X) return MM_ERR_ARG;
   if (rows <= 0 || cols <= 0 || label_off < 0 || label_off + rows > cols) return MM_ERR_SHAPE;
+  if (loss_acc && rows > 1) ++g_mm_nondet;
   hipLaunchKernelGGL(ce_strided_kernel, dim3(rows), dim3(256), 0, stream, X, dX, rows, cols, rs, cs, label_off, xscale,
                      w, accumulate, loss_acc);
+  return mm_check_launch();
+}
+
+// out[seg] += the n floats of segment seg, in a FIXED order: thread t takes elements t, t + 256, ..., the 256 sums meet in a tree of fixed
+// shape.  One workgroup per segment (the loss heads' per-row terms: a few hundred values).
+__global__ __launch_bounds__(256) void det_sum_kernel(const float* __restrict__ parts, int n, float* __restrict__ out) {
+  __shared__ float red[256];
+  const float* q = parts + (long long)blockIdx.x * n;
+  float a = 0.f;
+  for (int i = threadIdx.x; i < n; i += 256) a += q[i];
+  red[threadIdx.x] = a;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[blockIdx.x] += red[0];
+}
+
+void mm_launch_det_sum(const float* parts, int n, int nseg, float* out, hipStream_t stream) {
+  hipLaunchKernelGGL(det_sum_kernel, dim3(nseg), dim3(256), 0, stream, parts, n, out);
+}
+
+// The three heads with the loss summed in row order (deterministic mode): parts = `rows` floats of the caller's; the gradient part is the
+// same launch as the atomic form's.
+extern "C" int medmoe_ce_strided_det(const float* X, float* dX, int rows, int cols, long long rs, long long cs,
+                                     int label_off, float xscale, float w, int accumulate, float* loss_acc, float* parts,
+                                     hipStream_t stream) {
+  if (!X || !loss_acc || !parts) return MM_ERR_ARG;
+  if (rows <= 0 || cols <= 0 || label_off < 0 || label_off + rows > cols) return MM_ERR_SHAPE;
+  hipLaunchKernelGGL(ce_strided_kernel, dim3(rows), dim3(256), 0, stream, X, dX, rows, cols, rs, cs, label_off, xscale,
+                     w, accumulate, loss_acc, parts);
+  mm_launch_det_sum(parts, rows, 1, loss_acc, stream);
   return mm_check_launch();
 }
 
@@ -78,7 +114,8 @@ __device__ __forceinline__ float block256_sum(float v, float* red, float* bc) {
 __global__ __launch_bounds__(256) void soft_xent_strided_kernel(const float* __restrict__ X, float* __restrict__ dX,
                                                                 const float* __restrict__ soft, int rows, int cols, long long rs,
                                                                 long long cs, float xscale, float t1, float t2, float w,
-                                                                int accumulate, float* __restrict__ loss_acc) {
+                                                                int accumulate, float* __restrict__ loss_acc,
+                                                                float* __restrict__ parts = nullptr) {
   __shared__ float red[4];
   __shared__ float bc;
   const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -102,6 +139,7 @@ __global__ __launch_bounds__(256) void soft_xent_strided_kernel(const float* __r
   nn = block256_sum(nn, red, &bc);
   float* d = dX ? dX + (long long)r * rs : nullptr;
   if (np == 0.f) {                                      // uniform over the block
+    if (tid == 0 && parts) parts[r] = 0.f;
     if (d && !accumulate) for (int c = tid; c < cols; c += 256) d[(long long)c * cs] = 0.f;
     return;
   }
@@ -117,7 +155,8 @@ __global__ __launch_bounds__(256) void soft_xent_strided_kernel(const float* __r
   l = block256_sum(l, red, &bc);
   wsum = block256_sum(wsum, red, &bc);
   const float cw = w / (np * (1.f + nn));
-  if (tid == 0 && loss_acc) atomicAdd(loss_acc, cw * l);
+  if (tid == 0 && parts) parts[r] = cw * l;
+  else if (tid == 0 && loss_acc) atomicAdd(loss_acc, cw * l);
   if (d) {
     for (int c = tid; c < cols; c += 256) {
       const float s = sf[c], e = __expf(x[(long long)c * cs] * xscale - m);
@@ -135,8 +174,20 @@ extern "C" int medmoe_soft_xent_strided(const float* X, float* dX, const float* 
                                         hipStream_t stream) {
   if (!X || !soft) return MM_ERR_ARG;
   if (rows <= 0 || cols <= 0) return MM_ERR_SHAPE;
+  if (loss_acc && rows > 1) ++g_mm_nondet;
   hipLaunchKernelGGL(soft_xent_strided_kernel, dim3(rows), dim3(256), 0, stream, X, dX, soft, rows, cols, rs, cs, xscale, t1, t2, w,
                      accumulate, loss_acc);
+  return mm_check_launch();
+}
+
+extern "C" int medmoe_soft_xent_strided_det(const float* X, float* dX, const float* soft, int rows, int cols, long long rs, long long cs,
+                                            float xscale, float t1, float t2, float w, int accumulate, float* loss_acc, float* parts,
+                                            hipStream_t stream) {
+  if (!X || !soft || !loss_acc || !parts) return MM_ERR_ARG;
+  if (rows <= 0 || cols <= 0) return MM_ERR_SHAPE;
+  hipLaunchKernelGGL(soft_xent_strided_kernel, dim3(rows), dim3(256), 0, stream, X, dX, soft, rows, cols, rs, cs, xscale, t1, t2, w,
+                     accumulate, loss_acc, parts);
+  mm_launch_det_sum(parts, rows, 1, loss_acc, stream);
   return mm_check_launch();
 }
 
@@ -148,7 +199,7 @@ extern "C" int medmoe_soft_xent_strided(const float* X, float* dX, const float* 
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void hardneg_strided_kernel(const float* __restrict__ X, float* __restrict__ dX, int rows, int cols,
                                                               long long rs, long long cs, float margin, float w, int accumulate,
-                                                              float* __restrict__ loss_acc) {
+                                                              float* __restrict__ loss_acc, float* __restrict__ parts = nullptr) {
   __shared__ float redv[4];
   __shared__ int redi[4];
   __shared__ float bv;
@@ -179,7 +230,8 @@ __global__ __launch_bounds__(256) void hardneg_strided_kernel(const float* __res
   m = bv; mi = bi;
   const float l = m + margin - diag;
   const bool on = l > 0.f;
-  if (tid == 0 && loss_acc && on) atomicAdd(loss_acc, w * l);
+  if (tid == 0 && parts) parts[r] = on ? w * l : 0.f;
+  else if (tid == 0 && loss_acc && on) atomicAdd(loss_acc, w * l);
   if (dX) {
     float* d = dX + (long long)r * rs;
     for (int c = tid; c < cols; c += 256) {
@@ -197,7 +249,18 @@ extern "C" int medmoe_hardneg_strided(const float* X, float* dX, int rows, int c
                                       int accumulate, float* loss_acc, hipStream_t stream) {
   if (!X) return MM_ERR_ARG;
   if (rows <= 0 || cols <= 0 || rows > cols) return MM_ERR_SHAPE;
+  if (loss_acc && rows > 1) ++g_mm_nondet;
   hipLaunchKernelGGL(hardneg_strided_kernel, dim3(rows), dim3(256), 0, stream, X, dX, rows, cols, rs, cs, margin, w, accumulate, loss_acc);
+  return mm_check_launch();
+}
+
+extern "C" int medmoe_hardneg_strided_det(const float* X, float* dX, int rows, int cols, long long rs, long long cs, float margin, float w,
+                                          int accumulate, float* loss_acc, float* parts, hipStream_t stream) {
+  if (!X || !loss_acc || !parts) return MM_ERR_ARG;
+  if (rows <= 0 || cols <= 0 || rows > cols) return MM_ERR_SHAPE;
+  hipLaunchKernelGGL(hardneg_strided_kernel, dim3(rows), dim3(256), 0, stream, X, dX, rows, cols, rs, cs, margin, w, accumulate, loss_acc,
+                     parts);
+  mm_launch_det_sum(parts, rows, 1, loss_acc, stream);
   return mm_check_launch();
 }
 
@@ -262,7 +325,32 @@ __global__ __launch_bounds__(256) void cos_scale_bwd_kernel(float* __restrict__ 
 extern "C" int medmoe_cos_scale_bwd(float* dC, const float* C, const float* na, const float* nb, float* ca, float* cb,
                                     int M, int N, float eps, hipStream_t stream) {
   if (!dC || !C || !na || !nb || !ca || M <= 0 || N <= 0) return MM_ERR_ARG;
+  if (cb && M > 1) ++g_mm_nondet;
   hipLaunchKernelGGL(cos_scale_bwd_kernel, dim3(M), dim3(256), 0, stream, dC, C, na, nb, ca, cb, M, N, eps);
+  return mm_check_launch();
+}
+
+// cb[j] += -sum_i dC*cos / nb[j]^2 with ONE thread per column walking the rows in order (single writer); runs BEFORE cos_scale_bwd_kernel
+// rewrites dC
+__global__ __launch_bounds__(256) void cos_scale_cb_kernel(const float* __restrict__ dC, const float* __restrict__ C,
+                                                           const float* __restrict__ na, const float* __restrict__ nb,
+                                                           float* __restrict__ cb, int M, int N, float eps) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= N) return;
+  const float bj = nb[j];
+  float a = 0.f;
+  for (int i = 0; i < M; ++i) {
+    const long long o = (long long)i * N + j;
+    if (na[i] * bj >= eps) a += dC[o] * C[o];
+  }
+  cb[j] += -a / (bj * bj);
+}
+
+extern "C" int medmoe_cos_scale_bwd_det(float* dC, const float* C, const float* na, const float* nb, float* ca, float* cb,
+                                        int M, int N, float eps, hipStream_t stream) {
+  if (!dC || !C || !na || !nb || !ca || M <= 0 || N <= 0) return MM_ERR_ARG;
+  if (cb) hipLaunchKernelGGL(cos_scale_cb_kernel, dim3((N + 255) / 256), dim3(256), 0, stream, dC, C, na, nb, cb, M, N, eps);
+  hipLaunchKernelGGL(cos_scale_bwd_kernel, dim3(M), dim3(256), 0, stream, dC, C, na, nb, ca, (float*)nullptr, M, N, eps);
   return mm_check_launch();
 }
 

@@ -141,7 +141,7 @@ __global__ __launch_bounds__(128) void router_bwd_kernel(const float* __restrict
                                                          const float* __restrict__ dprobs_ext, float ce_scale,
                                                          float* __restrict__ dlogits,
                                                          float* __restrict__ dh, float* __restrict__ loss_acc,
-                                                         int B, int Hd, int E, int k) {
+                                                         int B, int Hd, int E, int k, float* __restrict__ parts = nullptr) {
   __shared__ float sdl[ROUTER_MAX_E];
   const int b = blockIdx.x, j = threadIdx.x;
   if (j == 0) {
@@ -154,12 +154,14 @@ __global__ __launch_bounds__(128) void router_bwd_kernel(const float* __restrict
     const int lab = labels ? labels[b] : -1;
     int am = 0;
     for (int e = 1; e < E; ++e) if (p[e] > p[am]) am = e;
+    float ce = 0.f;
     for (int e = 0; e < E; ++e) {
       const float q = dp[e] / s;
-      if (e == lab) atomicAdd(loss_acc, -__logf(q) / (float)B);
+      if (e == lab) { if (parts) ce = -__logf(q) / (float)B; else atomicAdd(loss_acc, -__logf(q) / (float)B); }
       dp[e] = labels ? ce_scale * (q - (e == lab ? 1.f : 0.f)) : 0.f;
     }
-    if (labels && am == lab) atomicAdd(loss_acc + 1, 1.f / (float)B);
+    if (parts) { parts[b] = ce; parts[B + b] = (labels && am == lab) ? 1.f / (float)B : 0.f; }      // summed in sample order by det_sum_kernel
+    else if (labels && am == lab) atomicAdd(loss_acc + 1, 1.f / (float)B);
     if (dprobs_ext)                      // gradient arriving from outside (autograd path of src/ mirror)
       for (int e = 0; e < E; ++e) dp[e] += dprobs_ext[(long long)b * E + e];
     if (dgates && k > 1) {
@@ -187,8 +189,22 @@ extern "C" int medmoe_router_bwd(const float* probs, const float* h, const float
                                  hipStream_t stream) {
   if (!probs || !h || !w2 || !idx || !dlogits || !dh || !loss_acc) return MM_ERR_ARG;
   if (B <= 0 || Hd <= 0 || E <= 0 || E > ROUTER_MAX_E || k < 1 || k > 8) return MM_ERR_SHAPE;
+  if (labels && B > 1) ++g_mm_nondet;
   hipLaunchKernelGGL(router_bwd_kernel, dim3(B), dim3(128), 0, stream, probs, h, w2, idx, dgates, labels, dprobs_ext,
                      ce_scale, dlogits, dh, loss_acc, B, Hd, E, k);
+  return mm_check_launch();
+}
+
+// medmoe_router_bwd with the cross-entropy and the accuracy summed in sample order: parts = 2 * B floats of the caller's
+extern "C" int medmoe_router_bwd_det(const float* probs, const float* h, const float* w2, const int* idx,
+                                     const float* dgates, const int* labels, const float* dprobs_ext, float ce_scale,
+                                     float* dlogits, float* dh, float* loss_acc, int B, int Hd, int E, int k, float* parts,
+                                     hipStream_t stream) {
+  if (!probs || !h || !w2 || !idx || !dlogits || !dh || !loss_acc || !parts) return MM_ERR_ARG;
+  if (B <= 0 || Hd <= 0 || E <= 0 || E > ROUTER_MAX_E || k < 1 || k > 8) return MM_ERR_SHAPE;
+  hipLaunchKernelGGL(router_bwd_kernel, dim3(B), dim3(128), 0, stream, probs, h, w2, idx, dgates, labels, dprobs_ext,
+                     ce_scale, dlogits, dh, loss_acc, B, Hd, E, k, parts);
+  mm_launch_det_sum(parts, B, 2, loss_acc, stream);
   return mm_check_launch();
 }
 
@@ -490,7 +506,10 @@ extern "C" int medmoe_combine_fwd(const void* expert_out, const int* slot_of, co
 // ---------------------------------------------------------------------------------------------
 constexpr int SA_WAVES = 16;          // waves per workgroup of scale_attn_bwd_kernel
 int g_sa_rows = 0;                    // medmoe_set_option(13, rows per wave): measurement only, 0 = the built-in rule
-template <int DCH, int HCH>
+// DET build (deterministic mode): a wave's rows lie inside ONE slot (wave = slot * wps + chunk of rows_per_wave rows), so it meets one expert
+// and one gate; its sums leave as a record rec[wave][Dh + 8] = [dw2 partial (Dh) | db2 | dgate | pad] with plain stores, and
+// scale_attn_bwd_reduce_kernel adds an expert's (a slot's) records in wave order.  No atomics, no LDS.
+template <int DCH, int HCH, bool DET = false>
 __global__ __launch_bounds__(SA_WAVES * 64) void scale_attn_bwd_kernel(const bf16_t* __restrict__ d_img_l, const float* __restrict__ d_img_g,
                                                              const bf16_t* __restrict__ G, const bf16_t* __restrict__ H1,
                                                              const float* __restrict__ wts, const float* __restrict__ w2,
@@ -499,10 +518,17 @@ __global__ __launch_bounds__(SA_WAVES * 64) void scale_attn_bwd_kernel(const bf1
                                                              const int* __restrict__ item_of_slot, const float* __restrict__ gates,
                                                              int k, int P, bf16_t* __restrict__ dG, bf16_t* __restrict__ dH1,
                                                              float* __restrict__ dw2, float* __restrict__ db2,
-                                                             float* __restrict__ dgate, int R, int Do, int Dh, int rows_per_wave) {
+                                                             float* __restrict__ dgate, int R, int Do, int Dh, int rows_per_wave,
+                                                             float* __restrict__ rec = nullptr, int wps = 1) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int wave = blockIdx.x * SA_WAVES + wid;
-  const int r_begin = wave * rows_per_wave, r_end = min(R, r_begin + rows_per_wave);
+  int r_begin = wave * rows_per_wave, r_end = min(R, r_begin + rows_per_wave);
+  float dgs = 0.f;
+  if constexpr (DET) {
+    const int slot = wave / wps, p0 = (wave - slot * wps) * rows_per_wave;
+    if (slot >= R / P) return;
+    r_begin = slot * P + p0; r_end = slot * P + min(P, p0 + rows_per_wave);
+  }
   float aw2[HCH][8];
 #pragma unroll
   for (int i = 0; i < HCH; ++i)
@@ -574,7 +600,10 @@ __global__ __launch_bounds__(SA_WAVES * 64) void scale_attn_bwd_kernel(const bf1
     for (int s = 0; s < SA_S; ++s) { dws[s] = wave_sum(dws[s]); w[s] = wts[(long long)r * SA_S + s]; wd += w[s] * dws[s]; }
 #pragma unroll
     for (int s = 0; s < SA_S; ++s) { da[s] = w[s] * (dws[s] - wd); ab2 += da[s]; }
-    if (dgate) { dg = wave_sum(dg); if (lane == 0) atomicAdd(dgate + item, dg); }
+    if (dgate) {
+      dg = wave_sum(dg);
+      if constexpr (DET) dgs += dg; else if (lane == 0) atomicAdd(dgate + item, dg);
+    }
 #pragma unroll
     for (int i = 0; i < DCH; ++i) {
       const int c = lane + i * 64;
@@ -613,6 +642,19 @@ __global__ __launch_bounds__(SA_WAVES * 64) void scale_attn_bwd_kernel(const bf1
   // addresses at batch 128 (serialised at the memory side: a third of the kernel).  The waves of a workgroup own consecutive row ranges,
   // almost always of one expert: sum them in LDS first, one atomic per element and workgroup; mixed workgroups (an expert boundary
   // inside) fall back to per-wave atomics.
+  if constexpr (DET) {
+    float* o = rec + (long long)wave * (Dh + 8);
+#pragma unroll
+    for (int i = 0; i < HCH; ++i) {
+      const int c = lane + i * 64;
+      if (c * 8 < Dh) {
+        *(float4*)(o + c * 8) = make_float4(aw2[i][0], aw2[i][1], aw2[i][2], aw2[i][3]);
+        *(float4*)(o + c * 8 + 4) = make_float4(aw2[i][4], aw2[i][5], aw2[i][6], aw2[i][7]);
+      }
+    }
+    if (lane == 0) *(float4*)(o + Dh) = make_float4(ab2, dgs, 0.f, 0.f);
+    return;
+  }
   __shared__ float red[SA_WAVES][HCH * 512 + 1];
   __shared__ int red_e[SA_WAVES];
   if (lane == 0) { red_e[wid] = cur_e; red[wid][HCH * 512] = ab2; }
@@ -639,11 +681,40 @@ __global__ __launch_bounds__(SA_WAVES * 64) void scale_attn_bwd_kernel(const bf1
   }
 }
 
-extern "C" int medmoe_scale_attn_bwd(const void* d_img_l, const float* d_img_g, const void* G, const void* H1,
-                                     const float* wts, const float* w2, const void* expert_out,
-                                     const int* expert_of_slot, const int* item_of_slot, const float* gates, int k,
-                                     int P, void* dG, void* dH1, float* dw2, float* db2, float* dgate, int R, int Do,
-                                     int Dh, hipStream_t stream) {
+// blockIdx.x < E: dw2[e] / db2[e] += the records of expert e's waves (its slots are row_off[e] / P .. row_off[e + 1] / P), in wave order;
+// blockIdx.x >= E (dgate != null): dgate[item of slot] += the slot's wps dgate partials in wave order, a thread per slot.
+__global__ __launch_bounds__(1024) void scale_attn_bwd_reduce_kernel(const float* __restrict__ rec, const int* __restrict__ row_off,
+                                                                     const int* __restrict__ item_of_slot, float* __restrict__ dw2,
+                                                                     float* __restrict__ db2, float* __restrict__ dgate, int E, int P,
+                                                                     int Dh, int wps, int nslots) {
+  __shared__ float4 red[16][64];
+  const int RL = Dh + 8;
+  if ((int)blockIdx.x >= E) {
+    if (blockIdx.y) return;
+    const int slot = ((int)blockIdx.x - E) * 1024 + threadIdx.y * 64 + threadIdx.x;
+    if (slot >= nslots) return;
+    float a = 0.f;
+    for (int w = 0; w < wps; ++w) a += rec[(long long)(slot * wps + w) * RL + Dh + 1];
+    dgate[item_of_slot[slot]] += a;
+    return;
+  }
+  const int e = blockIdx.x;
+  const int s0 = row_off[e] / P, s1 = row_off[e + 1] / P;
+  const int c4 = blockIdx.y * 64 + threadIdx.x;
+  const bool on = c4 * 4 <= Dh;                        // the float4 at Dh carries db2
+  const float4 t = det_sum_records(rec + (long long)s0 * wps * RL, RL, (s1 - s0) * wps, c4, on, red);
+  if (threadIdx.y == 0 && on && s1 > s0) {
+    const int c = c4 * 4;
+    if (c < Dh) { float* d = dw2 + (long long)e * Dh + c; d[0] += t.x; d[1] += t.y; d[2] += t.z; d[3] += t.w; }
+    else db2[e] += t.x;
+  }
+}
+
+static int scale_attn_bwd_impl(const void* d_img_l, const float* d_img_g, const void* G, const void* H1,
+                               const float* wts, const float* w2, const void* expert_out,
+                               const int* expert_of_slot, const int* item_of_slot, const float* gates, int k,
+                               int P, void* dG, void* dH1, float* dw2, float* db2, float* dgate, int R, int Do,
+                               int Dh, const int* row_off, int E, float* scratch, long long scratch_floats, hipStream_t stream) {
   if (!G || !H1 || !wts || !w2 || !expert_of_slot || !item_of_slot || !gates || !dG || !dH1 || !dw2 || !db2) return MM_ERR_ARG;
   if (!d_img_l && !d_img_g) return MM_ERR_ARG;
   if (dgate && !expert_out) return MM_ERR_ARG;
@@ -653,11 +724,51 @@ extern "C" int medmoe_scale_attn_bwd(const void* d_img_l, const float* d_img_g, 
   // (before the workgroup-level reduction of the final flush: 16 rows 4.55 ms, 64 2.89, 96 2.86 at R = 401408)
   // with it (tools/bench_scale_attn_bwd.py): R = 50176: 4 rows 342 us, 16 363, 32 584, 96 1423 (757 before); R = 401408: 4 rows 2207 us, 8 2236, 32 2530, 96 3405 (2721 before)
   const int rows_per_wave = g_sa_rows > 0 ? g_sa_rows : max(4, min(8, (R + 49999) / 50000));
+  if (row_off) {                                         // deterministic form
+    if (E < 1) return MM_ERR_ARG;
+    const int rpw = min(rows_per_wave, P), wps = (P + rpw - 1) / rpw, nslots = R / P;
+    const long long waves = (long long)nslots * wps;
+    if (!scratch || waves * (Dh + 8) > scratch_floats) return MM_ERR_ARG;
+    hipLaunchKernelGGL((scale_attn_bwd_kernel<2, 1, true>), dim3((unsigned)((waves + SA_WAVES - 1) / SA_WAVES)), dim3(SA_WAVES * 64), 0, stream,
+                       (const bf16_t*)d_img_l, d_img_g, (const bf16_t*)G, (const bf16_t*)H1, wts, w2, (const bf16_t*)expert_out, expert_of_slot,
+                       item_of_slot, gates, k, P, (bf16_t*)dG, (bf16_t*)dH1, dw2, db2, dgate, R, Do, Dh, rpw, scratch, wps);
+    hipLaunchKernelGGL(scale_attn_bwd_reduce_kernel, dim3(E + (dgate ? (nslots + 1023) / 1024 : 0), (Dh / 4 + 1 + 63) / 64), dim3(64, 16), 0, stream,
+                       scratch, row_off, item_of_slot, dw2, db2, dgate, E, P, Dh, wps, nslots);
+    return mm_check_launch();
+  }
+  ++g_mm_nondet;
   const int waves = (R + rows_per_wave - 1) / rows_per_wave;
   hipLaunchKernelGGL((scale_attn_bwd_kernel<2, 1>), dim3((waves + SA_WAVES - 1) / SA_WAVES), dim3(SA_WAVES * 64), 0, stream, (const bf16_t*)d_img_l,
                      d_img_g, (const bf16_t*)G, (const bf16_t*)H1, wts, w2, (const bf16_t*)expert_out, expert_of_slot,
                      item_of_slot, gates, k, P, (bf16_t*)dG, (bf16_t*)dH1, dw2, db2, dgate, R, Do, Dh, rows_per_wave);
   return mm_check_launch();
+}
+
+extern "C" int medmoe_scale_attn_bwd(const void* d_img_l, const float* d_img_g, const void* G, const void* H1,
+                                     const float* wts, const float* w2, const void* expert_out,
+                                     const int* expert_of_slot, const int* item_of_slot, const float* gates, int k,
+                                     int P, void* dG, void* dH1, float* dw2, float* db2, float* dgate, int R, int Do,
+                                     int Dh, hipStream_t stream) {
+  return scale_attn_bwd_impl(d_img_l, d_img_g, G, H1, wts, w2, expert_out, expert_of_slot, item_of_slot, gates, k, P, dG, dH1, dw2, db2, dgate,
+                             R, Do, Dh, nullptr, 0, nullptr, 0, stream);
+}
+
+// medmoe_scale_attn_bwd without atomics (deterministic mode): row_off [E + 1] = the dispatch's first slot row of every expert (slots are
+// sorted by expert), scratch: at least medmoe_scale_attn_bwd_det_scratch(R, P, Dh) floats of the caller's.
+extern "C" int medmoe_scale_attn_bwd_det(const void* d_img_l, const float* d_img_g, const void* G, const void* H1,
+                                         const float* wts, const float* w2, const void* expert_out,
+                                         const int* expert_of_slot, const int* item_of_slot, const float* gates, int k,
+                                         int P, void* dG, void* dH1, float* dw2, float* db2, float* dgate, int R, int Do,
+                                         int Dh, const int* row_off, int E, float* scratch, long long scratch_floats, hipStream_t stream) {
+  if (!row_off) return MM_ERR_ARG;
+  return scale_attn_bwd_impl(d_img_l, d_img_g, G, H1, wts, w2, expert_out, expert_of_slot, item_of_slot, gates, k, P, dG, dH1, dw2, db2, dgate,
+                             R, Do, Dh, row_off, E, scratch, scratch_floats, stream);
+}
+
+extern "C" long long medmoe_scale_attn_bwd_det_scratch(int R, int P, int Dh) {
+  if (R <= 0 || P <= 0) return 0;
+  const int rpw = 4 < P ? 4 : P;                       // the fewest rows a wave takes: the most records
+  return (long long)(R / P) * ((P + rpw - 1) / rpw) * (Dh + 8);
 }
 
 // dx[b,1+p,:] += sum_j dF[slot_of[b,j]*P + p, :]      (stage-feature gradient into the residual stream)

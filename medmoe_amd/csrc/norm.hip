@@ -126,7 +126,7 @@ __global__ __launch_bounds__(LNB_WAVES * 64) void layernorm_bwd_kernel(const bf1
                                                             const float* __restrict__ mean, const float* __restrict__ rstd,
                                                             const float* __restrict__ gamma, const bf16_t* __restrict__ add,
                                                             bf16_t* __restrict__ dx, float* __restrict__ dgamma,
-                                                            float* __restrict__ dbeta, int rows, int D) {
+                                                            float* __restrict__ dbeta, int rows, int D, float* __restrict__ part) {
   static_assert(LPR == 64 || NCH == 1, "several rows per wave only for rows of one chunk slot");
   constexpr int RPW = 64 / LPR;
   __shared__ float red[2][LNB_WAVES][512];   // [dgamma|dbeta][wave][lane*8+e] for one chunk slot at a time
@@ -218,15 +218,30 @@ __global__ __launch_bounds__(LNB_WAVES * 64) void layernorm_bwd_kernel(const bf1
         float v = 0.f;
 #pragma unroll
         for (int w = 0; w < LNB_WAVES; ++w) v += red[which][w][j];
-        atomicAdd((which ? dbeta : dgamma) + col, v);
+        if (part) part[((long long)blockIdx.x * 2 + which) * D + col] = v;      // deterministic mode: [workgroup][dgamma | dbeta][D], summed in workgroup order
+        else atomicAdd((which ? dbeta : dgamma) + col, v);
       }
     }
   }
 }
 
-extern "C" int medmoe_layernorm_bwd(const void* dy, const void* x, const float* mean, const float* rstd,
-                                    const float* gamma, const void* add, void* dx, float* dgamma,
-                                    float* dbeta, int rows, int D, hipStream_t stream) {
+// dgamma / dbeta += the workgroups' partial rows [blocks][2][D], in workgroup order (deterministic mode)
+__global__ __launch_bounds__(1024) void layernorm_bwd_reduce_kernel(const float* __restrict__ part, int blocks, int D, float* __restrict__ dgamma,
+                                                                    float* __restrict__ dbeta) {
+  __shared__ float4 red[16][64];
+  const int c4 = blockIdx.x * 64 + threadIdx.x;       // float4 column group of the [2 * D] record
+  const bool on = c4 * 4 < 2 * D;
+  const float4 t = det_sum_records(part, 2ll * D, blocks, c4, on, red);
+  if (threadIdx.y == 0 && on) {
+    const int c = c4 * 4;                               // D % 8 == 0: a float4 lies inside one half
+    float* d = c < D ? dgamma + c : dbeta + (c - D);
+    d[0] += t.x; d[1] += t.y; d[2] += t.z; d[3] += t.w;
+  }
+}
+
+static int layernorm_bwd_impl(const void* dy, const void* x, const float* mean, const float* rstd,
+                              const float* gamma, const void* add, void* dx, float* dgamma,
+                              float* dbeta, int rows, int D, bool det, float* scratch, long long scratch_floats, hipStream_t stream) {
   if (!dy || !x || !mean || !rstd || !gamma || !dx) return MM_ERR_ARG;
   if ((dgamma == nullptr) != (dbeta == nullptr)) return MM_ERR_ARG;
   if (rows <= 0 || D <= 0 || (D % 8) || D > 64 * 8 * LN_MAX_CHUNKS) return MM_ERR_SHAPE;
@@ -234,10 +249,32 @@ extern "C" int medmoe_layernorm_bwd(const void* dy, const void* x, const float* 
   const int rpb = LNB_WAVES * (64 / lpr);
   const int grid = min((rows + rpb - 1) / rpb, 256 * 2);
   const int nch = (D / 8 + 63) / 64;
+  float* part = nullptr;
+  if (det && dgamma) {
+    if (!scratch || (long long)grid * 2 * D > scratch_floats) return MM_ERR_ARG;
+    part = scratch;
+  } else if (dgamma && grid > 1) ++g_mm_nondet;
 #define LN_BWD(N) hipLaunchKernelGGL((layernorm_bwd_kernel<N>), dim3(grid), dim3(LNB_WAVES * 64), 0, stream, (const bf16_t*)dy, \
-                                     (const bf16_t*)x, mean, rstd, gamma, (const bf16_t*)add, (bf16_t*)dx, dgamma, dbeta, rows, D)
+                                     (const bf16_t*)x, mean, rstd, gamma, (const bf16_t*)add, (bf16_t*)dx, dgamma, dbeta, rows, D, part)
 #define LN_BWD_L(L) hipLaunchKernelGGL((layernorm_bwd_kernel<1, L>), dim3(grid), dim3(LNB_WAVES * 64), 0, stream, (const bf16_t*)dy, \
-                                       (const bf16_t*)x, mean, rstd, gamma, (const bf16_t*)add, (bf16_t*)dx, dgamma, dbeta, rows, D)
+                                       (const bf16_t*)x, mean, rstd, gamma, (const bf16_t*)add, (bf16_t*)dx, dgamma, dbeta, rows, D, part)
   if (lpr == 16) LN_BWD_L(16); else if (lpr == 32) LN_BWD_L(32); else if (nch == 1) LN_BWD(1); else if (nch == 2) LN_BWD(2); else if (nch == 3) LN_BWD(3); else LN_BWD(4);
+  if (part) hipLaunchKernelGGL(layernorm_bwd_reduce_kernel, dim3((2 * D / 4 + 63) / 64), dim3(64, 16), 0, stream, part, grid, D, dgamma, dbeta);
   return mm_check_launch();
 }
+
+extern "C" int medmoe_layernorm_bwd(const void* dy, const void* x, const float* mean, const float* rstd,
+                                    const float* gamma, const void* add, void* dx, float* dgamma,
+                                    float* dbeta, int rows, int D, hipStream_t stream) {
+  return layernorm_bwd_impl(dy, x, mean, rstd, gamma, add, dx, dgamma, dbeta, rows, D, false, nullptr, 0, stream);
+}
+
+// medmoe_layernorm_bwd without atomics on dgamma / dbeta: every workgroup stores its partial rows into `scratch` (at least
+// medmoe_layernorm_bwd_det_scratch(D) floats, the caller's, one per stream), a second kernel adds them in workgroup order.
+extern "C" int medmoe_layernorm_bwd_det(const void* dy, const void* x, const float* mean, const float* rstd,
+                                        const float* gamma, const void* add, void* dx, float* dgamma,
+                                        float* dbeta, int rows, int D, float* scratch, long long scratch_floats, hipStream_t stream) {
+  return layernorm_bwd_impl(dy, x, mean, rstd, gamma, add, dx, dgamma, dbeta, rows, D, true, scratch, scratch_floats, stream);
+}
+
+extern "C" long long medmoe_layernorm_bwd_det_scratch(int D) { return 512ll * 2 * D; }      // the grid never passes 512 workgroups

@@ -23,6 +23,7 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g,
 extern "C" int medmoe_sumsq(const float* g, long long n, float* out, hipStream_t stream) {
   if (!g || !out || n <= 0) return MM_ERR_ARG;
   const int grid = (int)min((n / 4 + 255) / 256 + 1, (long long)2048);
+  if (grid > 1) ++g_mm_nondet;
   hipLaunchKernelGGL(sumsq_kernel, dim3(grid), dim3(256), 0, stream, g, n, out);
   return mm_check_launch();
 }

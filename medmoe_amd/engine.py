@@ -99,6 +99,10 @@ class Engine:
             raise RuntimeError("medmoe_amd.Engine needs a GPU: the HIP path is the only path")
         self.cfg = cfg
         self.device = torch.device(device)
+        # deterministic mode (cfg.deterministic, MEDMOE_DETERMINISTIC=1, Trainer(deterministic=True) -> set_deterministic): every launch of a
+        # step that sums in arrival order is replaced by its staged / single-writer form; self._det owns the scratch buffers, one per stream
+        self.deterministic, self._det = False, None
+        self.set_deterministic(cfg.deterministic or os.environ.get("MEDMOE_DETERMINISTIC", "0") == "1")
         torch.cuda.set_device(self.device)
         self.params = ParamStore(cfg, self.device, seed)
         self.vocab = vocab or VocabTables.synthetic(cfg.vocab, self.device)
@@ -155,6 +159,33 @@ class Engine:
         # optimiser (its bias-correction scalars are host values).  Single rank, frozen text tower.
         self.use_graph = os.environ.get("MEDMOE_GRAPH", "0") == "1"
         self._graph = None
+
+    def set_deterministic(self, flag: bool):
+        """Switch deterministic mode on or off; refuses the combinations it is not built for.  The scratch buffers are allocated on first
+        use, in deterministic mode only."""
+        flag = bool(flag)
+        if flag:
+            if not self.cfg.freeze_text:
+                raise NotImplementedError("deterministic with freeze_text=False (text.freeze_bert: false): the trainable text tower's embedding "
+                                          "gradients meet in fp32 atomics and index_add_ - a named follow-up (DESIGN 3e)")
+            if os.environ.get("MEDMOE_GRAPH", "0") == "1":
+                raise NotImplementedError("deterministic with MEDMOE_GRAPH=1: the captured launch sequences are the default mode's - a named "
+                                          "follow-up (DESIGN 3e)")
+        self.deterministic = flag
+        self._det = (self._det or ops.DetScratch(self.device)) if flag else None
+        if getattr(self, "_local", None) is not None:
+            self._local.det = self._det
+        if getattr(self, "_gle", None) is not None:
+            self._gle.det = self._det
+
+    def _parts(self, n: int) -> torch.Tensor:
+        """Deterministic mode: the loss heads' per-row terms (summed in row order by a second launch) - one fp32 buffer of the engine's.
+        One buffer serves every head and router_bwd_det only because all of them launch on the main stream, where stream order keeps
+        a head's summing launch ahead of the next head's stores; a launch on the second stream would need its own (as ops.DetScratch has)."""
+        buf = self.ws.get("det_parts")
+        if buf is None or buf.numel() < n:
+            buf = self.ws["det_parts"] = torch.empty(max(n, 2 * self.B * self.world), device=self.device, dtype=F32)
+        return buf
 
     # ------------------------------------------------------------------------------------------
     # workspace
@@ -586,10 +617,25 @@ class Engine:
     def _head(self, S, dS, rs, cs, w, accumulate, loss):
         """Cross-entropy against the diagonal, or (cfg.soft_label) the Soft-GLoRIA head, over the rows / columns of a [B, B] matrix."""
         c, B = self.cfg, self.B
-        if c.soft_label:
+        if self.deterministic:
+            if c.soft_label:
+                ops.call("soft_xent_strided_det", S, dS, self._soft, B, B, rs, cs, c.temp3, c.threshold0, c.threshold1, w, accumulate, loss, self._parts(B))
+            else:
+                ops.call("ce_strided_det", S, dS, B, B, rs, cs, 0, c.temp3, w, accumulate, loss, self._parts(B))
+        elif c.soft_label:
             ops.call("soft_xent_strided", S, dS, self._soft, B, B, rs, cs, c.temp3, c.threshold0, c.threshold1, w, accumulate, loss)
         else:
             ops.call("ce_strided", S, dS, B, B, rs, cs, 0, c.temp3, w, accumulate, loss)
+
+    def _ce(self, S, dS, rows, cols, rs, cs, off, w, accumulate, loss):
+        """medmoe_ce_strided with a label offset (the data-parallel heads), or its deterministic form."""
+        if self.deterministic:
+            ops.call("ce_strided_det", S, dS, rows, cols, rs, cs, off, self.cfg.temp3, w, accumulate, loss, self._parts(rows))
+        else:
+            ops.call("ce_strided", S, dS, rows, cols, rs, cs, off, self.cfg.temp3, w, accumulate, loss)
+
+    def _cos_scale_bwd(self, *a):
+        ops.call("cos_scale_bwd_det" if self.deterministic else "cos_scale_bwd", *a)
 
     def prefetch_cap_lens(self, ids: torch.Tensor):
         """Word-piece segment map + caption lengths (text_encoder.py:32-90) and an ASYNCHRONOUS copy of the lengths to
@@ -648,7 +694,7 @@ class Engine:
             cb = None
             if self.train_text:
                 cb = ws["cb"]; cb.zero_()
-            ops.call("cos_scale_bwd", ws["dS"], ws["S"], ws["na"], ws["nb"], ws["ca"], cb, B, B, 1e-8)
+            self._cos_scale_bwd(ws["dS"], ws["S"], ws["na"], ws["nb"], ws["ca"], cb, B, B, 1e-8)
             ops.call("sgemm", ws["dS"], txt_g, ws["d_img_g"], B, Do, B, B, 1, Do, 1, Do, 1.0, 0.0)
             ops.call("add_rowscaled", ws["d_img_g"], img_g, ws["ca"], B, Do)
             if self.train_text:                                   # the caption side of the same matrix: d txt_g = dS^T img_g + cb txt_g
@@ -664,12 +710,12 @@ class Engine:
             ops.call("rownorm", img_g, ws["na"], B, Do); ops.call("rownorm", txt_all, ws["nb"], Bg, Do)
             ops.call("sgemm", img_g, txt_all, ws["S"], B, Bg, Do, Do, 1, 1, Do, Bg, 1.0, 0.0)
             ops.call("cos_scale", ws["S"], ws["na"], ws["nb"], B, Bg, 1e-8)
-            ops.call("ce_strided", ws["S"], ws["dS"], B, Bg, Bg, 1, off, c.temp3, wg, 0, lp[2:])
+            self._ce(ws["S"], ws["dS"], B, Bg, Bg, 1, off, wg, 0, lp[2:])
             if grad:
                 cb1 = None
                 if self.train_text:
                     cb1 = ws["cb1"]; cb1.zero_()
-                ops.call("cos_scale_bwd", ws["dS"], ws["S"], ws["na"], ws["nb"], ws["ca"], cb1, B, Bg, 1e-8)
+                self._cos_scale_bwd(ws["dS"], ws["S"], ws["na"], ws["nb"], ws["ca"], cb1, B, Bg, 1e-8)
                 ops.call("sgemm", ws["dS"], txt_all, ws["d_img_g"], B, Do, Bg, Bg, 1, Do, 1, Do, 1.0, 0.0)
                 ops.call("add_rowscaled", ws["d_img_g"], img_g, ws["ca"], B, Do)
                 if self.train_text:       # my images against ALL captions: the gathered captions' gradient, summed over ranks, my slice comes back
@@ -678,11 +724,11 @@ class Engine:
             ops.call("rownorm", txt_g, ws["na2"], B, Do); ops.call("rownorm", img_all, ws["nb2"], Bg, Do)
             ops.call("sgemm", txt_g, img_all, ws["S2"], B, Bg, Do, Do, 1, 1, Do, Bg, 1.0, 0.0)
             ops.call("cos_scale", ws["S2"], ws["na2"], ws["nb2"], B, Bg, 1e-8)
-            ops.call("ce_strided", ws["S2"], ws["dS2"], B, Bg, Bg, 1, off, c.temp3, wg, 0, lp[2:])
+            self._ce(ws["S2"], ws["dS2"], B, Bg, Bg, 1, off, wg, 0, lp[2:])
             if not grad:
                 return
             ws["cb2"].zero_()
-            ops.call("cos_scale_bwd", ws["dS2"], ws["S2"], ws["na2"], ws["nb2"], ws["ca2"], ws["cb2"], B, Bg, 1e-8)
+            self._cos_scale_bwd(ws["dS2"], ws["S2"], ws["na2"], ws["nb2"], ws["ca2"], ws["cb2"], B, Bg, 1e-8)
             # d img_all = dM^T txt_local + cb * img_all ; summed over ranks, my slice comes back
             ops.call("sgemm", ws["dS2"], txt_g, ws["d_img_all"], Bg, Do, B, 1, Bg, Do, 1, Do, 1.0, 0.0)
             ops.call("add_rowscaled", ws["d_img_all"], img_all, ws["cb2"], Bg, Do)
@@ -726,6 +772,7 @@ class Engine:
                 self._local = kind(*args, word_grad=word_grad, sim=sim)
             else:
                 self._local = kind(*args, sim=sim)
+        self._local.det = self._det
         return self._local, gather
 
     def _local_heads(self, sim, gsim, w: float):
@@ -742,8 +789,8 @@ class Engine:
         c, Bg, lp = self.cfg, self.B * self.world, self.ws["loss_parts"]
         S = D_.gather_rows(sim)
         G = torch.empty_like(S)
-        ops.call("ce_strided", S, G, Bg, Bg, Bg, 1, 0, c.temp3, w, 0, lp[3:])
-        ops.call("ce_strided", S, G, Bg, Bg, 1, Bg, 0, c.temp3, w, 1, lp[3:])
+        self._ce(S, G, Bg, Bg, Bg, 1, 0, w, 0, lp[3:])
+        self._ce(S, G, Bg, Bg, 1, Bg, 0, w, 1, lp[3:])
         return G
 
     def forward_backward_losses(self, labels: torch.Tensor, loss_scale: float = 1.0):
@@ -793,7 +840,7 @@ class Engine:
         dx = ws["dxa"]
         ops.call("pos_cls_grad", dx, p.grad("vit.pos_embed"), p.grad("vit.cls_token"), B, Nt, Dv)
         ops.gemm_tn(dx, ws["im2col"], p.grad("vit.patch_embed.weight"), db=p.grad("vit.patch_embed.bias"),
-                    g_rowmap=ws["rowmap_patch"], M=B * P)
+                    g_rowmap=ws["rowmap_patch"], M=B * P, det=self._det)
         self._wait(w_last)                                   # join: every weight gradient is final before the optimiser / the caller
         if bucket_ready is not None:
             bucket_ready(0)              # patch / CLS / position embeddings: complete
@@ -813,12 +860,15 @@ class Engine:
 
     def _wgrad(self, *a, **kw):
         side, main = self._wg_side, self._wg_main
-        if self.wgrad_staged and "row_off" not in kw and "x_rowmap" not in kw and "g_rowmap" not in kw:
+        if self.deterministic:
+            kw["det"] = self._det                                # medmoe_gemm_tn_det with the launch stream's own scratch (ops.DetScratch)
+        elif self.wgrad_staged and "row_off" not in kw and "x_rowmap" not in kw and "g_rowmap" not in kw:
             # plain wgrads: partial tiles through a scratch buffer + one summing kernel instead of 64 MB of fp32 atomics per launch
             # (medmoe_gemm_tn_staged); every launch of this method runs on one stream, so one scratch serves them all
             sc = self.ws.get("wg_scratch")
             if sc is None:
-                sc = self.ws["wg_scratch"] = torch.empty(256 * 65536, device=self.device, dtype=F32)
+                # at most 256 partial tiles per launch, each with its 512 column sums of G behind the tiles: db is staged too
+                sc = self.ws["wg_scratch"] = torch.empty(256 * (65536 + 512), device=self.device, dtype=F32)
             kw["scratch"] = sc
         if side is None:
             ops.gemm_tn(*a, **kw)
@@ -846,9 +896,14 @@ class Engine:
         use_gate = k > 1
         if use_gate:
             ws["dgate"].zero_()
-        ops.call("scale_attn_bwd", ws["d_img_l"], ws["d_img_g"], ws["G"], ws["H1"], ws["wts"], p.f32("moe.attn2.weight"),
-                 ws["eout"], ws["expert_of_slot"], ws["item_of_slot"], ws["gates"], k, P, ws["dG"], ws["dH1"],
-                 p.grad("moe.attn2.weight"), p.grad("moe.attn2.bias"), ws["dgate"] if use_gate else None, R, Do, Dh)
+        sa = (ws["d_img_l"], ws["d_img_g"], ws["G"], ws["H1"], ws["wts"], p.f32("moe.attn2.weight"),
+              ws["eout"], ws["expert_of_slot"], ws["item_of_slot"], ws["gates"], k, P, ws["dG"], ws["dH1"],
+              p.grad("moe.attn2.weight"), p.grad("moe.attn2.bias"), ws["dgate"] if use_gate else None, R, Do, Dh)
+        if self.deterministic:
+            sc = self._det.get(ops._scratch_query("scale_attn_bwd_det_scratch", R, P, Dh))
+            ops.call("scale_attn_bwd_det", *sa, ws["row_off"], E, sc, sc.numel())
+        else:
+            ops.call("scale_attn_bwd", *sa)
         grp = self._expert_tiles
         w_moe = None
         for s, l in enumerate(c.stage_layers()):
@@ -873,9 +928,13 @@ class Engine:
                 ops.gemm_nt(ws["dG"][s], p.w16t(f"moe.proj.{s}.weight"), ws["dF"][s], stride_b=Do * Dv, **grp(Do))
         # ---- router backward: CE on probabilities (medmoe_module.py:235-237) + gate gradients ----
         Hd = c.router_hidden
-        ops.call("router_bwd", ws["probs"], ws["router_h"], p.f32("moe.router.2.weight"), ws["idx"],
-                 ws["dgate"] if use_gate else None, lab32, dprobs_ext, c.w_cls * loss_scale / B, ws["dlogits"], ws["drouter_h"],
-                 ws["loss_parts"], B, Hd, E, k)
+        rb = (ws["probs"], ws["router_h"], p.f32("moe.router.2.weight"), ws["idx"],
+              ws["dgate"] if use_gate else None, lab32, dprobs_ext, c.w_cls * loss_scale / B, ws["dlogits"], ws["drouter_h"],
+              ws["loss_parts"], B, Hd, E, k)
+        if self.deterministic:
+            ops.call("router_bwd_det", *rb, self._parts(2 * B))
+        else:
+            ops.call("router_bwd", *rb)
         sg = lambda *a: ops.call("sgemm", *a)
         sg(ws["dlogits"], ws["router_h"], p.grad("moe.router.2.weight"), E, Hd, B, 1, E, Hd, 1, Hd, 1.0, 1.0)
         sg(ws["ones"], ws["dlogits"], p.grad("moe.router.2.bias"), 1, E, B, 0, 1, E, 1, E, 1.0, 1.0)
@@ -895,7 +954,7 @@ class Engine:
         L = c.n_layer_v
         dx, dx2 = ws["dxa"], ws["dxb"]
         ops.layernorm_bwd(ws["dln"], ws[f"x{L}"], ws["stf"][0], ws["stf"][1], p.f32("vit.final_layer_norm.weight"), dx,
-                          p.grad("vit.final_layer_norm.weight"), p.grad("vit.final_layer_norm.bias"))
+                          p.grad("vit.final_layer_norm.weight"), p.grad("vit.final_layer_norm.bias"), det=self._det)
         if bucket_ready is not None:
             wait(w_moe)                  # the experts' weight gradients ran on the second stream
             bucket_ready(L + 1)          # final LN + router + experts: complete
@@ -914,7 +973,7 @@ class Engine:
             ops.gemm_nt(ws["dz"], p.w16t(pre + "feedforward.model.0.weight"), ws["dln"])
             wait(w_dx2)
             ops.layernorm_bwd(ws["dln"], ws[f"xmid{l}"], st2[0], st2[1], p.f32(pre + "feedforward_layernorm.weight"), dx2,
-                              p.grad(pre + "feedforward_layernorm.weight"), p.grad(pre + "feedforward_layernorm.bias"), add=dx)
+                              p.grad(pre + "feedforward_layernorm.weight"), p.grad(pre + "feedforward_layernorm.bias"), add=dx, det=self._det)
             # attention: xmid = att Wo^T + bo + x
             w_dx2 = wgrad(dx2, ws[f"att{l}"], p.grad(pre + "attention.output_proj.weight"), db=p.grad(pre + "attention.output_proj.bias"))
             ops.gemm_nt(dx2, p.w16t(pre + "attention.output_proj.weight"), ws["datt"])
@@ -924,7 +983,7 @@ class Engine:
             ops.gemm_nt(ws["dqkv"], p.w16t(pre + "attention.input_proj.weight"), ws["dln"])
             wait(w_dx)                                       # the FC2 wgrad read dx: done before LayerNorm-backward rewrites it
             ops.layernorm_bwd(ws["dln"], ws[f"x{l}"], st1[0], st1[1], p.f32(pre + "attention_layernorm.weight"), dx,
-                              p.grad(pre + "attention_layernorm.weight"), p.grad(pre + "attention_layernorm.bias"), add=dx2)
+                              p.grad(pre + "attention_layernorm.weight"), p.grad(pre + "attention_layernorm.bias"), add=dx2, det=self._det)
             if bucket_ready is not None:
                 wait(w_dqkv)                                 # the side stream runs in order: its last wgrad of the layer covers all four
                 bucket_ready(l + 1)      # layer l: complete
@@ -1045,6 +1104,7 @@ class Engine:
         else:           # 256 regions: training uses the LDS-tiled pair kernels, whose forward and backward are one launch
             if self._gle is None:
                 self._gle = GenericLocalLoss(B, P, T, Do, self.device, sim=ws["sim"])
+            self._gle.det = self._det
             sim = self._gle.forward(ctx, words, caps, c.temp1, c.temp2)
         if gather:
             self._gathered_local_heads(sim, c.w_local / (B * self.world))

@@ -16,6 +16,7 @@ BF, F32, I32 = torch.bfloat16, torch.float32, torch.int32
 
 class GenericLocalLoss:
     host_lens = False                                             # forward needs the caption lengths on the device only: no host synchronisation
+    det = None                                                    # ops.DetScratch (deterministic mode), handed to the wgrad-shaped GEMM
 
     def __init__(self, B: int, HW: int, T: int, D: int, device, word_grad: bool = False, sim: Optional[torch.Tensor] = None):
         """sim: write the similarities into this fp32 [B, B] tensor of the caller's."""
@@ -74,7 +75,8 @@ class GenericLocalLoss:
         ops.call("local_scores_ragged", ctx16, words16, cap_lens, self.lp, self.lse, B, B, HW, T, D, self.members, B, Tp // 16, 0, Kp)
         ops.call("local_gen_fwd_a", self.lp, cap_lens, self.A, B, B, HW, HWp, T, Tp, temp1, Kp)
         self.WC.zero_()
-        ops.gemm_tn(self.A, ctx16, self.WC, x_rowmap=self.xmap, row_off=self.row_off, n_groups=B, stride_w=Kp * D, nsplit=1, M=B * HWp)
+        ops.gemm_tn(self.A, ctx16, self.WC, x_rowmap=self.xmap, row_off=self.row_off, n_groups=B, stride_w=Kp * D, nsplit=1, M=B * HWp,
+                    det=self.det)
         ops.call("local_gen_cos", self.WC, words16, self.wn, cap_lens, self.sim, self.stats, self.sume, B, B, T, Tp, D, temp2, 1e-8, Kp)
         return self.sim
 

@@ -21,6 +21,7 @@ class RaggedLocalLoss:
     and writes the bf16 gradient of the region features into `out`.  The instance owns its buffers; the pair matrices self.pair =
     {l_A, l_dS, l_U, wT} are sized on the first forward (`grow_pair_buffers`)."""
     host_lens = True                                              # forward also takes the caption lengths on the host (the class tables are built there)
+    det = None                                                    # ops.DetScratch (deterministic mode), handed to the wgrad-shaped GEMM
 
     def __init__(self, B: int, P: int, T: int, Do: int, device, sim: Optional[torch.Tensor] = None):
         """sim: write the similarities into this fp32 [B, B] tensor of the caller's."""
@@ -95,5 +96,5 @@ class RaggedLocalLoss:
             ops.gemm_nt(lU, lA, self.dGm, tiles=self.imgp_tiles, tile_count=self.imgp_tile_count,
                         max_tiles=self.imgp_tiles.shape[0], stride_b=HWp * Kp, M=B * HWp, N=HWp)
         ops.gemm_tn(self.dGm, ctx, self.dC32.view(B, HWp, Do), x_rowmap=self.ctx_xmap, row_off=self.imgp_row_off, n_groups=B,
-                    stride_w=HWp * Do, nsplit=1, M=B * HWp)                                  # dC_b += dGm_b . ctx_b
+                    stride_w=HWp * Do, nsplit=1, M=B * HWp, det=self.det)                    # dC_b += dGm_b . ctx_b
         ops.call("unpad_cast", self.dC32, out, B, P, HWp, Do)

@@ -79,6 +79,7 @@ class TransposedLocalLoss:
     gm3 and their tile tables, dGm32, dGmq, dC32q); the ragged pair matrices self.pair = {l_dS, l_A, (l_U,) words_r, l_stats3, (l_d2,)
     (l_dwn)} are sized on the first forward (`grow_pair_buffers`), so evaluation through `local_sim_forward` never allocates them."""
     host_lens = True                                              # forward also takes the caption lengths on the host (the class tables are built there)
+    det = None                                                    # ops.DetScratch (deterministic mode): the wgrad-shaped GEMMs take their staged / single-writer forms
 
     def __init__(self, B: int, P: int, T: int, Do: int, device, gram: bool = True, Bc: Optional[int] = None, word_grad: bool = False,
                  pitch: Optional[int] = None, sim: Optional[torch.Tensor] = None):
@@ -219,14 +220,14 @@ class TransposedLocalLoss:
         dC = self.dC32q
         dC.zero_(); self.dGm32.zero_()
         # dC = dS^T . W with the B image blocks seen as ONE [Kp][B*HWq] operand (chunks of HWq columns, bs apart): full 256-column tiles
-        ops.call("gemm_tn_cols", X, ld, Wr, Do, dC, Do, Kp, B * HWq, Do, 1, 0, 0, 0, HWq, bs)
+        ops.gemm_tn_cols(X, ld, Wr, Do, dC, Do, Kp, B * HWq, Do, 1, 0, 0, 0, HWq, bs, det=self.det)
         if self.gram:
-            ops.call("gemm_tn_gram", AT, ld, d2, srows, 1, self.dGm32, HWq, Kp, HWq, B, bs, HWq * HWq)               # dGm_b = A_b^T diag(d2_b) A_b
+            ops.gemm_tn_gram(AT, ld, d2, srows, 1, self.dGm32, HWq, Kp, HWq, B, bs, HWq * HWq, det=self.det)         # dGm_b = A_b^T diag(d2_b) A_b
         else:
-            ops.call("gemm_tn_cols", UT, ld, AT, ld, self.dGm32, HWq, Kp, HWq, HWq, B, bs, bs, HWq * HWq, 0, 0)        # dGm_b = U_b^T A_b
+            ops.gemm_tn_cols(UT, ld, AT, ld, self.dGm32, HWq, Kp, HWq, HWq, B, bs, bs, HWq * HWq, 0, 0, det=self.det)  # dGm_b = U_b^T A_b
         self.dGmq.copy_(self.dGm32.view(B * HWq, HWq))
         ops.gemm_tn(self.dGmq, ctx, dC.view(B, HWq, Do), x_rowmap=self.ctx_xmap_q, row_off=self.rowoff_q, n_groups=B,
-                    stride_w=HWq * Do, nsplit=1, M=B * HWq)                                  # dC_b += dGm_b . ctx_b
+                    stride_w=HWq * Do, nsplit=1, M=B * HWq, det=self.det)                    # dC_b += dGm_b . ctx_b
         ops.call("unpad_cast", dC, out, B, P, HWq, Do)
         if not self.word_grad:
             return None

@@ -194,12 +194,52 @@ def set_option(key: int, value: int):
     _chk(load_library().medmoe_set_option(_c.c_int(key), _c.c_int(value)), "set_option")
 
 
+class DetScratch:
+    """The scratch buffers of deterministic mode: one fp32 buffer per stream (launches on different streams may overlap), allocated on first
+    use and grown on demand while that stream is current, so the allocator orders a buffer's reuse behind the launches that read it."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self.bufs = {}
+
+    def get(self, floats: int) -> torch.Tensor:
+        key = _stream_handle() if self.device.type == "cuda" else 0
+        buf = self.bufs.get(key)
+        if buf is None or buf.numel() < floats:
+            self.bufs[key] = None                                   # release before allocating
+            buf = self.bufs[key] = torch.empty(max(int(floats), 1024), device=self.device, dtype=torch.float32)
+        return buf
+
+
+def nondet_launches() -> int:
+    """medmoe_nondet_launches: launches of this process so far that took an order-dependent form (atomic epilogues with several writers per
+    element, atomic loss sums).  A step in deterministic mode leaves it unchanged."""
+    f = _FN.get("nondet_launches")
+    if f is None:
+        f = load_library().medmoe_nondet_launches
+        f.argtypes = []
+        f.restype = _c.c_longlong
+        _FN["nondet_launches"] = f
+    return int(f())
+
+
+def _scratch_query(name: str, *ints) -> int:
+    f = _FN.get(name)
+    if f is None:
+        f = getattr(load_library(), "medmoe_" + name)
+        f.argtypes = [_c.c_int] * len(ints)
+        f.restype = _c.c_longlong
+        _FN[name] = f
+    return int(f(*ints))
+
+
 def gemm_tn(g, x, dw, *, db=None, x_rowmap=None, g_rowmap=None, row_off=None, n_groups=1,
-            stride_w=0, stride_db=0, nsplit=16, M=None, stream=None, scratch=None):
+            stride_w=0, stride_db=0, nsplit=16, M=None, stream=None, scratch=None, det: Optional[DetScratch] = None):
     """dw[g][Nn,Kk] += g[M,Nn]^T @ x[M,Kk]; db[g][Nn] += colsum(g).  fp32 atomic accumulation.  stream: a raw stream handle to launch on
     instead of torch's current stream (the caller orders it: stream_fork).  scratch (fp32, plain operands only): medmoe_gemm_tn_staged -
     partial tiles stored there and summed by a second kernel instead of atomics on dw, when the shape allows; the caller must not hand the
-    same scratch to launches that can overlap."""
+    same scratch to launches that can overlap.  det (deterministic mode): medmoe_gemm_tn_det on the current stream with that stream's scratch -
+    no order-dependent sum in dw or db, `nsplit` is not used."""
     lib = load_library()
     _need(g, torch.bfloat16, "g"); _need(x, torch.bfloat16, "x"); _need(dw, torch.float32, "dw")
     if M is None:
@@ -212,6 +252,25 @@ def gemm_tn(g, x, dw, *, db=None, x_rowmap=None, g_rowmap=None, row_off=None, n_
     for t, nm in ((x_rowmap, "x_rowmap"), (g_rowmap, "g_rowmap"), (row_off, "row_off")):
         if t is not None:
             _need(t, torch.int32, nm)
+    if det is not None:
+        if stream is not None:
+            raise ValueError("gemm_tn: deterministic launches run on the current stream (their scratch belongs to it)")
+        fd = _TN_FN.get(2)
+        if fd is None:
+            fd = lib.medmoe_gemm_tn_det
+            I, L, P = _c.c_int, _c.c_longlong, _vp
+            fd.argtypes = [P, I, P, I, P, I, P, I, I, I, P, P, P, I, L, L, P, L, P]
+            fd.restype = I
+            _TN_FN[2] = fd
+        need = _scratch_query("gemm_tn_det_scratch", M, Nn, Kk, int(x_rowmap is not None), int(g_rowmap is not None), int(row_off is not None), n_groups)
+        sc = det.get(need)
+        dp = lambda t: None if t is None else t.data_ptr()
+        dargs = (g.data_ptr(), g.stride(-2), x.data_ptr(), x.stride(-2), dw.data_ptr(), dw.stride(-2), dp(db), M, Nn, Kk, dp(x_rowmap), dp(g_rowmap),
+                 dp(row_off), n_groups, stride_w, stride_db, sc.data_ptr(), sc.numel())
+        with _Timed("gemm_tn_det (wgrad, staged / single writer: gemm_tn4w_kernel + tn_reduce_det_kernel / gemm_tn_kernel)", 2.0 * M * Nn * Kk, "flop",
+                    ("tn", M, Nn, Kk, n_groups)):
+            _chk(fd(*dargs, _stream_handle()), "gemm_tn_det")
+        return dw
     if scratch is not None and x_rowmap is None and g_rowmap is None and row_off is None and n_groups == 1:
         _need(scratch, torch.float32, "scratch")
         fs = _TN_FN.get(1)
@@ -268,13 +327,21 @@ def layernorm_fwd(x, gamma, beta, y, mean, rstd, eps):
     return y
 
 
-def layernorm_bwd(dy, x, mean, rstd, gamma, dx, dgamma=None, dbeta=None, add=None):
+def layernorm_bwd(dy, x, mean, rstd, gamma, dx, dgamma=None, dbeta=None, add=None, det: Optional[DetScratch] = None):
+    """det (deterministic mode): dgamma / dbeta leave as per-workgroup partial rows summed in workgroup order (medmoe_layernorm_bwd_det)."""
     lib = load_library()
     for t, nm in ((dy, "dy"), (x, "x"), (dx, "dx")):
         _need(t, torch.bfloat16, nm)
         if not t.is_contiguous():
             raise ValueError(f"layernorm_bwd: {nm} must be contiguous")
     rows, D = x.numel() // x.shape[-1], x.shape[-1]
+    if det is not None and dgamma is not None:
+        sc = det.get(_scratch_query("layernorm_bwd_det_scratch", D))
+        with _Timed("layernorm_bwd_kernel + layernorm_bwd_reduce_kernel", (8.0 if add is not None else 6.0) * rows * D, "byte"):
+            rc = lib.medmoe_layernorm_bwd_det(_ptr(dy), _ptr(x), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(add), _ptr(dx),
+                                              _ptr(dgamma), _ptr(dbeta), _c.c_int(rows), _c.c_int(D), _ptr(sc), _c.c_longlong(sc.numel()), _stream())
+            _chk(rc, "layernorm_bwd_det")
+        return dx
     with _Timed("layernorm_bwd_kernel", (8.0 if add is not None else 6.0) * rows * D, "byte"):
         rc = lib.medmoe_layernorm_bwd(_ptr(dy), _ptr(x), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(add), _ptr(dx),
                                       _ptr(dgamma), _ptr(dbeta), _c.c_int(rows), _c.c_int(D), _stream())
@@ -428,6 +495,9 @@ _SIGS = {
     "win_attn_fwd": "ppppiiiiii", "win_attn_bwd": "ppppppiiiiii", "patch_merge": "ppiiiii", "drop_path": "ppppil",
     "dropout_mask": "pliillll", "dropout_apply": "ppliillllf", "dropout_add_layernorm_fwd": "ppppppppiifllllf",
     "attn_drop_fwd": "ppppiiiillllf", "attn_drop_bwd": "pppppppiiiillllf",
+    "gemm_tn_cols_det": "pipipiiiiilllilpl", "gemm_tn_gram_det": "piplipiiiill", "scale_attn_bwd_det": "ppppppppppiipppppiiipipl",
+    "router_bwd_det": "pppppppfpppiiiip", "ce_strided_det": "ppiilliffipp", "soft_xent_strided_det": "pppiillffffipp", "hardneg_strided_det": "ppiillffipp",
+    "cos_scale_bwd_det": "ppppppiif",
     "sumsq": "plp", "sumsq_det": "plpp", "adam_step": "pppppldddddipff", "cast_bf16": "ppl", "transpose_many": "pppii",
 }
 
@@ -501,14 +571,31 @@ def _cost_tn_gram(a):       # (AT, ld, d2, srows, 1, out, ldo, Kp, HWq, B, bs, o
 
 _COSTS = {
     "local_scores_t": _cost_scores, "local_pair3": _cost_pair3, "local_pair3_wgrad": _cost_pair3, "local_sim_fwd": _cost_local_sim, "gemm_tn_cols": _cost_tn_cols, "gemm_tn_gram": _cost_tn_gram,
+    "gemm_tn_cols_det": _cost_tn_cols, "gemm_tn_gram_det": _cost_tn_gram,
     "adam_step": lambda a: ("adam_kernel", 34.0 * a[5], "byte"),                                   # p, g, m, v read; p, m, v, bf16 copy written
     "scale_attn_bwd": lambda a: ("scale_attn_bwd_kernel", 2.0 * a[17] * (4 * (2 * a[18] + 2 * a[19]) + 2 * a[18]), "byte"),    # G, dG, H1, dH1 x 4 scales + eout, d_img_l rows
+    "scale_attn_bwd_det": lambda a: ("scale_attn_bwd_kernel<DET> + scale_attn_bwd_reduce_kernel", 2.0 * a[17] * (4 * (2 * a[18] + 2 * a[19]) + 2 * a[18]), "byte"),
     "scale_attn_fwd": lambda a: ("scale_attn_fwd_kernel", 2.0 * a[8] * (4 * (a[9] + a[10]) + a[9]), "byte"),
     "dropout_add_layernorm_fwd": lambda a: ("dropout_add_layernorm_fwd_kernel", 8.0 * a[8] * a[9], "byte"),    # z, residual read; x1, y written
     "attn_drop_fwd": lambda a: ("attn_drop_fwd_kernel", 4.0 * a[5] * a[5] * 64 * a[4] * a[6], "flop"),
     "attn_drop_bwd": lambda a: ("attn_drop_bwd_kernel", 10.0 * a[8] * a[8] * 64 * a[7] * a[9], "flop"),
     "layernorm_fwd_rows": lambda a: ("layernorm_fwd_kernel", 4.0 * (ROWS_HINT or a[6]) * a[7], "byte"),
 }
+
+
+def gemm_tn_cols(G, ldg, X, ldx, dW, ldw, M, Nn, Kk, n_groups, gcol_stride, xcol_stride, stride_w, g_chunk_w, g_chunk_stride,
+                 det: Optional[DetScratch] = None):
+    """medmoe_gemm_tn_cols; det (deterministic mode): medmoe_gemm_tn_cols_det with the current stream's scratch."""
+    a = (G, ldg, X, ldx, dW, ldw, M, Nn, Kk, n_groups, gcol_stride, xcol_stride, stride_w, g_chunk_w, g_chunk_stride)
+    if det is None:
+        return call("gemm_tn_cols", *a)
+    sc = det.get(_scratch_query("gemm_tn_cols_det_scratch", M, Nn, Kk, n_groups))
+    call("gemm_tn_cols_det", *a, sc, sc.numel())
+
+
+def gemm_tn_gram(*a, det: Optional[DetScratch] = None):
+    """medmoe_gemm_tn_gram; det (deterministic mode): its single-writer form medmoe_gemm_tn_gram_det."""
+    call("gemm_tn_gram" if det is None else "gemm_tn_gram_det", *a)
 
 
 def local_fast_path(HW: int, T: int) -> bool:

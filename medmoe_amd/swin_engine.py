@@ -35,6 +35,9 @@ class SwinEngine:
     def __init__(self, engine: Engine, encoder: SwinMoEEncoder, drop_path_rate: float = 0.1):
         if engine.cfg.soft_label and engine.dist:
             raise NotImplementedError("soft_label with more than one rank (losses.py:826-883 has no gather)")
+        if getattr(engine, "deterministic", False):
+            raise NotImplementedError("deterministic with the Swin-T encoder (vision.arch = swin_t, SwinEngine): the relative-position bias "
+                                      "tables' gradients are summed by index_add_ - a named follow-up (DESIGN 3e)")
         self.eng, self.enc, self.cfg = engine, encoder, engine.cfg
         self.device = encoder.dev
         self.train_text = engine.train_text

@@ -79,6 +79,8 @@ class Trainer:
         self.default_root_dir, self.min_epochs, self.max_epochs = default_root_dir, min_epochs, max_epochs
         self.accumulate_grad_batches = max(1, int(accumulate_grad_batches))
         self.gradient_clip_val = gradient_clip_val
+        # Lightning's `deterministic`: handed to the module at the start of fit / validate / test, which hands it to its engine
+        self.deterministic = bool(deterministic)
         self.check_val_every_n_epoch = max(1, int(check_val_every_n_epoch))
         self.limit_train_batches, self.limit_val_batches = limit_train_batches, limit_val_batches
         self.callbacks = [c for c in (callbacks or []) if isinstance(c, Callback)]
@@ -129,7 +131,19 @@ class Trainer:
                 p.grad.copy_(g)
             off += n
 
+    def _hand_over(self, model):
+        """trainer.deterministic reaches the kernels through the module (`set_deterministic`); asking for it on a module that cannot honour it
+        is an error, not a run that silently does not repeat.  The trainer only raises the flag: an engine already deterministic through its
+        config or MEDMOE_DETERMINISTIC=1 stays so under the trainer's default False."""
+        if not self.deterministic:
+            return
+        if hasattr(model, "set_deterministic"):
+            model.set_deterministic(True)
+        else:
+            raise NotImplementedError(f"trainer.deterministic=true: {type(model).__name__} has no set_deterministic")
+
     def fit(self, model, datamodule=None, ckpt_path: Optional[str] = None):
+        self._hand_over(model)
         if ckpt_path:
             ckpt = torch.load(ckpt_path, map_location="cpu", weights_only=True)
             model.load_state_dict(ckpt["state_dict"])
@@ -203,6 +217,7 @@ class Trainer:
     def validate(self, model, datamodule, step: str = "validation_step"):
         """Mean `loss` over the validation batches -> val/loss.  A module that defines `validation_step` / `test_step` (the reference's
         hooks, medmoe_module.py:114-134) is evaluated through them; any other through `model_step`."""
+        self._hand_over(model)
         model.eval()
         step_fn = getattr(model, step, None)
         tot, n = 0.0, 0

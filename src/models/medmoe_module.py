@@ -129,6 +129,20 @@ class MedMoEPretrainingLightningModule(_Base):
         c.threshold0, c.threshold1 = float(_get(self.loss_cfg, "threshold0", 0.98)), float(_get(self.loss_cfg, "threshold1", 0.97))
         c.lr, c.weight_decay = float(opt.keywords.get("lr", 1e-3)), float(opt.keywords.get("weight_decay", 0.0))
 
+    def set_deterministic(self, flag: bool):
+        """trainer.deterministic: hand the flag to the HIP engine behind self.model (medmoe_amd.Engine.set_deterministic - every launch of
+        a step in its staged / single-writer form); the engine refuses the configurations the mode is not built for."""
+        flag = bool(flag)
+        eng = getattr(self.model, "engine", None)
+        if eng is None:
+            if flag:
+                raise NotImplementedError("trainer.deterministic=true needs the HIP engine behind self.model")
+            return
+        if flag and getattr(self.model, "swin", None) is not None:
+            raise NotImplementedError("deterministic with the Swin-T encoder (vision.arch = swin_t, SwinEngine): the relative-position bias "
+                                      "tables' gradients are summed by index_add_")
+        eng.set_deterministic(flag)
+
     def configure_fused(self, accumulate_grad_batches: int = 1, gradient_clip_val=None):
         """The trainer's two keys the fused step has to honour itself (trainer.accumulate_grad_batches, trainer.gradient_clip_val;
         pretraining_medmoe.yaml:23-24).  gradient_clip_val None / 0 = no clipping."""
