@@ -24,7 +24,13 @@ check-plan: tools/det_plan_check.cpp $(CSRC)/det_plan.h
 	$(CXX) -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I$(CSRC) $< -o build/det_plan_check
 	build/det_plan_check
 
+# host-only model of the per-block row-sum exchange of the backward pair launch (pair3.hip), under the thread sanitizer
+check-exchange: tools/pair3_exchange_check.cpp
+	@mkdir -p build
+	$(CXX) -std=c++17 -O1 -g -fsanitize=thread -pthread $< -o build/pair3_exchange_check
+	build/pair3_exchange_check
+
 clean:
 	rm -rf build $(LIB)
 
-.PHONY: all clean check-plan
+.PHONY: all clean check-plan check-exchange

@@ -21,6 +21,26 @@
 // Two launches per class: FWD writes sim, A (bf16) and the per-word sums (num, n2); after the cross-entropy over the sim matrix has
 // produced gsim = dL/dsim, BWD reads the log-probabilities, A and those sums back and writes dS (over the log-probabilities, in
 // place) and U = 2 dn2 A, both already scaled by gsim.
+//
+// The backward launch walks the region blocks sp = 0 .. NS-1 (two row tiles each) ONCE.  For block sp a wave forms y = Gm . A (seven MFMAs
+// per row tile), a1 = exp2(lp), S and da1 = a (k1 S + k2 y - k3), reduces a1 da1 over its 16 words (DPP) and keeps the block's eight da1 in
+// registers.  The word-softmax backward needs rd[hw] = sum of a1 da1 over ALL the caption's words, i.e. over the caption's NTT waves:
+//   NTT == 1: the DPP sum is rd, in every lane - no mailbox, no flag; ds = dn a + a1 (da1 - rd) and the block's 16-byte store follow at once.
+//   NTT > 1:  the wave writes its row sums into its mailbox slot of block sp (Rw + 32 sp ..), publishes flagR[wave] = 8 epoch + sp + 1 (behind
+//             s_waitcnt lgkmcnt(0): the sums are in the LDS before the flag; the values rise through a unit and from unit to unit), and THEN
+//             finishes block sp - 1: waits until the caption's NTT flags are all >= 8 epoch + sp, adds their slots in wave order w0 .. w0+NTT-1
+//             (the sum does not depend on which wave reads), forms ds from the kept da1 and stores the block.  Block NS-1 is finished behind
+//             the loop.  One block of lag: the partners' sums of block sp - 1 are usually there when they are asked for.
+// (An earlier form made pass a = all row sums, one exchange, pass b = everything again + ds: 91 MFMAs and fragment reads twice per unit.)
+// The mailboxes are double-buffered by epoch parity; the exchange rests on two arguments:
+//   No deadlock.  Every wave publishes block sp before it waits for anybody's block sp - 1, and what it does before that publish waits only
+//   for blocks < sp - 1: by induction over (epoch, sp) every awaited value gets published without its publisher waiting on a later block
+//   of the waiter.  All waves of a caption group sit in one resident workgroup and run the same j iterations; the idle waves of
+//   NTT 3 and 5 leave before the loop and no one waits for them.
+//   No slot is overwritten while it is read.  Slot (epoch k+2, sp) is slot (epoch k, sp).  To write it a wave must have finished epoch k+1,
+//   last of all its block NS-1, which needs every partner's flag 8 (k+1) + NS.  A partner publishes that flag behind s_waitcnt lgkmcnt(0),
+//   by which all its mailbox reads of epoch k (made while finishing the blocks of epoch k, before its epoch k+1 began) have returned.
+//   Inside one epoch every slot is written once, before the flag that lets it be read.
 #include "common.h"
 
 struct Pair3Args {
@@ -81,6 +101,14 @@ __device__ __forceinline__ void flag_publish(unsigned addr, int epoch) {
 }
 __device__ __forceinline__ void flag_wait(unsigned addr, int epoch) {
   while ((int)__builtin_amdgcn_readfirstlane(lds_load_b32(addr)) < epoch) __builtin_amdgcn_s_sleep(1);
+}
+
+// all N flags of a caption's waves (N <= 5 consecutive words from addr0) in one read: lane q reads wave q's flag, the wave leaves when no lane
+// has seen less than `value`
+template <int N>
+__device__ __forceinline__ void flag_wait_group(unsigned addr0, int lane, int value) {
+  const unsigned addr = addr0 + min(lane, N - 1) * 4;
+  while (__builtin_amdgcn_ballot_w64((int)lds_load_b32(addr) < value) != 0) __builtin_amdgcn_s_sleep(1);
 }
 
 template <int HW, int NTT, bool BWD, bool WN = false>       // WN: the backward launch also writes the word-norm coefficients p.dwn
@@ -316,62 +344,29 @@ __global__ __launch_bounds__(1024) void local_pair3_kernel(Pair3Args p) {
       }
     }
     __builtin_amdgcn_sched_barrier(0);
-    // ---- pass a: rd[hw] = sum over the caption's words of a1 da1 (word-softmax backward) ----
-    // Row-sum mailboxes by epoch parity: the backward launch has no other exchange between two of these, so a wave can write epoch
-    // k+1 while a partner still reads epoch k (never k+2: its own pass b of k+1 needs that partner's k+1 flag first)
+    // ---- one walk over the region blocks: y, a1, da1 and the row sums rd[hw] = sum over the caption's words of a1 da1 (word-softmax
+    // backward) once per row tile; dS = dnum A + a1 (da1 - rd), over the log-probabilities in place, one block behind (header comment) ----
     float* Rall = Rbase + (epoch & 1) * 16 * GR;
     float* Rw = Rall + wid * GR;
-#pragma unroll
-    for (int s = 0; s < NS; ++s) { opaque(lpv[s]); opaque(af[s]); }
-#pragma unroll
-    for (int rt = 0; rt < NRTA; ++rt) {
-      const int sp = rt >> 1, h = rt & 1;
-      const float4 L4 = *(const float4*)(Lw + 32 * sp + 8 * g + 4 * h);
-      const f32x4_t y = y_tile_now(rt);
-      const float Lr[4] = {L4.x, L4.y, L4.z, L4.w};
-      float pr[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float lp = lp_of(sp, 4 * h + r);
-        const float a1 = __builtin_amdgcn_exp2f(lp);
-        const float a = a_of(sp, 4 * h + r);
-        pr[r] = a1 * (a * (k1 * fmaf(lp, LN2, Lr[r]) + (k2 * y[r] - k3)));
-      }
-      row16_sum4(pr[0], pr[1], pr[2], pr[3]);
-      if (fr == 0) *(float4*)(Rw + 32 * sp + 8 * g + 4 * h) = make_float4(pr[0], pr[1], pr[2], pr[3]);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (NTT > 1) {
-      flag_publish(flagR + wid * 4, epoch);
-#pragma unroll
-      for (int q = 0; q < NTT; ++q) flag_wait(flagR + (w0 + q) * 4, epoch);
-    }
-    // ---- pass b: dS = dnum A + a1 (da1 - rd), over the log-probabilities in place ----
-#pragma unroll
-    for (int s = 0; s < NS; ++s) { opaque(lpv[s]); opaque(af[s]); }
-#pragma unroll
-    for (int sp = 0; sp < NS; ++sp) {
+    const int fl0 = epoch * 8 + 1;                          // this epoch's flag values: fl0 + sp, sp < NS <= 7
+    // NTT > 1: block sp's row sums from the caption's waves (in wave order, whoever reads), ds from the block's da1 kept in registers
+    auto finish_block = [&](int sp, const float (&da)[8]) __attribute__((always_inline)) {
+      flag_wait_group<NTT>(flagR + w0 * 4, lane, fl0 + sp);
       float ds[8];
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
-        const int rt = 2 * sp + h;
-        if (rt < NRTA) {
-          const float4 L4 = *(const float4*)(Lw + 32 * sp + 8 * g + 4 * h);
+        if (2 * sp + h < NRTA) {
           float rd[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
           for (int q = 0; q < NTT; ++q) {
             const float4 v = *(const float4*)(Rall + (w0 + q) * GR + 32 * sp + 8 * g + 4 * h);
             rd[0] += v.x; rd[1] += v.y; rd[2] += v.z; rd[3] += v.w;
           }
-          const f32x4_t y = y_tile_now(rt);
-          const float Lr[4] = {L4.x, L4.y, L4.z, L4.w};
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const float lp = lp_of(sp, 4 * h + r);
-            const float a1 = __builtin_amdgcn_exp2f(lp);
+            const float a1 = __builtin_amdgcn_exp2f(lp_of(sp, 4 * h + r));
             const float a = a_of(sp, 4 * h + r);
-            const float da1 = a * (k1 * fmaf(lp, LN2, Lr[r]) + (k2 * y[r] - k3));
-            ds[4 * h + r] = dn * a + a1 * (da1 - rd[r]);
+            ds[4 * h + r] = dn * a + a1 * (da[4 * h + r] - rd[r]);
           }
         } else {
 #pragma unroll
@@ -381,6 +376,58 @@ __global__ __launch_bounds__(1024) void local_pair3_kernel(Pair3Args p) {
       }
       if (32 * sp + 31 < HW || 32 * sp + 8 * g < pw)
         *(uint4*)(p.dS + off0 + 32 * sp) = make_uint4(pack2bf(ds[0], ds[1]), pack2bf(ds[2], ds[3]), pack2bf(ds[4], ds[5]), pack2bf(ds[6], ds[7]));
+      __builtin_amdgcn_sched_barrier(0);
+    };
+#pragma unroll
+    for (int s = 0; s < NS; ++s) { opaque(lpv[s]); opaque(af[s]); }
+    float dap[8];                                           // da1 of the block that waits for its row sums (NTT > 1)
+#pragma unroll
+    for (int sp = 0; sp < NS; ++sp) {
+      float dac[8], ds[8];
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int rt = 2 * sp + h;
+        if (rt < NRTA) {
+          const float4 L4 = *(const float4*)(Lw + 32 * sp + 8 * g + 4 * h);
+          const f32x4_t y = y_tile_now(rt);
+          const float Lr[4] = {L4.x, L4.y, L4.z, L4.w};
+          float pr[4], a1[4];
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float lp = lp_of(sp, 4 * h + r);
+            a1[r] = __builtin_amdgcn_exp2f(lp);
+            const float a = a_of(sp, 4 * h + r);
+            const float da1 = a * (k1 * fmaf(lp, LN2, Lr[r]) + (k2 * y[r] - k3));
+            dac[4 * h + r] = da1;
+            pr[r] = a1[r] * da1;
+          }
+          row16_sum4(pr[0], pr[1], pr[2], pr[3]);
+          if (NTT > 1) {
+            if (fr == 0) *(float4*)(Rw + 32 * sp + 8 * g + 4 * h) = make_float4(pr[0], pr[1], pr[2], pr[3]);
+          } else {                                          // the caption's only wave: the row sum is rd, in every lane
+#pragma unroll
+            for (int r = 0; r < 4; ++r) ds[4 * h + r] = dn * a_of(sp, 4 * h + r) + a1[r] * (dac[4 * h + r] - pr[r]);
+          }
+        } else {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) { dac[4 * h + r] = 0.f; ds[4 * h + r] = 0.f; }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      if (NTT > 1) {
+        flag_publish(flagR + wid * 4, fl0 + sp);
+        if (sp > 0) {
+          opaque(lpv[sp - 1]); opaque(af[sp - 1]);      // a1 and a again from the packed tiles: kept as fp32 they cost spills
+          finish_block(sp - 1, dap);
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) dap[e] = dac[e];
+      } else if (32 * sp + 31 < HW || 32 * sp + 8 * g < pw)
+        *(uint4*)(p.dS + off0 + 32 * sp) = make_uint4(pack2bf(ds[0], ds[1]), pack2bf(ds[2], ds[3]), pack2bf(ds[4], ds[5]), pack2bf(ds[6], ds[7]));
+    }
+    if (NTT > 1) {
+      opaque(lpv[NS - 1]); opaque(af[NS - 1]);
+      finish_block(NS - 1, dap);
     }
   }
 }
