@@ -278,6 +278,12 @@ int medmoe_stream_fork(hipStream_t from, hipStream_t to);
 /* fused clip + torch.optim.Adam step + bf16 down-cast (med-moe_pretraining.yaml:7-11) */
 int medmoe_adam_step(float* p, const float* g, float* m, float* v, void* p_bf16, long long n, double lr, double beta1, double beta2, double eps, double weight_decay, int step, const float* grad_normsq, float max_norm, float grad_scale, hipStream_t stream);
 
+/* the same step with parameter groups, one launch per arena: the arena is cut into n_runs contiguous runs (run_end: device int64[n_runs],
+   ascending, last == n; a boundary may fall on any element), run r steps with (lr / bc1) * run_lr_mult[r] and decays with
+   weight_decay * run_wd_mult[r] (device float[n_runs] each).  decoupled 0 = torch.optim.Adam (L2 decay added to the gradient, the update
+   of medmoe_adam_step), 1 = torch.optim.AdamW (p *= 1 - lr_r * wd_r, then Adam on the undecayed gradient).  No atomics. */
+int medmoe_adam_groups_step(float* p, const float* g, float* m, float* v, void* p_bf16, long long n, const long long* run_end, const float* run_lr_mult, const float* run_wd_mult, int n_runs, double lr, double beta1, double beta2, double eps, double weight_decay, int decoupled, int step, const float* grad_normsq, float max_norm, float grad_scale, hipStream_t stream);
+
 /* fp32 -> bf16 copy of the master weights */
 int medmoe_cast_bf16(const float* src, void* dst, long long n, hipStream_t stream);
 

@@ -2,7 +2,7 @@
 configs/model/med-moe.yaml, configs/model/med-moe_pretraining.yaml; ViT/MoE geometry per
 BASELINE.json configs)."""
 from dataclasses import dataclass
-from typing import List
+from typing import List, Tuple
 
 
 @dataclass
@@ -63,6 +63,17 @@ class MedMoEConfig:
     lr: float = 5e-5
     weight_decay: float = 0.0
     clip: float = 0.25
+    # optimiser family and parameter groups (medmoe_amd/optim_groups.py; the defaults are the experiment's torch.optim.Adam, ungrouped):
+    # "adamw" = decoupled weight decay; no_decay: fnmatch patterns over parameter names that get no decay; no_decay_1d: no decay for
+    # biases, LayerNorms and the position / class / token-type / relative-position embeddings; text_lr_mult: learning-rate multiplier
+    # of the trainable text tower; layer_decay: depth-wise learning-rate decay (BEiT convention), 1.0 = off
+    optimizer: str = "adam"
+    adam_betas: Tuple[float, float] = (0.9, 0.999)
+    adam_eps: float = 1e-8
+    no_decay: Tuple[str, ...] = ()
+    no_decay_1d: bool = False
+    text_lr_mult: float = 1.0
+    layer_decay: float = 1.0
 
     @property
     def n_patch(self) -> int:
@@ -86,6 +97,17 @@ class MedMoEConfig:
         return [max(1, (L * (s + 1)) // 4) for s in range(4)]
 
     def validate(self):
+        if self.optimizer not in ("adam", "adamw"):
+            raise ValueError(f"optimizer must be 'adam' or 'adamw', got {self.optimizer!r}")
+        if len(tuple(self.adam_betas)) != 2 or not all(0.0 <= float(b) < 1.0 for b in self.adam_betas):
+            raise ValueError(f"adam_betas must be two values in [0, 1), got {self.adam_betas}")
+        if not float(self.adam_eps) > 0.0:
+            raise ValueError(f"adam_eps must be > 0, got {self.adam_eps}")
+        for key in ("text_lr_mult", "layer_decay"):
+            if not float(getattr(self, key)) > 0.0:
+                raise ValueError(f"{key} must be > 0, got {getattr(self, key)}")
+        if isinstance(self.no_decay, str) or not all(isinstance(p, str) for p in self.no_decay):
+            raise ValueError(f"no_decay must be a list of name patterns, got {self.no_decay!r}")
         for key in ("text_hidden_dropout", "text_attn_dropout"):
             if not 0.0 <= float(getattr(self, key)) < 1.0:
                 raise ValueError(f"{key} must be in [0, 1), got {getattr(self, key)}")

@@ -76,6 +76,17 @@ extern "C" int medmoe_sumsq_det(const float* g, long long n, float* out, float* 
 // Update in torch.optim.Adam's operation order (exp_avg.lerp_, exp_avg_sq.mul_().addcmul_(), sqrt / sqrt(bc2) + eps,
 // addcdiv_ with step size lr / bc1); the scalars 1-b1, 1-b2, sqrt(bc2), lr/bc1 are formed in double on the host, as torch
 // forms them in Python floats (1 - 0.999f in fp32 is off by 1.3e-5 relative: the second moment would inherit that).
+// One element of the update, shared by adam_kernel and adam_groups_kernel so that both compile the same expressions (operation order and
+// the contraction the compiler applies to them): `wd` is the L2 decay added to the gradient, 0 for the decoupled form.
+__device__ __forceinline__ void adam_update(float& p, float g, float& m, float& v, float coef, float wd, float b2, float omb1, float omb2,
+                                            float eps, float step_size, float bc2_sqrt) {
+  const float gr = g * coef + wd * p;
+  m = m + omb1 * (gr - m);
+  v = b2 * v + omb2 * gr * gr;
+  const float denom = sqrtf(v) / bc2_sqrt + eps;
+  p -= step_size * (m / denom);
+}
+
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, bf16_t* __restrict__ p16, long long n,
                                                    float b2, float omb1, float omb2, float eps, float wd, float step_size,
@@ -93,13 +104,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
     float4 mm = *(float4*)(m + i * 4), vv = *(float4*)(v + i * 4);
     float* P = (float*)&pp; const float* G = (const float*)&gg; float* M = (float*)&mm; float* V = (float*)&vv;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float gr = G[e] * coef + wd * P[e];
-      M[e] = M[e] + omb1 * (gr - M[e]);
-      V[e] = b2 * V[e] + omb2 * gr * gr;
-      const float denom = sqrtf(V[e]) / bc2_sqrt + eps;
-      P[e] -= step_size * (M[e] / denom);
-    }
+    for (int e = 0; e < 4; ++e) adam_update(P[e], G[e], M[e], V[e], coef, wd, b2, omb1, omb2, eps, step_size, bc2_sqrt);
     *(float4*)(p + i * 4) = pp; *(float4*)(m + i * 4) = mm; *(float4*)(v + i * 4) = vv;
     if (p16) { uint2 o; o.x = pack2bf(P[0], P[1]); o.y = pack2bf(P[2], P[3]); *(uint2*)(p16 + i * 4) = o; }
   }
@@ -115,6 +120,86 @@ extern "C" int medmoe_adam_step(float* p, const float* g, float* m, float* v, vo
   hipLaunchKernelGGL(adam_kernel, dim3(grid), dim3(256), 0, stream, p, g, m, v, (bf16_t*)p_bf16, n, (float)beta2,
                      (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, (float)weight_decay, (float)(lr / bc1),
                      (float)sqrt(bc2), grad_normsq, max_norm, grad_scale);
+  return mm_check_launch();
+}
+
+// ---------------------------------------------------------------------------------------------
+// The same step with parameter groups.  The arena is cut into `n_runs` contiguous runs (run r = elements [run_end[r-1], run_end[r]),
+// run_end ascending, run_end[n_runs-1] == n); run r steps with step_size * lr_mult[r] and decays with wd * wd_mult[r].  decoupled = 0:
+// adam_kernel's update (L2 decay added to the gradient); decoupled = 1: torch.optim.AdamW's single-tensor order, p *= 1 - lr_r * wd_r
+// (formed in double and rounded once, as torch forms the Python float it hands to mul_), then Adam on the undecayed gradient.
+// The table is static between regroupings and lives on the device; a workgroup stages it in LDS (up to ADAM_LDS_RUNS runs, larger tables
+// are searched where they are: a few KB that stay in the caches) and every lane finds the run of its float4's first element by bisection.
+// A run boundary may fall on any element (the members of an arena group are stored back to back), so the run is followed per element
+// inside the float4; the four arrays are still moved 16 bytes per lane.  No atomics: the result is a function of the inputs only.
+// ---------------------------------------------------------------------------------------------
+#define ADAM_LDS_RUNS 1024
+
+template <bool LDS>
+__global__ __launch_bounds__(256) void adam_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                          float* __restrict__ v, bf16_t* __restrict__ p16, long long n,
+                                                          const long long* __restrict__ run_end, const float* __restrict__ run_lr,
+                                                          const float* __restrict__ run_wd, int n_runs, float b2, float omb1, float omb2,
+                                                          float eps, float wd, float step_size, float bc2_sqrt, double lr_d, double wd_d,
+                                                          int decoupled, const float* __restrict__ normsq, float max_norm,
+                                                          float grad_scale) {
+  __shared__ long long s_end[LDS ? ADAM_LDS_RUNS : 1];
+  __shared__ float s_lr[LDS ? ADAM_LDS_RUNS : 1], s_wd[LDS ? ADAM_LDS_RUNS : 1];
+  if (LDS) {
+    for (int r = threadIdx.x; r < n_runs; r += 256) { s_end[r] = run_end[r]; s_lr[r] = run_lr[r]; s_wd[r] = run_wd[r]; }
+    __syncthreads();
+  }
+  const long long* ends = LDS ? s_end : run_end;
+  const float* lrm = LDS ? s_lr : run_lr;
+  const float* wdm = LDS ? s_wd : run_wd;
+  float coef = grad_scale;
+  if (normsq && max_norm > 0.f) {
+    const float nrm = sqrtf(*normsq) * grad_scale;
+    coef *= fminf(1.f, max_norm / (nrm + 1e-6f));
+  }
+  const int last = n_runs - 1;
+  const long long n4 = n >> 2;
+  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+    float4 pp = *(float4*)(p + i * 4);
+    const float4 gg = *(const float4*)(g + i * 4);
+    float4 mm = *(float4*)(m + i * 4), vv = *(float4*)(v + i * 4);
+    float* P = (float*)&pp; const float* G = (const float*)&gg; float* M = (float*)&mm; float* V = (float*)&vv;
+    const long long e0 = i * 4;
+    int r = 0, hi = last;                                         // first run whose end lies behind e0 (r <= last whatever the table holds)
+    while (r < hi) {
+      const int mid = (r + hi) >> 1;
+      if (ends[mid] > e0) hi = mid; else r = mid + 1;
+    }
+    long long end = ends[r];
+    float ss = step_size * lrm[r], wdr = wd * wdm[r], keep = 1.f;
+    if (decoupled) { keep = (float)(1.0 - (lr_d * (double)lrm[r]) * (wd_d * (double)wdm[r])); wdr = 0.f; }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      if (e0 + e >= end && r < last) {                            // a boundary inside this float4: move on (runs may be one element long)
+        do { ++r; end = ends[r]; } while (e0 + e >= end && r < last);
+        ss = step_size * lrm[r]; wdr = wd * wdm[r];
+        if (decoupled) { keep = (float)(1.0 - (lr_d * (double)lrm[r]) * (wd_d * (double)wdm[r])); wdr = 0.f; }
+      }
+      if (decoupled) P[e] *= keep;
+      adam_update(P[e], G[e], M[e], V[e], coef, wdr, b2, omb1, omb2, eps, ss, bc2_sqrt);
+    }
+    *(float4*)(p + i * 4) = pp; *(float4*)(m + i * 4) = mm; *(float4*)(v + i * 4) = vv;
+    if (p16) { uint2 o; o.x = pack2bf(P[0], P[1]); o.y = pack2bf(P[2], P[3]); *(uint2*)(p16 + i * 4) = o; }
+  }
+}
+
+extern "C" int medmoe_adam_groups_step(float* p, const float* g, float* m, float* v, void* p_bf16, long long n, const long long* run_end,
+                                       const float* run_lr_mult, const float* run_wd_mult, int n_runs, double lr, double beta1,
+                                       double beta2, double eps, double weight_decay, int decoupled, int step, const float* grad_normsq,
+                                       float max_norm, float grad_scale, hipStream_t stream) {
+  if (!p || !g || !m || !v || !run_end || !run_lr_mult || !run_wd_mult || n <= 0 || n_runs < 1 || step < 1) return MM_ERR_ARG;
+  if (n % 4) return MM_ERR_SHAPE;   // flat buffers are padded to a multiple of 4 by the host
+  const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+  const int grid = (int)min((n / 4 + 255) / 256, (long long)256 * 8);
+  auto kern = n_runs <= ADAM_LDS_RUNS ? adam_groups_kernel<true> : adam_groups_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, stream, p, g, m, v, (bf16_t*)p_bf16, n, run_end, run_lr_mult, run_wd_mult, n_runs,
+                     (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, (float)weight_decay, (float)(lr / bc1),
+                     (float)sqrt(bc2), lr, weight_decay, decoupled ? 1 : 0, grad_normsq, max_norm, grad_scale);
   return mm_check_launch();
 }
 

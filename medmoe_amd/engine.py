@@ -129,6 +129,7 @@ class Engine:
             from .text_params import TextStore
             self.tstore = TextStore(cfg, self.device, self.params.text)
             self.params.text = self.tstore.as_dict()             # views of the flat buffers: an optimiser step updates them in place
+        self.apply_optimizer_groups()
         self.HWp, self.Tp, self.GW = ops.local_geometry(cfg.n_patch, cfg.max_len)
         # LDS-tiled pair kernels exist for 64 / 208 / 256 regions; any other geometry (576 regions of ViT-L/14 at 336 px) runs
         # the generic GEMM formulation (medmoe_amd/local_generic.py)
@@ -159,6 +160,25 @@ class Engine:
         # optimiser (its bias-correction scalars are host values).  Single rank, frozen text tower.
         self.use_graph = os.environ.get("MEDMOE_GRAPH", "0") == "1"
         self._graph = None
+
+    def optimizer_stores(self) -> Dict[str, object]:
+        """kind (medmoe_amd.optim_groups) -> the arenas this engine steps."""
+        out = {"vit": self.params}
+        if self.tstore is not None:
+            out["text"] = self.tstore
+        return out
+
+    def apply_optimizer_groups(self):
+        """cfg.no_decay / no_decay_1d / text_lr_mult / layer_decay -> the run tables of the stores (uploaded here, once; the default rule
+        set clears them and the step stays medmoe_adam_step)."""
+        from .optim_groups import GroupRules, apply_rules
+        apply_rules(self.optimizer_stores(), GroupRules.from_config(self.cfg))
+
+    def set_optimizer_groups(self, **rules):
+        """Change the rule set (any of no_decay, no_decay_1d, text_lr_mult, layer_decay) and regroup the stores."""
+        from .optim_groups import set_rules
+        set_rules(self.cfg, rules)
+        self.apply_optimizer_groups()
 
     def set_deterministic(self, flag: bool):
         """Switch deterministic mode on or off; refuses the combinations it is not built for.  The scratch buffers are allocated on first
@@ -1050,17 +1070,19 @@ class Engine:
                 "g_loss": lp[2] / c.w_global, "l_loss": lp[3] / c.w_local}
 
     def optimizer_step(self, lr: Optional[float] = None):
-        """clip_grad_norm_(cfg.clip) + torch.optim.Adam(lr, weight_decay), fused, on the gradients the stores hold; the working copies
-        follow.  ONE clip norm over both towers' gradients when the text tower trains, as clip_grad_norm_ over all parameters computes it."""
+        """clip_grad_norm_(cfg.clip) + torch.optim.Adam(lr, weight_decay) (cfg.optimizer = "adamw": torch.optim.AdamW; cfg.adam_betas /
+        adam_eps; the parameter groups the stores carry), fused, on the gradients the stores hold; the working copies follow.  ONE clip
+        norm over both towers' gradients when the text tower trains, as clip_grad_norm_ over all parameters computes it."""
         c, image, text = self.cfg, self.params, self.tstore if self.train_text else None
         lr = c.lr if lr is None else lr
         text_part = text.sumsq() if text is not None else None
         total = image.sumsq()
         if text is not None:
             total.add_(text_part)
-        image.adam_step(total, lr, c.weight_decay, c.clip)
+        kw = dict(betas=tuple(c.adam_betas), eps=c.adam_eps, decoupled=c.optimizer == "adamw")
+        image.adam_step(total, lr, c.weight_decay, c.clip, **kw)
         if text is not None:
-            text.adam_step(total, lr, c.weight_decay, c.clip)
+            text.adam_step(total, lr, c.weight_decay, c.clip, **kw)
 
     # ------------------------------------------------------------------------------------------
     # evaluation (medmoe_module.py:114-134 validation_step / test_step: model_step without a backward)

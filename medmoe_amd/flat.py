@@ -2,7 +2,8 @@
 gradient buffer `g32` of the same layout (one memset zeroes every gradient of a step, one all-reduce averages them), Adam's `m` / `v`, a bf16
 working copy `p16` in the nn.Linear [out, in] layout and a second one, `p16t`, holding every GEMM weight transposed ([in, out]: dgrad runs on
 the same NT kernel as forward).  `refresh()` is two kernels (cast + batched transpose) whatever the number of parameters, the clip norm is
-summed in a fixed order (`sumsq`), and clip + Adam + the bf16 copy are one launch (`adam_step`).
+summed in a fixed order (`sumsq`), and clip + Adam + the bf16 copy are one launch (`adam_step`) - also with parameter groups
+(`set_param_groups`: contiguous runs of the arena with their own learning-rate / weight-decay multipliers) and AdamW.
 
 The stores say what is specific to them: `ParamStore` (ViT tower + MoE: its spec list, seeded init, the 8-bit expert copies) and
 `TextStore` (trainable text tower) build the arena from their spec lists; `FlatStore` below takes any name -> tensor dict (Swin tower,
@@ -56,6 +57,9 @@ class FlatArena:
             self.shapes[a] = (sum(self.shapes[m][0] for m in ms),) + self.shapes[ms[0]][1:]
             self.offsets[a] = self.offsets[ms[0]]
         self.numel = off
+        self.groups: Dict[str, List[str]] = {a: list(ms) for a, ms in groups}
+        self.runs = None                                            # parameter groups: [(end, lr_mult, wd_mult)] in storage order, None = none set
+        self._run_table = self._one_run = None                      # the device form of `runs` / of the one-run table ((numel, 1, 1))
         self._views: Dict[tuple, tuple] = {}
         z = lambda dt: torch.zeros(off, device=dev, dtype=dt)
         self.p32, self.g32, self.p16, self.p16t = z(torch.float32), z(torch.float32), z(torch.bfloat16), z(torch.bfloat16)
@@ -141,14 +145,55 @@ class FlatArena:
         ops.call("sumsq_det", self.g32, self.numel, self.normsq, self.norm_scratch)
         return self.normsq
 
-    def adam_step(self, normsq_total: torch.Tensor, lr: float, weight_decay: float, clip: float, grad_scale: float = 1.0):
+    # -- parameter groups: contiguous runs of the arena with their own learning-rate and weight-decay multipliers ---------------------------
+    def _upload_runs(self, runs):
+        dev = self.device
+        return (torch.tensor([r[0] for r in runs], device=dev, dtype=torch.int64), torch.tensor([r[1] for r in runs], device=dev, dtype=torch.float32),
+                torch.tensor([r[2] for r in runs], device=dev, dtype=torch.float32))
+
+    def set_param_groups(self, assign: Dict[str, Tuple[float, float]]):
+        """assign: entry name or group alias -> (lr_mult, wd_mult); an alias covers all its members, a member's own entry wins over its
+        alias, everything unnamed gets (1, 1).  The arena is cut into runs in storage order: adjacent entries of equal multipliers are one
+        run, an entry's padding belongs to its run (so to the run of the entry before the next one), and because group members lie back to
+        back a boundary may fall on any element.  The table goes to the device once, here: a step reads nothing from the host."""
+        for name in assign:
+            if name not in self.shapes:
+                raise KeyError(f"set_param_groups: unknown parameter or group {name!r}")
+        alias_of = {m: a for a, ms in self.groups.items() for m in ms}
+        entries = sorted((o, n) for n, o in self.offsets.items() if n not in self.groups)
+        runs: List[Tuple[int, float, float]] = []
+        for k, (_, name) in enumerate(entries):
+            lm, wm = assign.get(name, assign.get(alias_of.get(name), (1.0, 1.0)))
+            end = entries[k + 1][0] if k + 1 < len(entries) else self.numel
+            if runs and runs[-1][1:] == (float(lm), float(wm)):
+                runs[-1] = (end, float(lm), float(wm))
+            else:
+                runs.append((end, float(lm), float(wm)))
+        self.runs = runs
+        self._run_table = self._upload_runs(runs)
+
+    def clear_param_groups(self):
+        self.runs = self._run_table = None
+
+    def adam_step(self, normsq_total: torch.Tensor, lr: float, weight_decay: float, clip: float, grad_scale: float = 1.0, *,
+                  betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, decoupled: bool = False):
         """clip (against `normsq_total`, the squared norm over ALL arenas of the model, as clip_grad_norm_ over all parameters computes it)
-        + torch.optim.Adam's update (betas 0.9 / 0.999, eps 1e-8, L2 weight decay) on the fp32 master, the bf16 copy written by the same
-        kernel; the derived copies follow.  Gradients must be in THIS arena's g32 (no new_grad_arena() since the backward)."""
+        + torch.optim.Adam's update (L2 weight decay; decoupled: torch.optim.AdamW's) on the fp32 master, the bf16 copy written by the same
+        kernel; the derived copies follow.  Without parameter groups, with Adam's default betas / eps and L2 decay this is medmoe_adam_step;
+        anything else is ONE medmoe_adam_groups_step over the arena's run table (a single run when no groups are set).  Gradients must be
+        in THIS arena's g32 (no new_grad_arena() since the backward)."""
         m, v = self.adam_state()
         self.step_count += 1
-        ops.call("adam_step", self.p32, self.g32, m, v, self.p16, self.numel, lr, 0.9, 0.999, 1e-8, weight_decay, self.step_count,
-                 normsq_total, clip, grad_scale)
+        b1, b2 = float(betas[0]), float(betas[1])
+        if self.runs is None and not decoupled and (b1, b2) == (0.9, 0.999) and float(eps) == 1e-8:
+            ops.call("adam_step", self.p32, self.g32, m, v, self.p16, self.numel, lr, 0.9, 0.999, 1e-8, weight_decay, self.step_count,
+                     normsq_total, clip, grad_scale)
+        else:
+            if self.runs is None and self._one_run is None:
+                self._one_run = self._upload_runs([(self.numel, 1.0, 1.0)])
+            ends, lrm, wdm = self._run_table if self.runs is not None else self._one_run
+            ops.call("adam_groups_step", self.p32, self.g32, m, v, self.p16, self.numel, ends, lrm, wdm, ends.numel(), lr, b1, b2, eps,
+                     weight_decay, 1 if decoupled else 0, self.step_count, normsq_total, clip, grad_scale)
         self._derive()
 
 

@@ -498,7 +498,7 @@ _SIGS = {
     "gemm_tn_cols_det": "pipipiiiiilllilpl", "gemm_tn_gram_det": "piplipiiiill", "scale_attn_bwd_det": "ppppppppppiipppppiiipipl",
     "router_bwd_det": "pppppppfpppiiiip", "ce_strided_det": "ppiilliffipp", "soft_xent_strided_det": "pppiillffffipp", "hardneg_strided_det": "ppiillffipp",
     "cos_scale_bwd_det": "ppppppiif",
-    "sumsq": "plp", "sumsq_det": "plpp", "adam_step": "pppppldddddipff", "cast_bf16": "ppl", "transpose_many": "pppii",
+    "sumsq": "plp", "sumsq_det": "plpp", "adam_step": "pppppldddddipff", "adam_groups_step": "ppppplpppidddddiipff", "cast_bf16": "ppl", "transpose_many": "pppii",
 }
 
 
@@ -573,6 +573,7 @@ _COSTS = {
     "local_scores_t": _cost_scores, "local_pair3": _cost_pair3, "local_pair3_wgrad": _cost_pair3, "local_sim_fwd": _cost_local_sim, "gemm_tn_cols": _cost_tn_cols, "gemm_tn_gram": _cost_tn_gram,
     "gemm_tn_cols_det": _cost_tn_cols, "gemm_tn_gram_det": _cost_tn_gram,
     "adam_step": lambda a: ("adam_kernel", 34.0 * a[5], "byte"),                                   # p, g, m, v read; p, m, v, bf16 copy written
+    "adam_groups_step": lambda a: ("adam_groups_kernel", 34.0 * a[5], "byte"),                     # the same traffic: the run table stays on chip
     "scale_attn_bwd": lambda a: ("scale_attn_bwd_kernel", 2.0 * a[17] * (4 * (2 * a[18] + 2 * a[19]) + 2 * a[18]), "byte"),    # G, dG, H1, dH1 x 4 scales + eout, d_img_l rows
     "scale_attn_bwd_det": lambda a: ("scale_attn_bwd_kernel<DET> + scale_attn_bwd_reduce_kernel", 2.0 * a[17] * (4 * (2 * a[18] + 2 * a[19]) + 2 * a[18]), "byte"),
     "scale_attn_fwd": lambda a: ("scale_attn_fwd_kernel", 2.0 * a[8] * (4 * (a[9] + a[10]) + a[9]), "byte"),

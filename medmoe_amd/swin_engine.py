@@ -48,6 +48,24 @@ class SwinEngine:
         self._gsim = None
         self._normsq = torch.zeros(1, device=self.device, dtype=F32)
         self._keep = None
+        self.apply_optimizer_groups()
+
+    def optimizer_stores(self) -> Dict[str, object]:
+        """kind (medmoe_amd.optim_groups) -> the arenas this engine steps."""
+        out = {"swin_tower": self.enc.tower.store, "swin_moe": self.enc.store}
+        if self.train_text:
+            out["text"] = self.eng.tstore
+        return out
+
+    def apply_optimizer_groups(self):
+        """The configuration's rule set -> the run tables of the two Swin arenas (and the text store's), uploaded here."""
+        from .optim_groups import GroupRules, apply_rules
+        apply_rules(self.optimizer_stores(), GroupRules.from_config(self.cfg))
+
+    def set_optimizer_groups(self, **rules):
+        from .optim_groups import set_rules
+        set_rules(self.cfg, rules)
+        self.apply_optimizer_groups()
 
     def _local(self, B: int, HW: int, T: int, D: int) -> GenericLocalLoss:
         if self._loc is None or (self._loc.B, self._loc.HW, self._loc.T, self._loc.D) != (B, HW, T, D):
@@ -156,10 +174,11 @@ class SwinEngine:
         torch.add(st_t.sumsq(), st_m.sumsq(), out=self._normsq)
         if self.train_text:
             self._normsq.add_(self.eng.tstore.sumsq())
-        st_t.adam_step(self._normsq, lr, c.weight_decay, c.clip)
-        st_m.adam_step(self._normsq, lr, c.weight_decay, c.clip)
+        kw = dict(betas=tuple(c.adam_betas), eps=c.adam_eps, decoupled=c.optimizer == "adamw")
+        st_t.adam_step(self._normsq, lr, c.weight_decay, c.clip, **kw)
+        st_m.adam_step(self._normsq, lr, c.weight_decay, c.clip, **kw)
         if self.train_text:
-            self.eng.tstore.adam_step(self._normsq, lr, c.weight_decay, c.clip)
+            self.eng.tstore.adam_step(self._normsq, lr, c.weight_decay, c.clip, **kw)
         self.enc.tower.refresh(cast=False)                          # patch-embedding pad form, bias tables
 
     def eval_step(self, batch: Dict[str, torch.Tensor]):

@@ -22,12 +22,15 @@ def _get(cfg: Any, key: str, default=None):
 
 class MedMoEPretrainingLightningModule(_Base):
     def __init__(self, model: nn.Module, loss: Any, optimizer: Any = None, scheduler: Any = None,
-                 compile: bool = False, num_classes: int = 5, fused_step: bool = False):
+                 compile: bool = False, num_classes: int = 5, fused_step: bool = False, optimizer_groups: Any = None):
         """`fused_step` (MI355X build, `model.fused_step` in the config tree): training steps run `Engine.train_step` - the hand-scheduled
         forward / losses / backward with the embedding all-gather, the reduce-scatter of the gathered-key gradients, the per-layer
         gradient all-reduce overlapped with backward and the fused clip + Adam - instead of torch autograd + a torch optimizer.
         Same losses, same update rule (tests/test_fused_module_gpu.py); needs the ViT image tower, the two GLoRIA losses (or their
-        Soft variants) and torch.optim.Adam in the config, and refuses anything else at construction."""
+        Soft variants) and torch.optim.Adam or torch.optim.AdamW in the config, and refuses anything else at construction.
+        `optimizer_groups` (fused step only): the rule set of medmoe_amd.optim_groups - no_decay (name patterns), no_decay_1d,
+        text_lr_mult, layer_decay - that cuts the engine's flat stores into parameter groups; the scheduler keeps driving the base
+        learning rate, the groups multiply it."""
         super().__init__()
         self.model = model
         self.loss_cfg = loss
@@ -40,6 +43,10 @@ class MedMoEPretrainingLightningModule(_Base):
         self.soft_label = bool(_get(loss, "soft_label", False))                 # :207-210: the reference loads `tool_bert` here
         self.fused_step = bool(fused_step)
         self._fused_acc, self._fused_clip, self._fused_opt = 1, None, None
+        self._optimizer_groups = dict(optimizer_groups) if optimizer_groups else {}
+        if self._optimizer_groups and not self.fused_step:
+            raise NotImplementedError("optimizer_groups needs fused_step=true: the autograd path steps ONE flat parameter, which cannot be "
+                                      "cut into groups (the fused step groups runs of the engine's flat stores)")
         if self.fused_step:
             self.automatic_optimization = False                                  # Lightning: manual optimisation (the engine steps itself)
             self._configure_engine()
@@ -115,11 +122,10 @@ class MedMoEPretrainingLightningModule(_Base):
         if _get(self.loss_cfg, "agg", "sum") != "sum":
             raise NotImplementedError("fused_step: only loss.agg = 'sum' (the reference default)")
         opt = self._optimizer
-        if not isinstance(opt, functools.partial) or opt.func is not torch.optim.Adam or opt.args \
-                or set(opt.keywords) - {"lr", "weight_decay", "betas", "eps"} \
-                or tuple(opt.keywords.get("betas", (0.9, 0.999))) != (0.9, 0.999) or float(opt.keywords.get("eps", 1e-8)) != 1e-8:
-            raise NotImplementedError("fused_step fuses torch.optim.Adam(lr, weight_decay) with betas (0.9, 0.999), eps 1e-8 (the experiment's "
-                                      "optimizer, med-moe_pretraining.yaml:7-11)")
+        if not isinstance(opt, functools.partial) or opt.func not in (torch.optim.Adam, torch.optim.AdamW) or opt.args \
+                or set(opt.keywords) - {"lr", "weight_decay", "betas", "eps"}:
+            raise NotImplementedError("fused_step fuses torch.optim.Adam or torch.optim.AdamW (lr, weight_decay, betas, eps; the experiment's "
+                                      "optimizer is Adam, med-moe_pretraining.yaml:7-11); no other optimizer and no other keyword")
         c = eng.cfg
         c.temp1, c.temp2 = float(_get(self.loss_cfg, "temp1", 4.0)), float(_get(self.loss_cfg, "temp2", 5.0))
         c.temp3 = float(_get(self.loss_cfg, "temp3", 10.0))
@@ -127,7 +133,16 @@ class MedMoEPretrainingLightningModule(_Base):
         c.soft_label = self.soft_label
         c.local_loss_global = bool(_get(self.loss_cfg, "local_loss_global", False))
         c.threshold0, c.threshold1 = float(_get(self.loss_cfg, "threshold0", 0.98)), float(_get(self.loss_cfg, "threshold1", 0.97))
-        c.lr, c.weight_decay = float(opt.keywords.get("lr", 1e-3)), float(opt.keywords.get("weight_decay", 0.0))
+        adamw = opt.func is torch.optim.AdamW
+        c.lr = float(opt.keywords.get("lr", 1e-3))
+        c.weight_decay = float(opt.keywords.get("weight_decay", 1e-2 if adamw else 0.0))      # the two classes' own defaults
+        c.optimizer = "adamw" if adamw else "adam"
+        c.adam_betas = tuple(float(b) for b in opt.keywords.get("betas", (0.9, 0.999)))
+        c.adam_eps = float(opt.keywords.get("eps", 1e-8))
+        from medmoe_amd.optim_groups import set_rules
+        set_rules(c, self._optimizer_groups)                         # validates the rule set and the optimiser keys above
+        if getattr(self.model, "swin", None) is None:                # arch = swin_t: the SwinEngine groups its own arenas when it is built
+            eng.apply_optimizer_groups()
 
     def set_deterministic(self, flag: bool):
         """trainer.deterministic: hand the flag to the HIP engine behind self.model (medmoe_amd.Engine.set_deterministic - every launch of
