@@ -284,6 +284,18 @@ int medmoe_adam_step(float* p, const float* g, float* m, float* v, void* p_bf16,
    of medmoe_adam_step), 1 = torch.optim.AdamW (p *= 1 - lr_r * wd_r, then Adam on the undecayed gradient).  No atomics. */
 int medmoe_adam_groups_step(float* p, const float* g, float* m, float* v, void* p_bf16, long long n, const long long* run_end, const float* run_lr_mult, const float* run_wd_mult, int n_runs, double lr, double beta1, double beta2, double eps, double weight_decay, int decoupled, int step, const float* grad_normsq, float max_norm, float grad_scale, hipStream_t stream);
 
+/* bf16 gradient exchange (no reference counterpart; what torch DDP's bf16_compress_hook does): out[i] = bf16(g[i] * scale), the product in
+   fp32, round to nearest even; NaN / Inf pass through, -0 stays -0.  16-byte accesses: both pointers 16-byte aligned (MM_ERR_ARG otherwise;
+   arena entries are padded to 8 elements), any n (a scalar tail covers n % 8).  6 B of HBM traffic per element. */
+int medmoe_grad_pack_bf16(const float* g, void* out_bf16, long long n, float scale, hipStream_t stream);
+/* medmoe_sumsq_det over a bf16 buffer (8-byte aligned): same grid, element order and partial-sum tree, so out[0] is bit-identical to
+   medmoe_sumsq_det on the fp32 up-cast of the buffer - the clip coefficient of the bf16-reduced gradient stays identical on every rank */
+int medmoe_sumsq_det_bf16(const void* g_bf16, long long n, float* out, float* scratch, hipStream_t stream);
+/* medmoe_adam_step / medmoe_adam_groups_step reading the gradient as bf16 (8-byte aligned, the arena's layout): the update is bit-identical
+   to theirs on float(g_bf16), and no pass widens the reduced gradient back to fp32.  No atomics. */
+int medmoe_adam_step_g16(float* p, const void* g_bf16, float* m, float* v, void* p_bf16, long long n, double lr, double beta1, double beta2, double eps, double weight_decay, int step, const float* grad_normsq, float max_norm, float grad_scale, hipStream_t stream);
+int medmoe_adam_groups_step_g16(float* p, const void* g_bf16, float* m, float* v, void* p_bf16, long long n, const long long* run_end, const float* run_lr_mult, const float* run_wd_mult, int n_runs, double lr, double beta1, double beta2, double eps, double weight_decay, int decoupled, int step, const float* grad_normsq, float max_norm, float grad_scale, hipStream_t stream);
+
 /* fp32 -> bf16 copy of the master weights */
 int medmoe_cast_bf16(const float* src, void* dst, long long n, hipStream_t stream);
 

@@ -35,6 +35,10 @@ class MedMoEConfig:
     # deterministic mode (trainer.deterministic): no launch of a step whose result depends on the order in which workgroups or waves arrive -
     # staged or single-writer forms of every weight-gradient GEMM, LayerNorm / scale-attention parameter gradient and loss sum
     deterministic: bool = False
+    # data parallelism: the number format of the gradient all-reduces.  "fp32": the flat fp32 gradient as it is.  "bf16": each arena is scaled
+    # by 1 / world and rounded to bf16 on the chip, the bf16 copy is summed over the ranks, and the clip norm and Adam read it -
+    # half the bytes on the wire.  Acts only where an all-reduce happens; a single process ignores it.  MEDMOE_GRAD_COMM=bf16 switches it on too.
+    grad_comm_dtype: str = "fp32"
     # MoE (swin.py:82-92)
     n_expert: int = 4
     top_k: int = 1
@@ -97,6 +101,8 @@ class MedMoEConfig:
         return [max(1, (L * (s + 1)) // 4) for s in range(4)]
 
     def validate(self):
+        if self.grad_comm_dtype not in ("fp32", "bf16"):
+            raise ValueError(f"grad_comm_dtype must be 'fp32' or 'bf16', got {self.grad_comm_dtype!r}")
         if self.optimizer not in ("adam", "adamw"):
             raise ValueError(f"optimizer must be 'adam' or 'adamw', got {self.optimizer!r}")
         if len(tuple(self.adam_betas)) != 2 or not all(0.0 <= float(b) < 1.0 for b in self.adam_betas):

@@ -4,6 +4,21 @@
 // fused bf16 down-cast of the updated weights, batched bf16 transposes (dgrad reads W^T), casts.
 #include "common.h"
 
+// The gradient operand of the clip norm and of Adam is either the arena's fp32 gradient or, after a bf16 gradient exchange, the
+// reduced bf16 buffer.  The kernels below are templates on its element type and differ in these loads alone: one float4 of gradients
+// (16 bytes of fp32, or 8 bytes of bf16 widened, element order kept: lo half first) and the scalar form for a tail.  The fp32
+// instantiations are the kernels as they were; a bf16 instantiation computes what the fp32 one computes on float(g_bf16), bit for bit.
+__device__ __forceinline__ float4 bf16x4_to_float4(uint2 r) {
+  float4 v;
+  v.x = __uint_as_float(r.x << 16); v.y = __uint_as_float(r.x & 0xffff0000u);
+  v.z = __uint_as_float(r.y << 16); v.w = __uint_as_float(r.y & 0xffff0000u);
+  return v;
+}
+__device__ __forceinline__ float4 grad4(const float* g, long long i) { return *(const float4*)(g + i * 4); }
+__device__ __forceinline__ float4 grad4(const bf16_t* g, long long i) { return bf16x4_to_float4(*(const uint2*)(g + i * 4)); }
+__device__ __forceinline__ float grad1(const float* g, long long i) { return g[i]; }
+__device__ __forceinline__ float grad1(const bf16_t* g, long long i) { return bf2f(g[i]); }
+
 __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g, long long n, float* __restrict__ out) {
   __shared__ float red[4];
   float s = 0.f;
@@ -33,18 +48,19 @@ extern "C" int medmoe_sumsq(const float* g, long long n, float* out, hipStream_t
 // bits; with data parallelism every rank would clip with a slightly different coefficient and the replicas' weights
 // would drift apart step by step (found with tools/two_rank_gpu.py: reduced gradients bit-identical, weights not).
 // scratch: >= 2049 floats, scratch[2048] (an arrival counter) must be 0 on entry and is 0 again on exit.
-__global__ __launch_bounds__(256) void sumsq_det_kernel(const float* __restrict__ g, long long n, float* __restrict__ out,
+template <typename GT>
+__global__ __launch_bounds__(256) void sumsq_det_kernel(const GT* __restrict__ g, long long n, float* __restrict__ out,
                                                        float* __restrict__ scratch) {
   __shared__ float red[4];
   __shared__ int last;
   float s = 0.f;
   const long long n4 = n >> 2;
   for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
-    const float4 v = *(const float4*)(g + i * 4);
+    const float4 v = grad4(g, i);
     s += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
   }
   if (blockIdx.x == 0 && threadIdx.x == 0)
-    for (long long i = n4 * 4; i < n; ++i) s += g[i] * g[i];
+    for (long long i = n4 * 4; i < n; ++i) s += grad1(g, i) * grad1(g, i);
   s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
   __syncthreads();
@@ -68,7 +84,7 @@ __global__ __launch_bounds__(256) void sumsq_det_kernel(const float* __restrict_
 extern "C" int medmoe_sumsq_det(const float* g, long long n, float* out, float* scratch, hipStream_t stream) {
   if (!g || !out || !scratch || n <= 0) return MM_ERR_ARG;
   const int grid = (int)min((n / 4 + 255) / 256 + 1, (long long)2048);
-  hipLaunchKernelGGL(sumsq_det_kernel, dim3(grid), dim3(256), 0, stream, g, n, out, scratch);
+  hipLaunchKernelGGL(sumsq_det_kernel<float>, dim3(grid), dim3(256), 0, stream, g, n, out, scratch);
   return mm_check_launch();
 }
 
@@ -87,7 +103,8 @@ __device__ __forceinline__ void adam_update(float& p, float g, float& m, float& 
   p -= step_size * (m / denom);
 }
 
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+template <typename GT>
+__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const GT* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, bf16_t* __restrict__ p16, long long n,
                                                    float b2, float omb1, float omb2, float eps, float wd, float step_size,
                                                    float bc2_sqrt, const float* __restrict__ normsq, float max_norm,
@@ -100,7 +117,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
   const long long n4 = n >> 2;
   for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
     float4 pp = *(float4*)(p + i * 4);
-    const float4 gg = *(const float4*)(g + i * 4);
+    const float4 gg = grad4(g, i);
     float4 mm = *(float4*)(m + i * 4), vv = *(float4*)(v + i * 4);
     float* P = (float*)&pp; const float* G = (const float*)&gg; float* M = (float*)&mm; float* V = (float*)&vv;
 #pragma unroll
@@ -117,7 +134,7 @@ extern "C" int medmoe_adam_step(float* p, const float* g, float* m, float* v, vo
   if (n % 4) return MM_ERR_SHAPE;   // flat buffers are padded to a multiple of 4 by the host
   const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
   const int grid = (int)min((n / 4 + 255) / 256, (long long)256 * 8);
-  hipLaunchKernelGGL(adam_kernel, dim3(grid), dim3(256), 0, stream, p, g, m, v, (bf16_t*)p_bf16, n, (float)beta2,
+  hipLaunchKernelGGL(adam_kernel<float>, dim3(grid), dim3(256), 0, stream, p, g, m, v, (bf16_t*)p_bf16, n, (float)beta2,
                      (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, (float)weight_decay, (float)(lr / bc1),
                      (float)sqrt(bc2), grad_normsq, max_norm, grad_scale);
   return mm_check_launch();
@@ -135,8 +152,8 @@ extern "C" int medmoe_adam_step(float* p, const float* g, float* m, float* v, vo
 // ---------------------------------------------------------------------------------------------
 #define ADAM_LDS_RUNS 1024
 
-template <bool LDS>
-__global__ __launch_bounds__(256) void adam_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+template <bool LDS, typename GT>
+__global__ __launch_bounds__(256) void adam_groups_kernel(float* __restrict__ p, const GT* __restrict__ g, float* __restrict__ m,
                                                           float* __restrict__ v, bf16_t* __restrict__ p16, long long n,
                                                           const long long* __restrict__ run_end, const float* __restrict__ run_lr,
                                                           const float* __restrict__ run_wd, int n_runs, float b2, float omb1, float omb2,
@@ -161,7 +178,7 @@ __global__ __launch_bounds__(256) void adam_groups_kernel(float* __restrict__ p,
   const long long n4 = n >> 2;
   for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
     float4 pp = *(float4*)(p + i * 4);
-    const float4 gg = *(const float4*)(g + i * 4);
+    const float4 gg = grad4(g, i);
     float4 mm = *(float4*)(m + i * 4), vv = *(float4*)(v + i * 4);
     float* P = (float*)&pp; const float* G = (const float*)&gg; float* M = (float*)&mm; float* V = (float*)&vv;
     const long long e0 = i * 4;
@@ -196,10 +213,81 @@ extern "C" int medmoe_adam_groups_step(float* p, const float* g, float* m, float
   if (n % 4) return MM_ERR_SHAPE;   // flat buffers are padded to a multiple of 4 by the host
   const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
   const int grid = (int)min((n / 4 + 255) / 256, (long long)256 * 8);
-  auto kern = n_runs <= ADAM_LDS_RUNS ? adam_groups_kernel<true> : adam_groups_kernel<false>;
+  auto kern = n_runs <= ADAM_LDS_RUNS ? adam_groups_kernel<true, float> : adam_groups_kernel<false, float>;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, stream, p, g, m, v, (bf16_t*)p_bf16, n, run_end, run_lr_mult, run_wd_mult, n_runs,
                      (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, (float)weight_decay, (float)(lr / bc1),
                      (float)sqrt(bc2), lr, weight_decay, decoupled ? 1 : 0, grad_normsq, max_norm, grad_scale);
+  return mm_check_launch();
+}
+
+// ---------------------------------------------------------------------------------------------
+// bf16 gradient exchange: the rank-local fp32 gradient is scaled by 1 / world and rounded to bf16 on the chip (grad_pack), the
+// bf16 buffer is all-reduced, and the clip norm and Adam read the reduced bf16 gradient where it lies - no pass widens it back to fp32.
+// No atomics besides sumsq's arrival counter, nothing read from the host: every result is a function of the inputs only.
+// ---------------------------------------------------------------------------------------------
+// out[i] = bf16_rne(g[i] * scale), the product formed in fp32 (as DDP's bf16_compress_hook divides before it rounds).  8 elements per lane
+// and iteration: two 16-byte loads, one 16-byte store; 6 B of HBM traffic per element.
+__global__ __launch_bounds__(256) void grad_pack_bf16_kernel(const float* __restrict__ g, bf16_t* __restrict__ out, long long n, float scale) {
+  const long long n8 = n >> 3;
+  for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n8; i += (long long)gridDim.x * 256) {
+    const float4 a = *(const float4*)(g + i * 8), b = *(const float4*)(g + i * 8 + 4);
+    uint4 o;
+    o.x = pack2bf(a.x * scale, a.y * scale); o.y = pack2bf(a.z * scale, a.w * scale);
+    o.z = pack2bf(b.x * scale, b.y * scale); o.w = pack2bf(b.z * scale, b.w * scale);
+    *(uint4*)(out + i * 8) = o;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0)
+    for (long long i = n8 * 8; i < n; ++i) out[i] = f2bf(g[i] * scale);
+}
+
+extern "C" int medmoe_grad_pack_bf16(const float* g, void* out_bf16, long long n, float scale, hipStream_t stream) {
+  if (!g || !out_bf16 || n <= 0) return MM_ERR_ARG;
+  if (((uintptr_t)g & 15) || ((uintptr_t)out_bf16 & 15)) return MM_ERR_ARG;   // bucket offsets are multiples of 8 elements of a 16-byte aligned arena
+  const int grid = (int)min((n / 8 + 255) / 256 + 1, (long long)256 * 8);
+  hipLaunchKernelGGL(grad_pack_bf16_kernel, dim3(grid), dim3(256), 0, stream, g, (bf16_t*)out_bf16, n, scale);
+  return mm_check_launch();
+}
+
+// sumsq_det_kernel's bf16 instantiation: the same grid, the same elements per thread in the same order, the same expressions and the same
+// partial-sum tree, so the result is bit-identical to medmoe_sumsq_det on the fp32 up-cast of the buffer (tests pin it with torch.equal).
+extern "C" int medmoe_sumsq_det_bf16(const void* g_bf16, long long n, float* out, float* scratch, hipStream_t stream) {
+  if (!g_bf16 || !out || !scratch || n <= 0) return MM_ERR_ARG;
+  if ((uintptr_t)g_bf16 & 7) return MM_ERR_ARG;                   // 8-byte loads
+  const int grid = (int)min((n / 4 + 255) / 256 + 1, (long long)2048);
+  hipLaunchKernelGGL(sumsq_det_kernel<bf16_t>, dim3(grid), dim3(256), 0, stream, (const bf16_t*)g_bf16, n, out, scratch);
+  return mm_check_launch();
+}
+
+// adam_kernel / adam_groups_kernel instantiated on the bf16 gradient (8 bytes per float4 of parameters: 32 B/param instead of 34, and no
+// 6 B/param widening pass before them).  One loop body and one adam_update for both element types: the step is bit-identical to the
+// fp32-gradient step on float(g_bf16).
+extern "C" int medmoe_adam_step_g16(float* p, const void* g_bf16, float* m, float* v, void* p_bf16, long long n, double lr,
+                                    double beta1, double beta2, double eps, double weight_decay, int step,
+                                    const float* grad_normsq, float max_norm, float grad_scale, hipStream_t stream) {
+  if (!p || !g_bf16 || !m || !v || n <= 0 || step < 1) return MM_ERR_ARG;
+  if ((uintptr_t)g_bf16 & 7) return MM_ERR_ARG;
+  if (n % 4) return MM_ERR_SHAPE;   // flat buffers are padded to a multiple of 4 by the host
+  const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+  const int grid = (int)min((n / 4 + 255) / 256, (long long)256 * 8);
+  hipLaunchKernelGGL(adam_kernel<bf16_t>, dim3(grid), dim3(256), 0, stream, p, (const bf16_t*)g_bf16, m, v, (bf16_t*)p_bf16, n, (float)beta2,
+                     (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, (float)weight_decay, (float)(lr / bc1),
+                     (float)sqrt(bc2), grad_normsq, max_norm, grad_scale);
+  return mm_check_launch();
+}
+
+extern "C" int medmoe_adam_groups_step_g16(float* p, const void* g_bf16, float* m, float* v, void* p_bf16, long long n,
+                                           const long long* run_end, const float* run_lr_mult, const float* run_wd_mult, int n_runs,
+                                           double lr, double beta1, double beta2, double eps, double weight_decay, int decoupled, int step,
+                                           const float* grad_normsq, float max_norm, float grad_scale, hipStream_t stream) {
+  if (!p || !g_bf16 || !m || !v || !run_end || !run_lr_mult || !run_wd_mult || n <= 0 || n_runs < 1 || step < 1) return MM_ERR_ARG;
+  if ((uintptr_t)g_bf16 & 7) return MM_ERR_ARG;
+  if (n % 4) return MM_ERR_SHAPE;   // flat buffers are padded to a multiple of 4 by the host
+  const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+  const int grid = (int)min((n / 4 + 255) / 256, (long long)256 * 8);
+  auto kern = n_runs <= ADAM_LDS_RUNS ? adam_groups_kernel<true, bf16_t> : adam_groups_kernel<false, bf16_t>;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, stream, p, (const bf16_t*)g_bf16, m, v, (bf16_t*)p_bf16, n, run_end, run_lr_mult,
+                     run_wd_mult, n_runs, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, (float)weight_decay,
+                     (float)(lr / bc1), (float)sqrt(bc2), lr, weight_decay, decoupled ? 1 : 0, grad_normsq, max_norm, grad_scale);
   return mm_check_launch();
 }
 

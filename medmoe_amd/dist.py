@@ -8,7 +8,10 @@ used by losses.py:503-524) plus DDP's gradient all-reduce (configs/trainer/ddp.y
   * the backward of the gathered keys is ONE reduce-scatter (BackpropType.GLOBAL semantics of
     torch.distributed.nn.functional.all_gather: every rank's gradient for my slice is summed);
   * gradients: one all-reduce over the single flat fp32 gradient buffer of a store (flat.FlatArena.g32: ParamStore, and
-    one more for TextStore / each FlatStore of the Swin encoder).
+    one more for TextStore / each FlatStore of the Swin encoder);
+  * opt-in (MedMoEConfig.grad_comm_dtype = "bf16"): the same all-reduces over a bf16 copy of the gradient, scaled by
+    1 / world and rounded on the chip before the exchange (what torch DDP's bf16_compress_hook does); half the bytes on the wire.
+    `comm` below is the arena (flat.FlatArena) or anything with its `g16` buffer, `pack(lo, hi, scale)` and `g16_reduced` flag.
 """
 import torch
 import torch.distributed as dist
@@ -47,12 +50,39 @@ def scatter_key_grads(d_all: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def allreduce_mean_(flat_grad: torch.Tensor):
+def _all_reduce_bf16(t: torch.Tensor, async_op: bool = False):
+    """Sum a bf16 slice over the ranks in place; returns the work handle of an async call, else None.  RCCL sums bf16 on the device.  gloo
+    (tests: two ranks sharing one GPU) stages device tensors through the host anyway and sums bf16 on host tensors only, so there the slice
+    is reduced as a host copy and copied back."""
+    if t.is_cuda and dist.get_backend() != "nccl":
+        torch.cuda.synchronize()                                  # as for fp32: the producers have to be finished before the host reads
+        host = t.cpu()
+        dist.all_reduce(host)
+        t.copy_(host)
+        return None
+    return dist.all_reduce(t, async_op=async_op) if async_op else dist.all_reduce(t)
+
+
+def allreduce_mean_(flat_grad: torch.Tensor, comm=None):
+    """Average an un-bucketed gradient arena over the ranks.  comm (bf16 exchange): `flat_grad` is packed into comm.g16 with the 1 / world
+    scale, g16 is summed over the ranks and marked as the step's reduced gradient; flat_grad itself is not touched."""
+    if comm is not None:
+        allreduce_mean_start(flat_grad, comm).finish()
+        return comm.g16
     if flat_grad.is_cuda and dist.get_backend() != "nccl":
         torch.cuda.synchronize()                                  # gloo reads the buffer from the host right away (tests)
     dist.all_reduce(flat_grad)
     flat_grad.div_(dist.get_world_size())
     return flat_grad
+
+
+def allreduce_mean_start(flat_grad: torch.Tensor, comm=None) -> "BucketedAllReduce":
+    """allreduce_mean_ in two halves, for an arena whose all-reduce runs underneath later work: the exchange of the whole arena is launched
+    here (one bucket of a BucketedAllReduce, so the pack / reduce / flag protocol of the bf16 exchange lives in that class alone) and the
+    caller joins it with `.finish()` on the returned reducer."""
+    red = BucketedAllReduce(flat_grad, [0, flat_grad.numel()], comm=comm)
+    red.ready(0)
+    return red
 
 
 def label_offset(local_batch: int) -> int:
@@ -66,14 +96,17 @@ class BucketedAllReduce:
     L-1..0, embeddings last); `ready(i)` launches an async all-reduce of bucket i on RCCL's stream (it
     waits for the kernels already enqueued on the compute stream), `finish()` joins them and averages.
     One message per ViT layer (7.1 M fp32 = 28 MB): large enough to run at link rate on the xGMI mesh,
-    small enough that only the last bucket is exposed."""
+    small enough that only the last bucket is exposed.
+    comm (bf16 exchange): `ready(i)` first packs bucket i into comm.g16 on the compute stream (bf16(g * 1 / world)) and all-reduces that
+    slice; `finish()` joins, marks comm.g16 as the step's reduced gradient and leaves flat_grad alone - the scale went in before the
+    rounding, so nothing is divided afterwards."""
 
-    def __init__(self, flat_grad: torch.Tensor, boundaries):
+    def __init__(self, flat_grad: torch.Tensor, boundaries, comm=None):
         # boundaries: ascending element offsets [0, ..., numel]; bucket i = [b[i], b[i+1])
         b = list(boundaries)
         if b[0] != 0 or b[-1] != flat_grad.numel() or any(b[i] >= b[i + 1] for i in range(len(b) - 1)):
             raise ValueError("bucket boundaries must cover the flat gradient exactly once")
-        self.flat, self.b, self.work = flat_grad, b, {}
+        self.flat, self.b, self.work, self.comm = flat_grad, b, {}, comm
 
     @property
     def n_buckets(self):
@@ -82,6 +115,11 @@ class BucketedAllReduce:
     def ready(self, i: int):
         if i in self.work:
             raise RuntimeError(f"bucket {i} reduced twice")
+        if self.comm is not None:
+            lo, hi = self.b[i], self.b[i + 1]
+            self.comm.pack(lo, hi, 1.0 / dist.get_world_size())
+            self.work[i] = _all_reduce_bf16(self.comm.g16[lo:hi], async_op=True)
+            return
         if self.flat.is_cuda and dist.get_backend() != "nccl":
             # RCCL enqueues the collective behind the kernels already on the compute stream; gloo reads the buffer
             # from the host right away, so the producers have to be finished first (tests / tools/two_rank_gpu.py)
@@ -93,6 +131,10 @@ class BucketedAllReduce:
             missing = [i for i in range(self.n_buckets) if i not in self.work]
             raise RuntimeError(f"gradient buckets never reduced: {missing}")
         for w in self.work.values():
-            w.wait()
+            if w is not None:
+                w.wait()
         self.work = {}
+        if self.comm is not None:
+            self.comm.g16_reduced = True
+            return
         self.flat.div_(dist.get_world_size())

@@ -118,6 +118,12 @@ class Engine:
             # MEDMOE_DIST_WORLD1=1: run the collectives even in a one-rank group, so that the RCCL path (backend "nccl",
             # async buckets, stream ordering) can be exercised on a single GPU (tests/test_rccl_world1_gpu.py)
             self.dist = self.world > 1 or os.environ.get("MEDMOE_DIST_WORLD1") == "1"
+        # bf16 gradient exchange (cfg.grad_comm_dtype = "bf16" or MEDMOE_GRAD_COMM=bf16): read per step through grad_comm(),
+        # because the Lightning module writes its keys into cfg after the engine exists
+        env_comm = os.environ.get("MEDMOE_GRAD_COMM", "")
+        if env_comm not in ("", "fp32", "bf16"):
+            raise ValueError(f"MEDMOE_GRAD_COMM must be 'fp32' or 'bf16', got {env_comm!r}")
+        self._grad_comm_env = env_comm == "bf16"
         # trainable text tower (cfg.freeze_text = False; reference freeze_bert: false): flat master / gradient / Adam buffers of its own, the padded
         # text pass with saved activations, a text backward, and the local loss in its word-gradient mode
         self.train_text = not cfg.freeze_text
@@ -148,6 +154,9 @@ class Engine:
         off = self.params.offsets
         self.bucket_bounds = [0] + [off[f"vit.layer.{l}.attention_layernorm.weight"] for l in range(cfg.n_layer_v)] \
             + [off["vit.final_layer_norm.weight"], self.params.numel]
+        if any(b % 8 for b in self.bucket_bounds):                  # FlatArena.pack moves 16 bytes per lane from a bucket's first element on
+            raise ValueError(f"gradient bucket offsets {self.bucket_bounds} must be multiples of 8 elements (a bucket starts inside an arena "
+                             "group, whose members are stored without padding?)")
         self._reducer = None
         self._side = None
         self.overlap_wgrad = os.environ.get("MEDMOE_OVERLAP_WGRAD", "1") == "1"    # weight-gradient GEMMs on a second stream (backward)
@@ -179,6 +188,13 @@ class Engine:
         from .optim_groups import set_rules
         set_rules(self.cfg, rules)
         self.apply_optimizer_groups()
+
+    def grad_comm(self, arena):
+        """The `comm` argument of the gradient all-reduces (medmoe_amd.dist) for `arena`: the arena itself when its gradient travels as bf16
+        (cfg.grad_comm_dtype = "bf16" or MEDMOE_GRAD_COMM=bf16, and this engine takes the data-parallel steps), None for the fp32 exchange."""
+        if self.cfg.grad_comm_dtype not in ("fp32", "bf16"):
+            raise ValueError(f"grad_comm_dtype must be 'fp32' or 'bf16', got {self.cfg.grad_comm_dtype!r}")
+        return arena if self.dist and (self._grad_comm_env or self.cfg.grad_comm_dtype == "bf16") else None
 
     def set_deterministic(self, flag: bool):
         """Switch deterministic mode on or off; refuses the combinations it is not built for.  The scratch buffers are allocated on first
@@ -1046,7 +1062,11 @@ class Engine:
         if self.dist:
             from . import dist as D_
             if optimizer:
-                red = D_.BucketedAllReduce(self.params.g32, self.bucket_bounds)
+                # the arena (bf16 exchange) or None.  The fp32 exchange keeps the two-argument call: reducers that stand in
+                # for the class (tests/test_host_logic.py's dry run) take (flat, bounds) and nothing else
+                comm = self.grad_comm(self.params)
+                red = D_.BucketedAllReduce(self.params.g32, self.bucket_bounds) if comm is None else \
+                    D_.BucketedAllReduce(self.params.g32, self.bucket_bounds, comm=comm)
                 self.backward(batch["label"], loss_scale, bucket_ready=red.ready)     # all-reduce overlapped with backward
                 red.finish()
             else:
@@ -1057,7 +1077,7 @@ class Engine:
             self.backward_text(self._d_words, self.ws["d_txt_g"])
             if self.dist and optimizer:                           # the text tower's gradient: one more all-reduce (not overlapped)
                 from . import dist as D_
-                D_.allreduce_mean_(self.tstore.g32)
+                D_.allreduce_mean_(self.tstore.g32, comm=self.grad_comm(self.tstore))
         self.dropout_step += 1                                      # the next call draws new masks (evaluation never advances it)
         if optimizer:
             self.optimizer_step()

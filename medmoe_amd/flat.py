@@ -4,6 +4,8 @@ working copy `p16` in the nn.Linear [out, in] layout and a second one, `p16t`, h
 the same NT kernel as forward).  `refresh()` is two kernels (cast + batched transpose) whatever the number of parameters, the clip norm is
 summed in a fixed order (`sumsq`), and clip + Adam + the bf16 copy are one launch (`adam_step`) - also with parameter groups
 (`set_param_groups`: contiguous runs of the arena with their own learning-rate / weight-decay multipliers) and AdamW.
+With the bf16 gradient exchange an arena also holds `g16`, the bf16 copy that `pack` fills and the ranks all-reduce: `g32` keeps
+the rank-local fp32 sum (what accumulation over micro-batches needs), and while `g16_reduced` is set the clip norm and Adam read `g16`.
 
 The stores say what is specific to them: `ParamStore` (ViT tower + MoE: its spec list, seeded init, the 8-bit expert copies) and
 `TextStore` (trainable text tower) build the arena from their spec lists; `FlatStore` below takes any name -> tensor dict (Swin tower,
@@ -74,6 +76,11 @@ class FlatArena:
         self.tr_max_tiles = max(((r[2] + 63) // 64) * ((r[3] + 63) // 64) for r in rows) if rows else 0
         self.m = self.v = self.normsq = self.norm_scratch = None
         self.step_count = 0
+        # bf16 gradient exchange: `g16` (bf16, this layout, allocated on first need) receives pack()'s bf16(g32 * scale) and is
+        # what the ranks all-reduce; `g16_reduced` says that it holds the reduced gradient of the current step, and sumsq() / adam_step()
+        # then read it instead of g32.  g32 keeps the rank-local fp32 sum throughout: micro-batches accumulate there, unrounded.
+        self._g16 = None
+        self.g16_reduced = False
 
     # -- views: built once per buffer (a backward asks for a few hundred of them per step) -----------------------------------------------
     def view(self, flat, name, shape=None):
@@ -124,9 +131,26 @@ class FlatArena:
     def after_update(self):
         """Hook: copies a store derives from the fp32 master itself (ParamStore's 8-bit expert weights)."""
 
+    # -- bf16 gradient exchange ----------------------------------------------------------------------------------------------------------
+    @property
+    def g16(self) -> torch.Tensor:
+        if self._g16 is None:
+            self._g16 = torch.zeros(self.numel, device=self.device, dtype=torch.bfloat16)
+        return self._g16
+
+    def pack(self, lo: int, hi: int, scale: float):
+        """g16[lo:hi] = bf16(g32[lo:hi] * scale) on the current stream (medmoe_grad_pack_bf16; lo a multiple of 8, as every entry's offset
+        is).  g32 is left as it is: the rank-local fp32 sum that accumulation over micro-batches needs."""
+        ops.call("grad_pack_bf16", self.g32[lo:hi], self.g16[lo:hi], hi - lo, scale)
+
+    def reduced_grad(self) -> torch.Tensor:
+        """The gradient the optimiser will see, as fp32: the reduced bf16 gradient up-cast while it is current, g32 otherwise."""
+        return self.g16.float() if self.g16_reduced else self.g32
+
     # -- fused clip + Adam ---------------------------------------------------------------------------------------------------------------
     def zero_grad(self):
         self.g32.zero_()
+        self.g16_reduced = False
 
     def has_adam_state(self) -> bool:
         return self.m is not None
@@ -142,7 +166,10 @@ class FlatArena:
     def sumsq(self) -> torch.Tensor:
         """Sum of squares of the gradient arena, summed in a fixed order (identical on every rank): this arena's share of the clip norm."""
         self.adam_state()
-        ops.call("sumsq_det", self.g32, self.numel, self.normsq, self.norm_scratch)
+        if self.g16_reduced:                                        # the bf16-reduced gradient: the same sum in the same order, read as bf16
+            ops.call("sumsq_det_bf16", self.g16, self.numel, self.normsq, self.norm_scratch)
+        else:
+            ops.call("sumsq_det", self.g32, self.numel, self.normsq, self.norm_scratch)
         return self.normsq
 
     # -- parameter groups: contiguous runs of the arena with their own learning-rate and weight-decay multipliers ---------------------------
@@ -181,19 +208,22 @@ class FlatArena:
         + torch.optim.Adam's update (L2 weight decay; decoupled: torch.optim.AdamW's) on the fp32 master, the bf16 copy written by the same
         kernel; the derived copies follow.  Without parameter groups, with Adam's default betas / eps and L2 decay this is medmoe_adam_step;
         anything else is ONE medmoe_adam_groups_step over the arena's run table (a single run when no groups are set).  Gradients must be
-        in THIS arena's g32 (no new_grad_arena() since the backward)."""
+        in THIS arena's g32 (no new_grad_arena() since the backward) - or, after a bf16 gradient exchange (`g16_reduced`), in g16: the
+        same two launches in their _g16 form read it as bf16, and the flag is cleared with the step."""
         m, v = self.adam_state()
         self.step_count += 1
         b1, b2 = float(betas[0]), float(betas[1])
+        g, sfx = (self.g16, "_g16") if self.g16_reduced else (self.g32, "")
         if self.runs is None and not decoupled and (b1, b2) == (0.9, 0.999) and float(eps) == 1e-8:
-            ops.call("adam_step", self.p32, self.g32, m, v, self.p16, self.numel, lr, 0.9, 0.999, 1e-8, weight_decay, self.step_count,
+            ops.call("adam_step" + sfx, self.p32, g, m, v, self.p16, self.numel, lr, 0.9, 0.999, 1e-8, weight_decay, self.step_count,
                      normsq_total, clip, grad_scale)
         else:
             if self.runs is None and self._one_run is None:
                 self._one_run = self._upload_runs([(self.numel, 1.0, 1.0)])
             ends, lrm, wdm = self._run_table if self.runs is not None else self._one_run
-            ops.call("adam_groups_step", self.p32, self.g32, m, v, self.p16, self.numel, ends, lrm, wdm, ends.numel(), lr, b1, b2, eps,
+            ops.call("adam_groups_step" + sfx, self.p32, g, m, v, self.p16, self.numel, ends, lrm, wdm, ends.numel(), lr, b1, b2, eps,
                      weight_decay, 1 if decoupled else 0, self.step_count, normsq_total, clip, grad_scale)
+        self.g16_reduced = False
         self._derive()
 
 
@@ -218,6 +248,7 @@ class FlatStore(FlatArena):
         """A fresh gradient buffer (the previous one stays alive through whoever still holds views of it: parameter .grad tensors that were
         not released before this backward)."""
         self.g32 = torch.zeros_like(self.g32)
+        self.g16_reduced = False
 
     def grads(self) -> Dict[str, torch.Tensor]:
         return {n: self.grad(n) for n in self.names}

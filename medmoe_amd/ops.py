@@ -499,6 +499,7 @@ _SIGS = {
     "router_bwd_det": "pppppppfpppiiiip", "ce_strided_det": "ppiilliffipp", "soft_xent_strided_det": "pppiillffffipp", "hardneg_strided_det": "ppiillffipp",
     "cos_scale_bwd_det": "ppppppiif",
     "sumsq": "plp", "sumsq_det": "plpp", "adam_step": "pppppldddddipff", "adam_groups_step": "ppppplpppidddddiipff", "cast_bf16": "ppl", "transpose_many": "pppii",
+    "grad_pack_bf16": "pplf", "sumsq_det_bf16": "plpp", "adam_step_g16": "pppppldddddipff", "adam_groups_step_g16": "ppppplpppidddddiipff",
 }
 
 
@@ -574,6 +575,9 @@ _COSTS = {
     "gemm_tn_cols_det": _cost_tn_cols, "gemm_tn_gram_det": _cost_tn_gram,
     "adam_step": lambda a: ("adam_kernel", 34.0 * a[5], "byte"),                                   # p, g, m, v read; p, m, v, bf16 copy written
     "adam_groups_step": lambda a: ("adam_groups_kernel", 34.0 * a[5], "byte"),                     # the same traffic: the run table stays on chip
+    "adam_step_g16": lambda a: ("adam_kernel<bf16>", 32.0 * a[5], "byte"),                           # the gradient read as bf16: 2 B/param less
+    "adam_groups_step_g16": lambda a: ("adam_groups_kernel<LDS, bf16>", 32.0 * a[5], "byte"),
+    "grad_pack_bf16": lambda a: ("grad_pack_bf16_kernel", 6.0 * a[2], "byte"),                     # fp32 read, bf16 written
     "scale_attn_bwd": lambda a: ("scale_attn_bwd_kernel", 2.0 * a[17] * (4 * (2 * a[18] + 2 * a[19]) + 2 * a[18]), "byte"),    # G, dG, H1, dH1 x 4 scales + eout, d_img_l rows
     "scale_attn_bwd_det": lambda a: ("scale_attn_bwd_kernel<DET> + scale_attn_bwd_reduce_kernel", 2.0 * a[17] * (4 * (2 * a[18] + 2 * a[19]) + 2 * a[18]), "byte"),
     "scale_attn_fwd": lambda a: ("scale_attn_fwd_kernel", 2.0 * a[8] * (4 * (a[9] + a[10]) + a[9]), "byte"),

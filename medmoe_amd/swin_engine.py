@@ -137,24 +137,32 @@ class SwinEngine:
             self._d_words.record_stream(side)
         if eng.dist and optimizer:
             import torch.distributed as dist
+            from . import dist as D_
             pending = []
+            comm_m, comm_t = eng.grad_comm(enc.store), eng.grad_comm(enc.tower.store)     # the arenas (bf16 exchange) or None
 
             def moe_ready():                                        # the MoE arena is complete: its all-reduce runs under the tower's backward
+                if comm_m is not None:                              # packed on the compute stream, the bf16 copy all-reduced behind it
+                    pending.append(D_.allreduce_mean_start(enc.store.g32, comm=comm_m))
+                    return
                 if dist.get_backend() != "nccl":
                     torch.cuda.synchronize()                        # gloo reads the buffer from the host right away (tests)
                 pending.append(dist.all_reduce(enc.store.g32, async_op=True))
             enc.backward(ws["d_img_g"], d_local.view(B, HW, D), labels=batch["label"], cls_weight=c.w_cls * loss_scale, zero_grad=zero_grad,
                          loss_parts=lp, after_moe=moe_ready)
-            if dist.get_backend() != "nccl":
-                torch.cuda.synchronize()
-            dist.all_reduce(enc.tower.store.g32)
-            pending[0].wait()
-            enc.store.g32.div_(eng.world); enc.tower.store.g32.div_(eng.world)
+            if comm_m is not None:
+                D_.allreduce_mean_(enc.tower.store.g32, comm=comm_t)
+                pending[0].finish()                                 # joins and marks g16 as reduced; the 1 / world scale went in with the pack
+            else:
+                if dist.get_backend() != "nccl":
+                    torch.cuda.synchronize()
+                dist.all_reduce(enc.tower.store.g32)
+                pending[0].wait()
+                enc.store.g32.div_(eng.world); enc.tower.store.g32.div_(eng.world)
             if text_done is not None:                               # the text arena: one more all-reduce, averaged as Engine.train_step does
                 torch.cuda.current_stream().wait_event(text_done)
                 text_done = None
-                from . import dist as D_
-                D_.allreduce_mean_(eng.tstore.g32)
+                D_.allreduce_mean_(eng.tstore.g32, comm=eng.grad_comm(eng.tstore))
         else:
             enc.backward(ws["d_img_g"], d_local.view(B, HW, D), labels=batch["label"], cls_weight=c.w_cls * loss_scale, zero_grad=zero_grad,
                          loss_parts=lp)

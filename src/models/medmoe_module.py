@@ -22,7 +22,8 @@ def _get(cfg: Any, key: str, default=None):
 
 class MedMoEPretrainingLightningModule(_Base):
     def __init__(self, model: nn.Module, loss: Any, optimizer: Any = None, scheduler: Any = None,
-                 compile: bool = False, num_classes: int = 5, fused_step: bool = False, optimizer_groups: Any = None):
+                 compile: bool = False, num_classes: int = 5, fused_step: bool = False, optimizer_groups: Any = None,
+                 grad_comm_dtype: str = "fp32"):
         """`fused_step` (MI355X build, `model.fused_step` in the config tree): training steps run `Engine.train_step` - the hand-scheduled
         forward / losses / backward with the embedding all-gather, the reduce-scatter of the gathered-key gradients, the per-layer
         gradient all-reduce overlapped with backward and the fused clip + Adam - instead of torch autograd + a torch optimizer.
@@ -30,7 +31,9 @@ class MedMoEPretrainingLightningModule(_Base):
         Soft variants) and torch.optim.Adam or torch.optim.AdamW in the config, and refuses anything else at construction.
         `optimizer_groups` (fused step only): the rule set of medmoe_amd.optim_groups - no_decay (name patterns), no_decay_1d,
         text_lr_mult, layer_decay - that cuts the engine's flat stores into parameter groups; the scheduler keeps driving the base
-        learning rate, the groups multiply it."""
+        learning rate, the groups multiply it.
+        `grad_comm_dtype` (`model.grad_comm_dtype`, fused step only): "fp32" or "bf16" - the number format of the data-parallel gradient
+        all-reduces (MedMoEConfig.grad_comm_dtype); a single process ignores it."""
         super().__init__()
         self.model = model
         self.loss_cfg = loss
@@ -47,6 +50,12 @@ class MedMoEPretrainingLightningModule(_Base):
         if self._optimizer_groups and not self.fused_step:
             raise NotImplementedError("optimizer_groups needs fused_step=true: the autograd path steps ONE flat parameter, which cannot be "
                                       "cut into groups (the fused step groups runs of the engine's flat stores)")
+        self._grad_comm_dtype = str(grad_comm_dtype)
+        if self._grad_comm_dtype not in ("fp32", "bf16"):
+            raise ValueError(f"grad_comm_dtype must be 'fp32' or 'bf16', got {grad_comm_dtype!r}")
+        if self._grad_comm_dtype != "fp32" and not self.fused_step:
+            raise NotImplementedError("grad_comm_dtype needs fused_step=true: the bf16 exchange packs the engine's flat gradient arenas, the "
+                                      "autograd path all-reduces torch's own .grad tensors in fp32")
         if self.fused_step:
             self.automatic_optimization = False                                  # Lightning: manual optimisation (the engine steps itself)
             self._configure_engine()
@@ -139,6 +148,7 @@ class MedMoEPretrainingLightningModule(_Base):
         c.optimizer = "adamw" if adamw else "adam"
         c.adam_betas = tuple(float(b) for b in opt.keywords.get("betas", (0.9, 0.999)))
         c.adam_eps = float(opt.keywords.get("eps", 1e-8))
+        c.grad_comm_dtype = self._grad_comm_dtype
         from medmoe_amd.optim_groups import set_rules
         set_rules(c, self._optimizer_groups)                         # validates the rule set and the optimiser keys above
         if getattr(self.model, "swin", None) is None:                # arch = swin_t: the SwinEngine groups its own arenas when it is built
