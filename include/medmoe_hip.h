@@ -387,6 +387,22 @@ int medmoe_cos_scale_bwd_det(float* dC, const float* C, const float* na, const f
    loss sum): counted on the host, one add per such launch.  A deterministic step leaves it unchanged. */
 long long medmoe_nondet_launches(void);
 
+/* LoRA adapters on the text tower's fused q / k / v projection (csrc/lora.hip).  n targets (1..3) own the D columns of a qkv row
+   (pitch ldq) from c0 / c1 / c2 on (multiples of 8, not overlapping; D % 64 == 0).  Adapters are stored padded to rank 16 and stacked over the
+   targets: A [n*16][D], Bw [n*D][16] (pad rows of A / pad columns of Bw zero), At [D][n*16] and Bt [16][n*D] their transposes; U and dU are
+   [M][n*16] bf16; s = lora_alpha / r.  Dropout on the side path's input: the (seed, step, site, thresh, scale) of medmoe_dropout_apply over
+   the [M][D] array, thresh = 0 for none.
+   fwd: U = (keep X scale) A^T, qkv[:, c_t : c_t + D] = bf16(qkv + s U_t B_t^T), one launch. */
+int medmoe_lora_fwd(const void* X, const void* A, const void* Bw, void* U, void* qkv, int ldq, int M, int D, int n, int c0, int c1, int c2, float s, long long seed, long long step, long long site, long long thresh, float scale, hipStream_t stream);
+/* dU_t = bf16(s dqkv_t B_t); dy [M][D] (bf16, may be null: nothing below trains) += keep scale (dU A) */
+int medmoe_lora_bwd_dx(const void* dqkv, int ldq, const void* Bt, const void* At, void* dU, void* dy, int M, int D, int n, int c0, int c1, int c2, float s, long long seed, long long step, long long site, long long thresh, float scale, hipStream_t stream);
+/* gB [n*D][16] += s dqkv_t^T U_t, gA [n*16][D] += dU_t^T (keep X scale): partial sums per 256 rows in `scratch`
+   (scratch_floats >= medmoe_lora_wgrad_scratch(M, D, n)), added up in a fixed order by a second kernel - no atomics */
+int medmoe_lora_bwd_wgrad(const void* dqkv, int ldq, const void* X, const void* U, const void* dU, float* gA, float* gB, float* scratch, long long scratch_floats, int M, int D, int n, int c0, int c1, int c2, float s, long long seed, long long step, long long site, long long thresh, float scale, hipStream_t stream);
+long long medmoe_lora_wgrad_scratch(int M, int D, int n);
+/* W (bf16 [>= c_t + D rows][ldw], a copy of the fused projection's weight): rows c_t .. c_t + D - 1 = bf16(W + s B_t A_t) */
+int medmoe_lora_merge(void* W, int ldw, const void* A, const void* Bw, int D, int n, int c0, int c1, int c2, float s, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,6 +32,15 @@ class MedMoEConfig:
     text_hidden_dropout: float = 0.0
     text_attn_dropout: float = 0.0
     dropout_seed: int = 0
+    # LoRA adapters on the text tower's attention projections (reference configs/model/med-moe.yaml:27-30 lora / lora_r / lora_alpha /
+    # lora_dropout; peft's LoraConfig(target_modules=["query", "value"]) sketched in vision_encoder.py:30-36): the base tower stays frozen
+    # (freeze_text = True), rank-r adapters A [r, D], B [D, r] on the chosen slices of the fused q / k / v projection train.
+    # text_lora_dropout acts on the side path's input only, one mask per layer shared by its targets (site 4 * layer + 3 of csrc/philox.h)
+    text_lora: bool = False
+    text_lora_r: int = 8
+    text_lora_alpha: float = 16.0
+    text_lora_dropout: float = 0.0
+    text_lora_targets: Tuple[str, ...] = ("query", "value")
     # deterministic mode (trainer.deterministic): no launch of a step whose result depends on the order in which workgroups or waves arrive -
     # staged or single-writer forms of every weight-gradient GEMM, LayerNorm / scale-attention parameter gradient and loss sum
     deterministic: bool = False
@@ -117,6 +126,23 @@ class MedMoEConfig:
         for key in ("text_hidden_dropout", "text_attn_dropout"):
             if not 0.0 <= float(getattr(self, key)) < 1.0:
                 raise ValueError(f"{key} must be in [0, 1), got {getattr(self, key)}")
+        if not 0.0 <= float(self.text_lora_dropout) < 1.0:
+            raise ValueError(f"text_lora_dropout must be in [0, 1), got {self.text_lora_dropout}")
+        if self.text_lora:
+            if not self.freeze_text:
+                raise ValueError("text_lora with freeze_text=False (text.freeze_bert: false): the adapters train on a FROZEN base tower - "
+                                 "set freeze_text=True (or train the whole tower without adapters)")
+            if not 1 <= int(self.text_lora_r) <= 16:
+                raise ValueError(f"text_lora_r must be in 1..16 (the side path runs on the 16-wide MFMA), got {self.text_lora_r}")
+            tg = (self.text_lora_targets,) if isinstance(self.text_lora_targets, str) else tuple(self.text_lora_targets)
+            if not tg or len(set(tg)) != len(tg) or any(t not in ("query", "key", "value") for t in tg):
+                raise ValueError(f"text_lora_targets must be a non-empty list of distinct names out of query / key / value, got {tg!r}")
+            if not float(self.text_lora_alpha) > 0.0:
+                raise ValueError(f"text_lora_alpha must be > 0, got {self.text_lora_alpha}")
+            if self.deterministic:
+                raise NotImplementedError("deterministic with text_lora (text.lora: true): the trainable text path (the local loss' word gradients, "
+                                          "the text backward) has no deterministic form yet - a named follow-up (DESIGN 3e); the adapters' own "
+                                          "weight gradients are summed in a fixed order already")
         if self.expert_fp8 and self.expert_mx:
             raise ValueError("expert_fp8 and expert_mx are two formats of the same weights: set one")
         if self.expert_mx and (self.d_v % 32 or self.d_out % 64):

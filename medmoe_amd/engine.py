@@ -87,7 +87,7 @@ class Engine:
         self.text_dropout = cfg.text_hidden_dropout > 0.0 or cfg.text_attn_dropout > 0.0
         self.dropout_step = 0                                        # one per train_step call, counted on the host; travels with the checkpoint
         self._text_drop_step = None                                  # the step whose masks the last text pass applied (None: it applied none)
-        if self.text_dropout and cfg.freeze_text:
+        if self.text_dropout and cfg.freeze_text and not cfg.text_lora:
             raise NotImplementedError("text_hidden_dropout / text_attn_dropout > 0 (model.model.text.hidden_dropout_prob / "
                                       "attention_probs_dropout_prob) with freeze_text=True (text.freeze_bert: true): dropout is built for the "
                                       "trainable tower's padded pass, not for the packed frozen one")
@@ -126,12 +126,26 @@ class Engine:
         self._grad_comm_env = env_comm == "bf16"
         # trainable text tower (cfg.freeze_text = False; reference freeze_bert: false): flat master / gradient / Adam buffers of its own, the padded
         # text pass with saved activations, a text backward, and the local loss in its word-gradient mode
-        self.train_text = not cfg.freeze_text
+        # LoRA (cfg.text_lora): the base tower stays the frozen bf16 dict, rank-r adapters on slices of the fused q / k / v projection
+        # train in a small arena of their own (medmoe_amd/text_lora.py).  Everything keyed on train_text follows: the padded pass, the word
+        # gradients, backward_text (which then skips every base weight gradient), the text dropouts
+        self.text_lora = bool(cfg.text_lora)
+        self.train_text = (not cfg.freeze_text) or self.text_lora
         self.tstore = None
-        if self.train_text:
-            if cfg.soft_label:
-                raise NotImplementedError("soft_label with a trainable text tower: the reference scores captions with a SEPARATE frozen BERT "
-                                          "(medmoe_module.py:207-210); this build takes them from the tower itself, which must then stay frozen")
+        self.lora = None
+        self._lora_drop_step = None                                  # the step whose LoRA dropout mask the last text pass applied (None: none)
+        self._base_t: Dict[str, tuple] = {}                          # LoRA: transposed bf16 copies of the frozen base's GEMM weights (dgrad operands)
+        if self.train_text and cfg.soft_label:
+            raise NotImplementedError("soft_label with a trainable text tower: the reference scores captions with a SEPARATE frozen BERT "
+                                      "(medmoe_module.py:207-210); this build takes them from the tower itself, which must then stay frozen")
+        if self.text_lora:
+            if cfg.text_lora_dropout > 0.0 and os.environ.get("MEDMOE_GRAPH", "0") == "1":
+                raise NotImplementedError("text_lora_dropout > 0 (model.model.text.lora_dropout) with MEDMOE_GRAPH=1: the dropout step counter is a "
+                                          "by-value launch argument, a replayed graph would repeat one step's masks")
+            from .text_lora import LoraStore
+            self.lora = LoraStore(cfg, self.device, seed)
+            self.refresh_text_base()
+        elif self.train_text:
             from .text_params import TextStore
             self.tstore = TextStore(cfg, self.device, self.params.text)
             self.params.text = self.tstore.as_dict()             # views of the flat buffers: an optimiser step updates them in place
@@ -173,8 +187,45 @@ class Engine:
     def optimizer_stores(self) -> Dict[str, object]:
         """kind (medmoe_amd.optim_groups) -> the arenas this engine steps."""
         out = {"vit": self.params}
-        if self.tstore is not None:
-            out["text"] = self.tstore
+        if self.text_arena() is not None:
+            out["text"] = self.text_arena()
+        return out
+
+    def text_arena(self):
+        """The arena the text side trains: the whole tower's (freeze_text = False), the LoRA adapters' (text_lora), or None (frozen)."""
+        return self.lora if self.lora is not None else self.tstore
+
+    # -- LoRA: the frozen base's dgrad operands, the adapters' launches, the merged tower ----------------------------------------------------
+    _BASE_GEMMS = ("attention.input_proj.weight", "attention.output_proj.weight", "feedforward.model.0.weight", "feedforward.model.2.weight")
+
+    def refresh_text_base(self):
+        """LoRA: the transposed bf16 copy ([in, out]) of the four GEMM weights of every layer of the frozen base - what the text backward's
+        dgrad GEMMs read.  Made at construction and again after the base changed (a loaded checkpoint replaces the tensors of params.text:
+        `_base_wt` notices); never per step, and the base has no fp32 master, gradient or Adam state."""
+        for l in range(self.cfg.n_layer_t):
+            for n in self._BASE_GEMMS:
+                self._base_wt(f"layer.{l}.{n}")
+
+    def _base_wt(self, name: str) -> torch.Tensor:
+        w = self.params.text[name]
+        hit = self._base_t.get(name)
+        if hit is None or hit[0] is not w:
+            hit = self._base_t[name] = (w, w.t().contiguous())
+        return hit[1]
+
+    def _lora_rng(self, l: int):
+        if self._lora_drop_step is None:
+            return None
+        return ops.dropout_rng(self.cfg.dropout_seed, self._lora_drop_step, 4 * l + ops.DROPOUT_SITE_LORA, self.cfg.text_lora_dropout)
+
+    def merged_text_params(self) -> Dict[str, torch.Tensor]:
+        """The frozen-tower parameter dict (names and dtypes of params.text) with the adapters merged into the fused projections:
+        W_t <- bf16(W_t + s B_t A_t) (medmoe_lora_merge on a copy).  For export, and for evaluation on a plain frozen engine."""
+        if self.lora is None:
+            raise RuntimeError("merged_text_params: this engine has no LoRA adapters (cfg.text_lora)")
+        lo, out = self.lora, {k: v.clone() for k, v in self.params.text.items()}
+        for l in range(self.cfg.n_layer_t):
+            ops.lora_merge(out[f"layer.{l}.attention.input_proj.weight"], lo.A16(l), lo.B16(l), lo.targets, lo.scale)
         return out
 
     def apply_optimizer_groups(self):
@@ -201,6 +252,9 @@ class Engine:
         use, in deterministic mode only."""
         flag = bool(flag)
         if flag:
+            if self.cfg.text_lora:
+                raise NotImplementedError("deterministic with text_lora (text.lora: true): the trainable text path (the local loss' word "
+                                          "gradients, the text backward) has no deterministic form yet - a named follow-up (DESIGN 3e)")
             if not self.cfg.freeze_text:
                 raise NotImplementedError("deterministic with freeze_text=False (text.freeze_bert: false): the trainable text tower's embedding "
                                           "gradients meet in fp32 atomics and index_add_ - a named follow-up (DESIGN 3e)")
@@ -293,7 +347,14 @@ class Engine:
                 buf(f"t_x1{l}", (Mt, Dt)); buf(f"t_st1{l}", (2, Mt), F32); buf(f"t_r{l}", (Mt, Dt))
                 buf(f"t_h{l}", (Mt, c.ff_t)); buf(f"t_dg{l}", (Mt, c.ff_t)); buf(f"t_x2{l}", (Mt, Dt)); buf(f"t_st2{l}", (2, Mt), F32)
             buf("t_dH", (Mt, Dt)); buf("t_da", (Mt, Dt)); buf("t_db", (Mt, Dt)); buf("t_dc", (Mt, Dt)); buf("t_datt", (Mt, Dt))
-            buf("t_dz", (Mt, c.ff_t)); buf("t_dqkv", (Mt, 3 * Dt)); buf("t_delta", (B * Ht * T,), F32); buf("t_dxemb", (Mt, Dt), F32)
+            buf("t_dz", (Mt, c.ff_t)); buf("t_dqkv", (Mt, 3 * Dt)); buf("t_delta", (B * Ht * T,), F32)
+            if self.lora is None:
+                buf("t_dxemb", (Mt, Dt), F32)
+            else:                  # the adapters' U = dropout(x) A^T per layer (bf16, 16 per target: the backward reads it), one d U, the wgrad partials
+                nt = len(self.lora.targets)
+                for l in range(Lt):
+                    buf(f"t_lu{l}", (Mt, nt * ops.LORA_RANK_PAD))
+                buf("t_ldu", (Mt, nt * ops.LORA_RANK_PAD)); buf("t_lsc", (ops.lora_wgrad_scratch(Mt, Dt, nt),), F32)
             buf("d_txt_g", (B, Dt), F32); buf("cb", (B * self.world,), F32)
             if c.text_hidden_dropout > 0.0:      # a GEMM output before its dropout + residual + LayerNorm launch; d z = keep * d x1 / (1 - p) in the backward
                 buf("t_z", (Mt, Dt)); buf("t_dzd", (Mt, Dt))
@@ -525,6 +586,8 @@ class Engine:
         self._tt_state = (ids32, tt32, km)
         drop = training and self.text_dropout
         self._text_drop_step = self.dropout_step if drop else None
+        lo = self.lora
+        self._lora_drop_step = self.dropout_step if (training and lo is not None and c.text_lora_dropout > 0.0) else None
         ph, pa = (c.text_hidden_dropout, c.text_attn_dropout) if drop else (0.0, 0.0)
         x = ws["t_x0"]
         ops.call("text_embed_ln", ids32, tt32, t["word_embeddings"], t["position_embeddings"], t["token_type_embeddings"],
@@ -535,6 +598,8 @@ class Engine:
             b = f"layer.{l}."
             st1, st2 = ws[f"t_st1{l}"], ws[f"t_st2{l}"]
             ops.gemm_nt(x, t[b + "attention.input_proj.weight"], ws[f"t_qkv{l}"], bias=t[b + "attention.input_proj.bias"])
+            if lo is not None:     # qkv[:, target columns] += s (dropout(x) A^T) B^T, U kept for the backward: one launch
+                ops.lora_fwd(x, lo.A16(l), lo.B16(l), ws[f"t_lu{l}"], ws[f"t_qkv{l}"], lo.targets, lo.scale, self._lora_rng(l))
             if drop:
                 if pa > 0.0:
                     ops.attn_drop_fwd(ws[f"t_qkv{l}"], ws[f"t_att{l}"], ws[f"t_lse{l}"], km, B, T, H, self._drop_rng(4 * l, pa))
@@ -586,6 +651,8 @@ class Engine:
     def backward_text(self, d_words: Optional[torch.Tensor], d_txt_g: Optional[torch.Tensor]):
         """Back-propagate d loss / d word embeddings (fp32 [B, T, D]) and d loss / d sentence embeddings (fp32 [B, D]) through the aggregation,
         the post-norm blocks (transformer.py:116-130) and the embedding front-end into the text store's flat gradient buffer."""
+        if self.lora is not None:
+            return self._backward_text_lora(d_words, d_txt_g)
         c, ws, ts = self.cfg, self.ws, self.tstore
         B, T, Dt, H, L = self.B, c.max_len, c.d_t, c.n_head_t, c.n_layer_t
         ids32, tt32, km = self._tt_state
@@ -634,6 +701,45 @@ class Engine:
         grad("position_embeddings").add_(dxe.sum(dim=0))
         tt = tt32.view(-1).long() if tt32 is not None else torch.zeros(B * T, device=self.device, dtype=torch.long)
         grad("token_type_embeddings").index_add_(0, tt, ws["t_dxemb"])
+
+    def _backward_text_lora(self, d_words: Optional[torch.Tensor], d_txt_g: Optional[torch.Tensor]):
+        """backward_text with LoRA adapters on a frozen base: the same chain of dgrad GEMMs (on the base's transposed copies), LayerNorm and
+        attention backwards, WITHOUT any base parameter gradient - no weight-gradient GEMM, no LayerNorm gamma / beta sums, no embedding
+        backward.  Per layer, after the attention backward has written d qkv: medmoe_lora_bwd_dx (d U, and the adapters' term of d x added into
+        the base dgrad GEMM's output) and medmoe_lora_bwd_wgrad (the adapters' gradients, += into the arena).  At layer 0 nothing below
+        trains: the dgrad GEMM and the d x term are both skipped."""
+        c, ws, lo, t = self.cfg, self.ws, self.lora, self.params.text
+        B, T, Dt, H, L = self.B, c.max_len, c.d_t, c.n_head_t, c.n_layer_t
+        _, _, km = self._tt_state
+        wt = self._base_wt
+        dH = ws["t_dH"]
+        drop = self._text_drop_step is not None
+        ph, pa = (c.text_hidden_dropout, c.text_attn_dropout) if drop else (0.0, 0.0)
+        ops.call("text_aggregate_bwd", d_words, d_txt_g, self._seg_used, dH, B, T, Dt)
+        dy, d1, d2 = ws["t_da"], ws["t_db"], ws["t_dc"]
+        dy.copy_(dH)
+        for l in range(L - 1, -1, -1):
+            b = f"layer.{l}."
+            st1, st2 = ws[f"t_st1{l}"], ws[f"t_st2{l}"]
+            ops.layernorm_bwd(dy, ws[f"t_x2{l}"], st2[0], st2[1], t[b + "feedforward_layernorm.weight"], d1)
+            dz = ops.dropout_apply(d1, ws["t_dzd"], self._drop_rng(4 * l + 2, ph)) if ph > 0.0 else d1
+            ops.gemm_nt(dz, wt(b + "feedforward.model.2.weight"), ws["t_dz"], aux=ws[f"t_dg{l}"], epi=ops.EPI_MUL_AUX)
+            ops.gemm_nt(ws["t_dz"], wt(b + "feedforward.model.0.weight"), d2, residual=d1)
+            ops.layernorm_bwd(d2, ws[f"t_x1{l}"], st1[0], st1[1], t[b + "attention_layernorm.weight"], d1)
+            dz = ops.dropout_apply(d1, ws["t_dzd"], self._drop_rng(4 * l + 1, ph)) if ph > 0.0 else d1
+            ops.gemm_nt(dz, wt(b + "attention.output_proj.weight"), ws["t_datt"])
+            if pa > 0.0:
+                ops.attn_drop_bwd(ws[f"t_qkv{l}"], ws[f"t_att{l}"], ws["t_datt"], ws[f"t_lse{l}"], km, ws["t_dqkv"], ws["t_delta"], B, T, H,
+                                  self._drop_rng(4 * l, pa))
+            else:
+                ops.attn_bwd(ws[f"t_qkv{l}"], ws[f"t_att{l}"], ws["t_datt"], ws[f"t_lse{l}"], km, ws["t_dqkv"], ws["t_delta"], B, T, H)
+            rng = self._lora_rng(l)
+            if l > 0:
+                ops.gemm_nt(ws["t_dqkv"], wt(b + "attention.input_proj.weight"), dy, residual=d1)           # d x = d x1 + dqkv Wqkv (base)
+            ops.lora_bwd_dx(ws["t_dqkv"], lo.B16t(l), lo.A16t(l), ws["t_ldu"], dy if l > 0 else None, lo.targets, lo.scale, rng)
+            ops.lora_bwd_wgrad(ws["t_dqkv"], ws[f"t_x{l}"], ws[f"t_lu{l}"], ws["t_ldu"], lo.gA(l), lo.gB(l), ws["t_lsc"], lo.targets, lo.scale, rng)
+            if l > 0 and l >= self._text_first_sel:
+                dy.add_(dH)
 
     def text_soft_target(self) -> torch.Tensor:
         """Caption-to-caption scores of the Soft-GLoRIA losses (medmoe_module.py:258-281 get_text_soft_target): the frozen text model's last
@@ -1044,7 +1150,7 @@ class Engine:
         if zero_grad:
             self.params.zero_grad()
             if self.train_text:
-                self.tstore.zero_grad()
+                self.text_arena().zero_grad()
         if self.overlap_wgrad and batch["image"].is_cuda and B * self.cfg.n_tok_v <= 131072:
             # the frozen text tower is independent of the image tower: at small per-rank batches its GEMMs (77 tokens per pair) fill
             # a fraction of the chip, so it runs on the second stream underneath the image tower
@@ -1077,7 +1183,7 @@ class Engine:
             self.backward_text(self._d_words, self.ws["d_txt_g"])
             if self.dist and optimizer:                           # the text tower's gradient: one more all-reduce (not overlapped)
                 from . import dist as D_
-                D_.allreduce_mean_(self.tstore.g32, comm=self.grad_comm(self.tstore))
+                D_.allreduce_mean_(self.text_arena().g32, comm=self.grad_comm(self.text_arena()))
         self.dropout_step += 1                                      # the next call draws new masks (evaluation never advances it)
         if optimizer:
             self.optimizer_step()
@@ -1093,7 +1199,7 @@ class Engine:
         """clip_grad_norm_(cfg.clip) + torch.optim.Adam(lr, weight_decay) (cfg.optimizer = "adamw": torch.optim.AdamW; cfg.adam_betas /
         adam_eps; the parameter groups the stores carry), fused, on the gradients the stores hold; the working copies follow.  ONE clip
         norm over both towers' gradients when the text tower trains, as clip_grad_norm_ over all parameters computes it."""
-        c, image, text = self.cfg, self.params, self.tstore if self.train_text else None
+        c, image, text = self.cfg, self.params, self.text_arena() if self.train_text else None
         lr = c.lr if lr is None else lr
         text_part = text.sumsq() if text is not None else None
         total = image.sumsq()

@@ -468,6 +468,79 @@ def attn_drop_bwd(qkv, out, dout, lse, key_mask, dqkv, delta, B, N, H, rng, head
 
 
 # ---------------------------------------------------------------------------------------------
+# LoRA adapters on the text tower's fused q / k / v projection (csrc/lora.hip; medmoe_amd/text_lora.py holds the arena)
+# ---------------------------------------------------------------------------------------------
+LORA_RANK_PAD = 16                   # adapters are stored at rank 16: pad rows of A / pad columns of B are zero and stay zero
+LORA_TARGETS = ("query", "key", "value")
+DROPOUT_SITE_LORA = 3                # + 4 * layer: the fourth site of a layer, one mask shared by the layer's targets
+_NO_DROP = (0, 0, 0, 0, 1.0)
+
+
+def lora_cols(targets, D: int):
+    """Column offsets of the targets in a fused [q | k | v] row, padded to three launch arguments."""
+    c = [LORA_TARGETS.index(t) * D for t in targets]
+    return tuple(c + [0] * (3 - len(c)))
+
+
+def _lora_check(name, M, D, n, u_like, **bf16):
+    if not 1 <= n <= 3 or D % 64 or M <= 0:
+        raise ValueError(f"{name}: 1..3 targets, D a multiple of 64, M > 0 (got n={n}, D={D}, M={M})")
+    for nm, t in bf16.items():
+        if t is not None:
+            _need(t, torch.bfloat16, nm)
+            if not t.is_contiguous():
+                raise ValueError(f"{name}: {nm} must be contiguous")
+    if u_like is not None and u_like.numel() != M * n * LORA_RANK_PAD:
+        raise ValueError(f"{name}: U / dU must be [M, n * {LORA_RANK_PAD}]")
+
+
+def lora_fwd(x, A, Bw, U, qkv, targets, s, rng=None):
+    """U = dropout(x) A^T (stored bf16 [M, n*16]); qkv[:, c_t : c_t + D] += s U_t B_t^T in place.  A [n*16, D], Bw [n*D, 16] bf16."""
+    M, D, n = x.shape[0], x.shape[1], len(targets)
+    _lora_check("lora_fwd", M, D, n, U, x=x, A=A, Bw=Bw, U=U, qkv=qkv)
+    if A.numel() != n * LORA_RANK_PAD * D or Bw.numel() != A.numel() or qkv.shape[0] != M or qkv.shape[-1] != 3 * D:
+        raise ValueError("lora_fwd: A [n*16, D], Bw [n*D, 16], qkv [M, 3D]")
+    call("lora_fwd", x, A, Bw, U, qkv, qkv.stride(-2), M, D, n, *lora_cols(targets, D), s, *(rng or _NO_DROP))
+    return qkv
+
+
+def lora_bwd_dx(dqkv, Bt, At, dU, dy, targets, s, rng=None):
+    """dU_t = s dqkv_t B_t (stored bf16 [M, n*16]); dy [M, D] += dropout mask * (dU A) (dy None: skipped).  Bt [16, n*D], At [D, n*16] bf16."""
+    M, D, n = dqkv.shape[0], dqkv.shape[-1] // 3, len(targets)
+    _lora_check("lora_bwd_dx", M, D, n, dU, dqkv=dqkv, Bt=Bt, At=At, dU=dU, dy=dy)
+    if Bt.numel() != n * LORA_RANK_PAD * D or At.numel() != Bt.numel() or dqkv.shape[-1] != 3 * D or (dy is not None and dy.numel() != M * D):
+        raise ValueError("lora_bwd_dx: Bt [16, n*D], At [D, n*16], dqkv [M, 3D], dy [M, D]")
+    call("lora_bwd_dx", dqkv, dqkv.stride(-2), Bt, At, dU, dy, M, D, n, *lora_cols(targets, D), s, *(rng or _NO_DROP))
+    return dU
+
+
+def lora_wgrad_scratch(M: int, D: int, n: int) -> int:
+    return _scratch_query("lora_wgrad_scratch", M, D, n)
+
+
+def lora_bwd_wgrad(dqkv, x, U, dU, gA, gB, scratch, targets, s, rng=None):
+    """gB [n*D, 16] += s dqkv_t^T U_t, gA [n*16, D] += dU_t^T dropout(x) (fp32): per-chunk partial sums in `scratch`, summed in a fixed order."""
+    M, D, n = x.shape[0], x.shape[1], len(targets)
+    _lora_check("lora_bwd_wgrad", M, D, n, U, dqkv=dqkv, x=x, U=U, dU=dU)
+    for t, nm in ((gA, "gA"), (gB, "gB"), (scratch, "scratch")):
+        _need(t, torch.float32, nm)
+    if gA.numel() != n * LORA_RANK_PAD * D or gB.numel() != gA.numel() or dU.numel() != U.numel() or dqkv.shape[0] != M or dqkv.shape[-1] != 3 * D \
+            or not gA.is_contiguous() or not gB.is_contiguous() or scratch.numel() < lora_wgrad_scratch(M, D, n):
+        raise ValueError("lora_bwd_wgrad: gA [n*16, D], gB [n*D, 16] contiguous, dqkv [M, 3D], scratch of lora_wgrad_scratch(M, D, n) floats")
+    call("lora_bwd_wgrad", dqkv, dqkv.stride(-2), x, U, dU, gA, gB, scratch, scratch.numel(), M, D, n, *lora_cols(targets, D), s, *(rng or _NO_DROP))
+
+
+def lora_merge(W, A, Bw, targets, s):
+    """W [3D, D] bf16 (a COPY of the fused projection's weight): rows of target t = bf16(W + s B_t A_t)."""
+    D, n = W.shape[1], len(targets)
+    _lora_check("lora_merge", 1, D, n, None, W=W, A=A, Bw=Bw)
+    if W.shape[0] != 3 * D or A.numel() != n * LORA_RANK_PAD * D or Bw.numel() != A.numel():
+        raise ValueError("lora_merge: W [3D, D], A [n*16, D], Bw [n*D, 16]")
+    call("lora_merge", W, W.stride(0), A, Bw, D, n, *lora_cols(targets, D), s)
+    return W
+
+
+# ---------------------------------------------------------------------------------------------
 # generic caller for the remaining entry points: sig chars  p=pointer(tensor|None) i=int l=int64 f=float d=double
 # ---------------------------------------------------------------------------------------------
 _SIGS = {
@@ -499,6 +572,7 @@ _SIGS = {
     "router_bwd_det": "pppppppfpppiiiip", "ce_strided_det": "ppiilliffipp", "soft_xent_strided_det": "pppiillffffipp", "hardneg_strided_det": "ppiillffipp",
     "cos_scale_bwd_det": "ppppppiif",
     "sumsq": "plp", "sumsq_det": "plpp", "adam_step": "pppppldddddipff", "adam_groups_step": "ppppplpppidddddiipff", "cast_bf16": "ppl", "transpose_many": "pppii",
+    "lora_fwd": "pppppiiiiiiifllllf", "lora_bwd_dx": "pippppiiiiiifllllf", "lora_bwd_wgrad": "pippppppliiiiiifllllf", "lora_merge": "pippiiiiif",
     "grad_pack_bf16": "pplf", "sumsq_det_bf16": "plpp", "adam_step_g16": "pppppldddddipff", "adam_groups_step_g16": "ppppplpppidddddiipff",
 }
 
@@ -584,6 +658,10 @@ _COSTS = {
     "dropout_add_layernorm_fwd": lambda a: ("dropout_add_layernorm_fwd_kernel", 8.0 * a[8] * a[9], "byte"),    # z, residual read; x1, y written
     "attn_drop_fwd": lambda a: ("attn_drop_fwd_kernel", 4.0 * a[5] * a[5] * 64 * a[4] * a[6], "flop"),
     "attn_drop_bwd": lambda a: ("attn_drop_bwd_kernel", 10.0 * a[8] * a[8] * 64 * a[7] * a[9], "flop"),
+    # the adapters' own algorithmic traffic (a = the launch arguments): X once, the targeted qkv / dqkv columns, U / dU, dy
+    "lora_fwd": lambda a: ("lora_fwd_kernel", 2.0 * a[6] * (a[7] + 2 * a[8] * a[7] + a[8] * 16), "byte"),
+    "lora_bwd_dx": lambda a: ("lora_bwd_dx_kernel", 2.0 * a[6] * (a[8] * a[7] + a[8] * 16 + (2 * a[7] if a[5] is not None else 0)), "byte"),
+    "lora_bwd_wgrad": lambda a: ("lora_bwd_wgrad_kernel + lora_wgrad_reduce_kernel", 2.0 * a[9] * (a[11] * a[10] + a[10] + 2 * a[11] * 16), "byte"),
     "layernorm_fwd_rows": lambda a: ("layernorm_fwd_kernel", 4.0 * (ROWS_HINT or a[6]) * a[7], "byte"),
 }
 

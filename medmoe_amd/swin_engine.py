@@ -54,7 +54,7 @@ class SwinEngine:
         """kind (medmoe_amd.optim_groups) -> the arenas this engine steps."""
         out = {"swin_tower": self.enc.tower.store, "swin_moe": self.enc.store}
         if self.train_text:
-            out["text"] = self.eng.tstore
+            out["text"] = self.eng.text_arena()
         return out
 
     def apply_optimizer_groups(self):
@@ -109,7 +109,7 @@ class SwinEngine:
         eng, enc, c = self.eng, self.enc, self.cfg
         B = batch["image"].shape[0]
         if self.train_text and zero_grad:
-            eng.tstore.zero_grad()
+            eng.text_arena().zero_grad()
         out = self.forward(batch, self._drop_path_masks(B), training=True)
         eng.dropout_step += 1                                       # as Engine.train_step: one per call, the text pass above used the old value
         ws = eng.ws
@@ -162,7 +162,7 @@ class SwinEngine:
             if text_done is not None:                               # the text arena: one more all-reduce, averaged as Engine.train_step does
                 torch.cuda.current_stream().wait_event(text_done)
                 text_done = None
-                D_.allreduce_mean_(eng.tstore.g32, comm=eng.grad_comm(eng.tstore))
+                D_.allreduce_mean_(eng.text_arena().g32, comm=eng.grad_comm(eng.text_arena()))
         else:
             enc.backward(ws["d_img_g"], d_local.view(B, HW, D), labels=batch["label"], cls_weight=c.w_cls * loss_scale, zero_grad=zero_grad,
                          loss_parts=lp)
@@ -181,12 +181,12 @@ class SwinEngine:
         lr = c.lr if lr is None else lr
         torch.add(st_t.sumsq(), st_m.sumsq(), out=self._normsq)
         if self.train_text:
-            self._normsq.add_(self.eng.tstore.sumsq())
+            self._normsq.add_(self.eng.text_arena().sumsq())
         kw = dict(betas=tuple(c.adam_betas), eps=c.adam_eps, decoupled=c.optimizer == "adamw")
         st_t.adam_step(self._normsq, lr, c.weight_decay, c.clip, **kw)
         st_m.adam_step(self._normsq, lr, c.weight_decay, c.clip, **kw)
         if self.train_text:
-            self.eng.tstore.adam_step(self._normsq, lr, c.weight_decay, c.clip, **kw)
+            self.eng.text_arena().adam_step(self._normsq, lr, c.weight_decay, c.clip, **kw)
         self.enc.tower.refresh(cast=False)                          # patch-embedding pad form, bias tables
 
     def eval_step(self, batch: Dict[str, torch.Tensor]):

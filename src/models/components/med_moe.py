@@ -77,6 +77,19 @@ def _text_dropout(c: MedMoEConfig, text: Any) -> MedMoEConfig:
     c.text_hidden_dropout = float(_get(text, "hidden_dropout_prob", 0.0))
     c.text_attn_dropout = float(_get(text, "attention_probs_dropout_prob", 0.0))
     c.dropout_seed = int(_get(text, "dropout_seed", 0))
+    return _text_lora(c, text)
+
+
+def _text_lora(c: MedMoEConfig, text: Any) -> MedMoEConfig:
+    """model.model.text.lora / lora_r / lora_alpha / lora_dropout / lora_targets (the reference's names, med-moe.yaml:27-30, on the text tower:
+    peft-style adapters on the attention projections of a frozen BERT).  Absent keys leave the defaults: no adapters."""
+    c.text_lora = bool(_get(text, "lora", False))
+    c.text_lora_r = int(_get(text, "lora_r", c.text_lora_r))
+    c.text_lora_alpha = float(_get(text, "lora_alpha", c.text_lora_alpha))
+    c.text_lora_dropout = float(_get(text, "lora_dropout", 0.0))
+    tg = _get(text, "lora_targets", None)
+    if tg is not None:
+        c.text_lora_targets = (tg,) if isinstance(tg, str) else tuple(str(t) for t in tg)
     return c
 
 
@@ -142,6 +155,10 @@ class MedMoE(nn.Module):
                 state_dict[prefix + "image_encoder." + k[len(prefix + "swin."):]] = state_dict.pop(k)
         for k, v in module.engine.params.text.items():
             state_dict[prefix + "text_encoder." + k] = v
+        if module.engine.lora is not None:                           # text.lora: true - the adapters in peft's shapes ([r, D] / [D, r])
+            lo = module.engine.lora
+            for n in lo.true_names():
+                state_dict[prefix + "text_encoder." + n + ".weight"] = lo.true_view(lo.p32, n)
         return state_dict
 
     def _from_reference_keys(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
@@ -166,6 +183,10 @@ class MedMoE(nn.Module):
                 views = p.named_views()
                 for k in want & got:
                     views[k].copy_(named[k].to(views[k].device, views[k].dtype).reshape(views[k].shape))
+            if text and self.engine.lora is not None:             # text.lora: true - adapters into their arena, the rest into the frozen base
+                lora = {k: text.pop(k) for k in [k for k in text if ".lora_" in k]}
+                if lora:
+                    self.engine.lora.load_named(lora)
             if text:
                 if self.engine.tstore is not None:                # trainable text tower: into its flat master buffer
                     self.engine.tstore.load_named(text)
@@ -222,6 +243,9 @@ class MedMoE(nn.Module):
             ids, mask, tt = tok["ids"].to(self.device), tok["attn_mask"].to(self.device), tok.get("token_type")
         else:
             raise NotImplementedError("raw caption strings need a tokenizer: set_vocabulary(idxtoword, tokenizer) or pass token ids")
+        if self.cfg.text_lora and torch.is_grad_enabled():
+            raise NotImplementedError("text.lora: true trains through the fused step (model.fused_step: true -> Engine.train_step has the adapters' "
+                                      "backward); the torch-autograd mirror keeps the text tower frozen")
         if not self.cfg.freeze_text and torch.is_grad_enabled():
             raise NotImplementedError("text.freeze_bert: false trains through the fused step (model.fused_step: true -> Engine.train_step has the "
                                       "text backward); the torch-autograd mirror keeps the text tower frozen")

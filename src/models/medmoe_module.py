@@ -246,12 +246,12 @@ class MedMoEPretrainingLightningModule(_Base):
         if getattr(m, "swin", None) is not None:
             enc = m.swin._encoder()
             out = {"swin_tower": enc.tower.store, "swin_moe": enc.store}
-            if m.engine.tstore is not None:                          # text.freeze_bert: false - the text tower's Adam state travels too
-                out["text"] = m.engine.tstore
+            if m.engine.text_arena() is not None:                    # text.freeze_bert: false / text.lora: true - the text arena's Adam state travels too
+                out["text"] = m.engine.text_arena()
             return out
         out = {"image": m.engine.params}
-        if m.engine.tstore is not None:
-            out["text"] = m.engine.tstore
+        if m.engine.text_arena() is not None:
+            out["text"] = m.engine.text_arena()
         return out
 
     def on_save_checkpoint(self, checkpoint: Dict[str, Any]) -> None:
