@@ -403,6 +403,25 @@ long long medmoe_lora_wgrad_scratch(int M, int D, int n);
 /* W (bf16 [>= c_t + D rows][ldw], a copy of the fused projection's weight): rows c_t .. c_t + D - 1 = bf16(W + s B_t A_t) */
 int medmoe_lora_merge(void* W, int ldw, const void* A, const void* Bw, int D, int n, int c0, int c1, int c2, float s, hipStream_t stream);
 
+/* Variable-length backward of a TRAINABLE text tower: the text pass on the packed non-padding tokens of medmoe_text_pack.  Every
+   entry point takes the row count as a DEVICE int (count / rows_dev, 1 <= value <= the host-side bound that sizes the grid); rows at and past
+   the count are neither read for a result nor written, and reach no sum.
+   attn_bwd_varlen: medmoe_attn_bwd on medmoe_attn_fwd_varlen's layout - qkv / dqkv [sum len][3*H*64], out / dout [sum len][H*64], lse and
+   delta [B][H][Nmax]; Nmax <= 80, no key mask (every key of a sequence is valid). */
+int medmoe_attn_bwd_varlen(const void* qkv, const void* out, const void* dout, const float* lse, const int* seq_off, void* dqkv, float* delta, int B, int Nmax, int H, int head_dim, hipStream_t stream);
+/* medmoe_layernorm_bwd over the first min(rows, *rows_dev) rows; dgamma / dbeta may both be null */
+int medmoe_layernorm_bwd_rows(const void* dy, const void* x, const float* mean, const float* rstd, const float* gamma, const void* add, void* dx, float* dgamma, float* dbeta, int rows, int D, const int* rows_dev, hipStream_t stream);
+/* dH[r] = d_word[b, seg[src]] + d_sent[b] / T (0 where seg[src] < 0) for packed row r < *count, src = src_of_row[r], b = src / T */
+int medmoe_text_aggregate_bwd_packed(const float* d_word, const float* d_sent, const int* seg, const int* src_of_row, const int* count, void* dH, int B, int T, int D, hipStream_t stream);
+/* medmoe_text_embed_ln_bwd on packed dy rows: ids / type_ids read at src = src_of_row[r], position src % T; dx (fp32 [B*T][D], zeroed by the
+   caller) is written at row src; g_word / dgamma / dbeta accumulate (fp32 atomics) */
+int medmoe_text_embed_ln_bwd_packed(const int* ids, const int* type_ids, const float* word, const float* pos, const float* type, const float* gamma, const void* dy, float* dx, float* dgamma, float* dbeta, float* g_word, int B, int T, int D, int vocab, float eps, const int* src_of_row, const int* count, hipStream_t stream);
+/* medmoe_lora_fwd / _bwd_dx / _bwd_wgrad over the first min(M, *rows_dev) rows; the wgrad scratch is sized for M, a 256-row chunk past the
+   count adds exact zeros in the same fixed order */
+int medmoe_lora_fwd_rows(const void* X, const void* A, const void* Bw, void* U, void* qkv, int ldq, int M, int D, int n, int c0, int c1, int c2, float s, long long seed, long long step, long long site, long long thresh, float scale, const int* rows_dev, hipStream_t stream);
+int medmoe_lora_bwd_dx_rows(const void* dqkv, int ldq, const void* Bt, const void* At, void* dU, void* dy, int M, int D, int n, int c0, int c1, int c2, float s, long long seed, long long step, long long site, long long thresh, float scale, const int* rows_dev, hipStream_t stream);
+int medmoe_lora_bwd_wgrad_rows(const void* dqkv, int ldq, const void* X, const void* U, const void* dU, float* gA, float* gB, float* scratch, long long scratch_floats, int M, int D, int n, int c0, int c1, int c2, float s, long long seed, long long step, long long site, long long thresh, float scale, const int* rows_dev, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,6 +41,10 @@ class MedMoEConfig:
     text_lora_alpha: float = 16.0
     text_lora_dropout: float = 0.0
     text_lora_targets: Tuple[str, ...] = ("query", "value")
+    # variable-length pass of the TRAINABLE text tower (full or LoRA): forward and backward run on the packed non-padding tokens,
+    # as the frozen tower's forward does (same rule: B <= 1024 and T <= 80, else the padded pass).  Opt-in; MEDMOE_TEXT_TRAIN_VARLEN=1 switches
+    # it on too.  Hidden / LoRA dropout masks are then functions of the PACKED (row, column); attention dropout has no packed kernels
+    text_train_varlen: bool = False
     # deterministic mode (trainer.deterministic): no launch of a step whose result depends on the order in which workgroups or waves arrive -
     # staged or single-writer forms of every weight-gradient GEMM, LayerNorm / scale-attention parameter gradient and loss sum
     deterministic: bool = False
@@ -128,6 +132,10 @@ class MedMoEConfig:
                 raise ValueError(f"{key} must be in [0, 1), got {getattr(self, key)}")
         if not 0.0 <= float(self.text_lora_dropout) < 1.0:
             raise ValueError(f"text_lora_dropout must be in [0, 1), got {self.text_lora_dropout}")
+        if self.text_train_varlen and float(self.text_attn_dropout) > 0.0:
+            raise NotImplementedError("text_train_varlen (text.train_varlen: true) with text_attn_dropout > 0 (text.attention_probs_dropout_prob): "
+                                      "the attention-probability dropout kernels have no packed form yet - a named follow-up (DESIGN 3i); hidden "
+                                      "and LoRA dropout are supported")
         if self.text_lora:
             if not self.freeze_text:
                 raise ValueError("text_lora with freeze_text=False (text.freeze_bert: false): the adapters train on a FROZEN base tower - "

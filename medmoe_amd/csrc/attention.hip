@@ -273,7 +273,7 @@ __global__ __launch_bounds__(RT, 4) void attn_bwd_dq_kernel(const bf16_t* __rest
                                                           const bf16_t* __restrict__ dout, const float* __restrict__ lse,
                                                           const unsigned char* __restrict__ key_mask,
                                                           bf16_t* __restrict__ dqkv, float* __restrict__ delta,
-                                                          int N, int H, float scale) {
+                                                          int Nmax, int H, float scale, const int* __restrict__ seq_off) {
   using G = AttnGeom<NKT>;
   __shared__ __attribute__((aligned(16))) char smem[2 * G::RM_BYTES + G::NKP * 4];
   char* sK = smem;
@@ -283,14 +283,18 @@ __global__ __launch_bounds__(RT, 4) void attn_bwd_dq_kernel(const bf16_t* __rest
   const int b = blockIdx.x / H, h = blockIdx.x - b * H;
   const int D = H * HD;
   const long long rs = 3LL * D;
-  const bf16_t* base = qkv + (long long)b * N * rs + h * HD;
-  const bf16_t* obase = o + (long long)b * N * D + h * HD;
-  const bf16_t* dobase = dout + (long long)b * N * D + h * HD;
+  // seq_off (variable-length batches, as attn_fwd_kernel): sequence b = packed rows seq_off[b] .. seq_off[b+1], every key valid; lse / delta
+  // rows stay [Nmax] long
+  const long long row0 = seq_off ? (long long)seq_off[b] : (long long)b * Nmax;
+  const int N = seq_off ? max(1, min(seq_off[b + 1] - seq_off[b], Nmax)) : Nmax;
+  const bf16_t* base = qkv + row0 * rs + h * HD;
+  const bf16_t* obase = o + row0 * D + h * HD;
+  const bf16_t* dobase = dout + row0 * D + h * HD;
 
   fill_rowmajor<G::FILL, RT>(sK, base + D, rs, N, tid);
   fill_rowmajor<G::FILL, RT>(sV, base + 2 * D, rs, N, tid);
   for (int k = tid; k < G::NKP; k += RT)
-    sMask[k] = (k < N && (!key_mask || key_mask[(long long)b * N + k])) ? 0.f : -INFINITY;
+    sMask[k] = (k < N && (!key_mask || key_mask[(long long)b * Nmax + k])) ? 0.f : -INFINITY;
   __syncthreads();
 
   const int fr = lane & 15, g = lane >> 4;
@@ -325,8 +329,8 @@ __global__ __launch_bounds__(RT, 4) void attn_bwd_dq_kernel(const bf16_t* __rest
     dl += __shfl_xor(dl, 16, 64);
     dl += __shfl_xor(dl, 32, 64);
     const float c2 = scale * 1.44269504088896f;
-    const float nL2 = -lse[((long long)b * H + h) * N + qc] * 1.44269504088896f;     // p = 2^(s c2 - L log2 e)
-    if (g == 0 && q < N) delta[((long long)b * H + h) * N + q] = dl;
+    const float nL2 = -lse[((long long)b * H + h) * Nmax + qc] * 1.44269504088896f;     // p = 2^(s c2 - L log2 e)
+    if (g == 0 && q < N) delta[((long long)b * H + h) * Nmax + q] = dl;
 
     f32x4_t acc[4];
 #pragma unroll
@@ -375,7 +379,7 @@ __global__ __launch_bounds__(RT, 4) void attn_bwd_dq_kernel(const bf16_t* __rest
       for (int nd = 0; nd < 4; ++nd) {
         const f32x4_t v = acc[nd] * scale;
         uint2 pk; pk.x = pack2bf(v[0], v[1]); pk.y = pack2bf(v[2], v[3]);
-        *(uint2*)(dqkv + ((long long)b * N + q) * rs + h * HD + nd * 16 + g * 4) = pk;
+        *(uint2*)(dqkv + (row0 + q) * rs + h * HD + nd * 16 + g * 4) = pk;
       }
     }
 #pragma unroll
@@ -390,7 +394,8 @@ template <int NKT, int RT>
 __global__ __launch_bounds__(RT, 4) void attn_bwd_dkv_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dout,
                                                            const float* __restrict__ lse, const float* __restrict__ delta,
                                                            const unsigned char* __restrict__ key_mask,
-                                                           bf16_t* __restrict__ dqkv, int N, int H, float scale) {
+                                                           bf16_t* __restrict__ dqkv, int Nmax, int H, float scale,
+                                                           const int* __restrict__ seq_off) {
   using G = AttnGeom<NKT>;
   __shared__ __attribute__((aligned(16))) char smem[2 * G::RM_BYTES + G::NKP * 12];
   char* sQ = smem;
@@ -402,16 +407,18 @@ __global__ __launch_bounds__(RT, 4) void attn_bwd_dkv_kernel(const bf16_t* __res
   const int b = blockIdx.x / H, h = blockIdx.x - b * H;
   const int D = H * HD;
   const long long rs = 3LL * D;
-  const bf16_t* base = qkv + (long long)b * N * rs + h * HD;
-  const bf16_t* dobase = dout + (long long)b * N * D + h * HD;
+  const long long row0 = seq_off ? (long long)seq_off[b] : (long long)b * Nmax;            // as attn_bwd_dq_kernel
+  const int N = seq_off ? max(1, min(seq_off[b + 1] - seq_off[b], Nmax)) : Nmax;
+  const bf16_t* base = qkv + row0 * rs + h * HD;
+  const bf16_t* dobase = dout + row0 * D + h * HD;
 
   fill_rowmajor<G::FILL, RT>(sQ, base, rs, N, tid);
   fill_rowmajor<G::FILL, RT>(sDO, dobase, D, N, tid);
   for (int k = tid; k < G::NKP; k += RT) {
     const bool valid = k < N;
-    sMask[k] = (valid && (!key_mask || key_mask[(long long)b * N + k])) ? 0.f : -INFINITY;
-    sLse[k] = valid ? lse[((long long)b * H + h) * N + k] * 1.44269504088896f : INFINITY;    // exp2 domain; padded query rows -> p = 0
-    sDelta[k] = valid ? delta[((long long)b * H + h) * N + k] : 0.f;
+    sMask[k] = (valid && (!key_mask || key_mask[(long long)b * Nmax + k])) ? 0.f : -INFINITY;
+    sLse[k] = valid ? lse[((long long)b * H + h) * Nmax + k] * 1.44269504088896f : INFINITY;    // exp2 domain; padded query rows -> p = 0
+    sDelta[k] = valid ? delta[((long long)b * H + h) * Nmax + k] : 0.f;
   }
   __syncthreads();
 
@@ -487,7 +494,7 @@ __global__ __launch_bounds__(RT, 4) void attn_bwd_dkv_kernel(const bf16_t* __res
       }
     }
     if (key < N) {
-      bf16_t* row = dqkv + ((long long)b * N + key) * rs + h * HD;
+      bf16_t* row = dqkv + (row0 + key) * rs + h * HD;
 #pragma unroll
       for (int nd = 0; nd < 4; ++nd) {
         const f32x4_t kv = dk[nd] * scale;
@@ -932,11 +939,11 @@ template <int K, int RT>
 static void launch_bwd(const void* qkv, const void* out, const void* dout, const float* lse, const unsigned char* key_mask, void* dqkv,
                        float* delta, int B, int N, int H, float scale, hipStream_t stream) {
   if (key_mask) hipLaunchKernelGGL((attn_bwd_dq_kernel<K, true, RT>), dim3(B * H), dim3(RT), 0, stream, (const bf16_t*)qkv, (const bf16_t*)out,
-                                   (const bf16_t*)dout, lse, key_mask, (bf16_t*)dqkv, delta, N, H, scale);
+                                   (const bf16_t*)dout, lse, key_mask, (bf16_t*)dqkv, delta, N, H, scale, (const int*)nullptr);
   else hipLaunchKernelGGL((attn_bwd_dq_kernel<K, false, RT>), dim3(B * H), dim3(RT), 0, stream, (const bf16_t*)qkv, (const bf16_t*)out,
-                          (const bf16_t*)dout, lse, key_mask, (bf16_t*)dqkv, delta, N, H, scale);
+                          (const bf16_t*)dout, lse, key_mask, (bf16_t*)dqkv, delta, N, H, scale, (const int*)nullptr);
   hipLaunchKernelGGL((attn_bwd_dkv_kernel<K, RT>), dim3(B * H), dim3(RT), 0, stream, (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta,
-                     key_mask, (bf16_t*)dqkv, N, H, scale);
+                     key_mask, (bf16_t*)dqkv, N, H, scale, (const int*)nullptr);
 }
 
 extern "C" int medmoe_attn_fwd(const void* qkv, void* out, float* lse, const unsigned char* key_mask,
@@ -994,5 +1001,18 @@ extern "C" int medmoe_attn_bwd(const void* qkv, const void* out, const void* dou
   else if (nkt == 13) launch_bwd<13, 512>(qkv, out, dout, lse, key_mask, dqkv, delta, B, N, H, scale, stream);
   else if (nkt == 17) launch_bwd<17, 512>(qkv, out, dout, lse, key_mask, dqkv, delta, B, N, H, scale, stream);
   else launch_bwd<37, 1024>(qkv, out, dout, lse, key_mask, dqkv, delta, B, N, H, scale, stream);
+  return mm_check_launch();
+}
+
+// Backward over a PACKED variable-length batch (medmoe_attn_fwd_varlen's layout): qkv / dqkv [sum len, 3*H*64], out / dout [sum len, H*64],
+// lse (of the forward) and delta (written here) [B][H][Nmax]; Nmax <= 80 (the 5-tile resident build), every key of a sequence valid.
+extern "C" int medmoe_attn_bwd_varlen(const void* qkv, const void* out, const void* dout, const float* lse, const int* seq_off, void* dqkv,
+                                      float* delta, int B, int Nmax, int H, int head_dim, hipStream_t stream) {
+  if (!qkv || !out || !dout || !lse || !seq_off || !dqkv || !delta) return MM_ERR_ARG;
+  if (head_dim != HD || B <= 0 || H <= 0 || Nmax <= 0 || Nmax > 80) return MM_ERR_SHAPE;
+  hipLaunchKernelGGL((attn_bwd_dq_kernel<5, false, 256>), dim3(B * H), dim3(256), 0, stream, (const bf16_t*)qkv, (const bf16_t*)out,
+                     (const bf16_t*)dout, lse, (const unsigned char*)nullptr, (bf16_t*)dqkv, delta, Nmax, H, 0.125f, seq_off);
+  hipLaunchKernelGGL((attn_bwd_dkv_kernel<5, 256>), dim3(B * H), dim3(256), 0, stream, (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta,
+                     (const unsigned char*)nullptr, (bf16_t*)dqkv, Nmax, H, 0.125f, seq_off);
   return mm_check_launch();
 }

@@ -428,13 +428,16 @@ extern "C" int medmoe_text_aggregate_packed(const void* h0, const void* h1, cons
 // the hidden states; sent[b] = (1 / T) sum_w word[b, w].  Every selected layer's hidden state therefore receives the SAME gradient:
 // dH[b, t] = d_word[b, seg[b, t]] + d_sent[b] / T for kept tokens, 0 for dropped ones.
 __global__ __launch_bounds__(256) void text_aggregate_bwd_kernel(const float* __restrict__ d_word, const float* __restrict__ d_sent,
-                                                                 const int* __restrict__ seg, bf16_t* __restrict__ dH, int rows, int T, int D) {
+                                                                 const int* __restrict__ seg, bf16_t* __restrict__ dH, int rows, int T, int D,
+                                                                 const int* __restrict__ src_of_row, const int* __restrict__ rows_dev) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int n4 = D >> 2;
   const float invT = 1.f / (float)T;
+  if (rows_dev) rows = min(rows, *rows_dev);              // packed rows (text_pack): row r holds token src_of_row[r] = b * T + t
   for (int row = blockIdx.x * 4 + wid; row < rows; row += gridDim.x * 4) {
-    const int b = row / T;
-    const int w = seg[row];
+    const int src = src_of_row ? src_of_row[row] : row;
+    const int b = src / T;
+    const int w = seg[src];
     for (int c = lane; c < n4; c += 64) {
       uint2 o = make_uint2(0u, 0u);
       if (w >= 0) {
@@ -456,7 +459,20 @@ extern "C" int medmoe_text_aggregate_bwd(const float* d_word, const float* d_sen
   if (!seg || !dH || (!d_word && !d_sent)) return MM_ERR_ARG;
   if (B <= 0 || T <= 0 || D <= 0 || (D % 4)) return MM_ERR_SHAPE;
   const int rows = B * T;
-  hipLaunchKernelGGL(text_aggregate_bwd_kernel, dim3(min((rows + 3) / 4, 256 * 8)), dim3(256), 0, stream, d_word, d_sent, seg, (bf16_t*)dH, rows, T, D);
+  hipLaunchKernelGGL(text_aggregate_bwd_kernel, dim3(min((rows + 3) / 4, 256 * 8)), dim3(256), 0, stream, d_word, d_sent, seg, (bf16_t*)dH, rows, T, D,
+                     (const int*)nullptr, (const int*)nullptr);
+  return mm_check_launch();
+}
+
+// the same for PACKED hidden states (text_pack): dH[r] = d_word[b, seg[src]] + d_sent[b] / T for packed row r < *count, src = src_of_row[r],
+// b = src / T - the padded kernel's row src, bit for bit.  Rows at and past the count are not written.
+extern "C" int medmoe_text_aggregate_bwd_packed(const float* d_word, const float* d_sent, const int* seg, const int* src_of_row, const int* count,
+                                                void* dH, int B, int T, int D, hipStream_t stream) {
+  if (!seg || !dH || !src_of_row || !count || (!d_word && !d_sent)) return MM_ERR_ARG;
+  if (B <= 0 || T <= 0 || D <= 0 || (D % 4)) return MM_ERR_SHAPE;
+  const int rows = B * T;
+  hipLaunchKernelGGL(text_aggregate_bwd_kernel, dim3(min((rows + 3) / 4, 256 * 8)), dim3(256), 0, stream, d_word, d_sent, seg, (bf16_t*)dH, rows, T, D,
+                     src_of_row, count);
   return mm_check_launch();
 }
 
@@ -468,7 +484,8 @@ __global__ __launch_bounds__(256) void text_embed_ln_bwd_kernel(const int* __res
                                                                 const float* __restrict__ pos, const float* __restrict__ type,
                                                                 const float* __restrict__ gamma, const bf16_t* __restrict__ dy,
                                                                 float* __restrict__ dx, float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                                float* __restrict__ g_word, int rows, int T, int D, int vocab, float eps) {
+                                                                float* __restrict__ g_word, int rows, int T, int D, int vocab, float eps,
+                                                                const int* __restrict__ src_of_row, const int* __restrict__ rows_dev) {
   __shared__ float red[2][4][2048];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int n4 = D >> 2;
@@ -477,10 +494,12 @@ __global__ __launch_bounds__(256) void text_embed_ln_bwd_kernel(const int* __res
   for (int i = 0; i < 8; ++i)
 #pragma unroll
     for (int e = 0; e < 4; ++e) { ag[i][e] = 0.f; ab[i][e] = 0.f; }
+  if (rows_dev) rows = min(rows, *rows_dev);              // packed rows (text_pack): dy row r belongs to token src_of_row[r], dx goes to row src
   for (int row = blockIdx.x * 4 + wid; row < rows; row += gridDim.x * 4) {
-    const int t = row % T;
-    int id = ids[row]; id = min(max(id, 0), vocab - 1);
-    const int tt = tts ? min(max(tts[row], 0), 1) : 0;
+    const int src = src_of_row ? src_of_row[row] : row;
+    const int t = src % T;
+    int id = ids[src]; id = min(max(id, 0), vocab - 1);
+    const int tt = tts ? min(max(tts[src], 0), 1) : 0;
     float4 v[8];
     float s = 0.f;
 #pragma unroll
@@ -533,7 +552,7 @@ __global__ __launch_bounds__(256) void text_embed_ln_bwd_kernel(const int* __res
         float o[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) o[e] = rstd * (dgv[i][e] - m1 - xv[e] * m2);
-        *(float4*)(dx + (long long)row * D + c * 4) = make_float4(o[0], o[1], o[2], o[3]);
+        *(float4*)(dx + (long long)src * D + c * 4) = make_float4(o[0], o[1], o[2], o[3]);
 #pragma unroll
         for (int e = 0; e < 4; ++e) atomicAdd(g_word + (long long)id * D + c * 4 + e, o[e]);
       }
@@ -562,7 +581,22 @@ extern "C" int medmoe_text_embed_ln_bwd(const int* ids, const int* type_ids, con
   const int rows = B * T;
   ++g_mm_nondet;                                    // word rows shared by tokens and dgamma / dbeta meet in atomics
   hipLaunchKernelGGL(text_embed_ln_bwd_kernel, dim3(min((rows + 3) / 4, 256 * 4)), dim3(256), 0, stream, ids, type_ids, word, pos, type, gamma,
-                     (const bf16_t*)dy, dx, dgamma, dbeta, g_word, rows, T, D, vocab, eps);
+                     (const bf16_t*)dy, dx, dgamma, dbeta, g_word, rows, T, D, vocab, eps, (const int*)nullptr, (const int*)nullptr);
+  return mm_check_launch();
+}
+
+// the same on PACKED rows (text_pack): dy row r < *count is the gradient of token src = src_of_row[r] (id and token type read at src, position
+// src % T); dx goes to row src of the PADDED fp32 [B*T, D] buffer, which the caller zeroes first (the rows of padding tokens are not written),
+// so the position / token-type sums over it stay as they are; g_word / dgamma / dbeta accumulate as above.
+extern "C" int medmoe_text_embed_ln_bwd_packed(const int* ids, const int* type_ids, const float* word, const float* pos, const float* type,
+                                               const float* gamma, const void* dy, float* dx, float* dgamma, float* dbeta, float* g_word, int B,
+                                               int T, int D, int vocab, float eps, const int* src_of_row, const int* count, hipStream_t stream) {
+  if (!ids || !word || !pos || !type || !gamma || !dy || !dx || !dgamma || !dbeta || !g_word || !src_of_row || !count) return MM_ERR_ARG;
+  if (B <= 0 || T <= 0 || D <= 0 || (D % 4) || D > 2048 || vocab <= 0) return MM_ERR_SHAPE;
+  const int rows = B * T;
+  ++g_mm_nondet;                                    // word rows shared by tokens and dgamma / dbeta meet in atomics
+  hipLaunchKernelGGL(text_embed_ln_bwd_kernel, dim3(min((rows + 3) / 4, 256 * 4)), dim3(256), 0, stream, ids, type_ids, word, pos, type, gamma,
+                     (const bf16_t*)dy, dx, dgamma, dbeta, g_word, rows, T, D, vocab, eps, src_of_row, count);
   return mm_check_launch();
 }
 

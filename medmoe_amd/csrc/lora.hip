@@ -49,10 +49,11 @@ __device__ __forceinline__ uint4 keep8(uint4 v, const DropRng& rng, long long ro
 template <int NT, bool DROP>
 __global__ __launch_bounds__(256) void lora_fwd_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ A, const bf16_t* __restrict__ Bw,
                                                        bf16_t* __restrict__ U, bf16_t* __restrict__ qkv, int ldq, int M, int D, LoraCols cols,
-                                                       float s, DropRng rng) {
+                                                       float s, DropRng rng, const int* __restrict__ rows_dev) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int r = lane & 15, g = lane >> 4;
   const long long row0 = ((long long)blockIdx.x * 4 + wid) * 16;
+  if (rows_dev) M = min(M, *rows_dev);             // the *_rows entry points: the first *rows_dev rows only (packed variable-length batches)
   if (row0 >= M) return;
   const long long m = row0 + r;
   const bool mok = m < M;
@@ -110,10 +111,11 @@ __global__ __launch_bounds__(256) void lora_fwd_kernel(const bf16_t* __restrict_
 template <int NT, bool DROP>
 __global__ __launch_bounds__(256) void lora_bwd_dx_kernel(const bf16_t* __restrict__ dqkv, int ldq, const bf16_t* __restrict__ Bt,
                                                           const bf16_t* __restrict__ At, bf16_t* __restrict__ dU, bf16_t* __restrict__ dy, int M,
-                                                          int D, LoraCols cols, float s, DropRng rng) {
+                                                          int D, LoraCols cols, float s, DropRng rng, const int* __restrict__ rows_dev) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int r = lane & 15, g = lane >> 4;
   const long long row0 = ((long long)blockIdx.x * 4 + wid) * 16;
+  if (rows_dev) M = min(M, *rows_dev);
   if (row0 >= M) return;
   const long long m = row0 + r;
   const bool mok = m < M;
@@ -188,13 +190,15 @@ __device__ __forceinline__ uint4 lds_col8(const bf16_t* p, int pitch) {       //
 template <int NT, bool DROP>
 __global__ __launch_bounds__(256) void lora_bwd_wgrad_kernel(const bf16_t* __restrict__ dqkv, int ldq, const bf16_t* __restrict__ X,
                                                              const bf16_t* __restrict__ U, const bf16_t* __restrict__ dU, float* __restrict__ part,
-                                                             int M, int D, LoraCols cols, float s, DropRng rng) {
+                                                             int M, int D, LoraCols cols, float s, DropRng rng,
+                                                             const int* __restrict__ rows_dev) {
   constexpr int PP = NT * LR + 2;
   __shared__ __attribute__((aligned(16))) bf16_t Qs[NT + 1][32][WG_PITCH];
   __shared__ __attribute__((aligned(16))) bf16_t Ps[2][32][PP];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int r = lane & 15, g = lane >> 4;
   const int chunk = blockIdx.x, cb = blockIdx.y * WG_COLS;
+  if (rows_dev) M = min(M, *rows_dev);             // a chunk past the count runs no step and stores exact zeros: the second pass keeps its chunk order
   const long long mbeg = (long long)chunk * WG_ROWS;
   const long long mend = mbeg + WG_ROWS < M ? mbeg + WG_ROWS : M;
   const int gpr = D >> 2;
@@ -318,29 +322,54 @@ static int lora_check(int ld, int M, int D, int n, int c0, int c1, int c2, LoraC
            else hipLaunchKernelGGL((KERNEL<3, false>), grid, dim3(256), 0, stream, __VA_ARGS__); }                             \
   } while (0)
 
-extern "C" int medmoe_lora_fwd(const void* X, const void* A, const void* Bw, void* U, void* qkv, int ldq, int M, int D, int n, int c0, int c1,
-                               int c2, float s, long long seed, long long step, long long site, long long thresh, float scale,
-                               hipStream_t stream) {
+static int lora_fwd_impl(const void* X, const void* A, const void* Bw, void* U, void* qkv, int ldq, int M, int D, int n, int c0, int c1,
+                         int c2, float s, long long seed, long long step, long long site, long long thresh, float scale,
+                         const int* rows_dev, hipStream_t stream) {
   if (!X || !A || !Bw || !U || !qkv) return MM_ERR_ARG;
   LoraCols cols;
   if (int rc = lora_check(ldq, M, D, n, c0, c1, c2, &cols)) return rc;
   const DropRng rng = make_drop_rng(seed, step, site, thresh, scale);
   const dim3 grid((unsigned)((M + 63) / 64));
-  LORA_DISPATCH(lora_fwd_kernel, grid, (const bf16_t*)X, (const bf16_t*)A, (const bf16_t*)Bw, (bf16_t*)U, (bf16_t*)qkv, ldq, M, D, cols, s, rng);
+  LORA_DISPATCH(lora_fwd_kernel, grid, (const bf16_t*)X, (const bf16_t*)A, (const bf16_t*)Bw, (bf16_t*)U, (bf16_t*)qkv, ldq, M, D, cols, s, rng,
+                rows_dev);
   return mm_check_launch();
 }
+extern "C" int medmoe_lora_fwd(const void* X, const void* A, const void* Bw, void* U, void* qkv, int ldq, int M, int D, int n, int c0, int c1,
+                               int c2, float s, long long seed, long long step, long long site, long long thresh, float scale,
+                               hipStream_t stream) {
+  return lora_fwd_impl(X, A, Bw, U, qkv, ldq, M, D, n, c0, c1, c2, s, seed, step, site, thresh, scale, nullptr, stream);
+}
+// the *_rows forms: the same kernels over the first min(M, *rows_dev) rows (rows_dev: device int; M bounds the grid).  Rows at and past the
+// count are neither read nor written; the dropout mask of element (row, column) is the one the plain form draws.
+extern "C" int medmoe_lora_fwd_rows(const void* X, const void* A, const void* Bw, void* U, void* qkv, int ldq, int M, int D, int n, int c0,
+                                    int c1, int c2, float s, long long seed, long long step, long long site, long long thresh, float scale,
+                                    const int* rows_dev, hipStream_t stream) {
+  if (!rows_dev) return MM_ERR_ARG;
+  return lora_fwd_impl(X, A, Bw, U, qkv, ldq, M, D, n, c0, c1, c2, s, seed, step, site, thresh, scale, rows_dev, stream);
+}
 
-extern "C" int medmoe_lora_bwd_dx(const void* dqkv, int ldq, const void* Bt, const void* At, void* dU, void* dy, int M, int D, int n, int c0,
-                                  int c1, int c2, float s, long long seed, long long step, long long site, long long thresh, float scale,
-                                  hipStream_t stream) {
+static int lora_bwd_dx_impl(const void* dqkv, int ldq, const void* Bt, const void* At, void* dU, void* dy, int M, int D, int n, int c0,
+                            int c1, int c2, float s, long long seed, long long step, long long site, long long thresh, float scale,
+                            const int* rows_dev, hipStream_t stream) {
   if (!dqkv || !Bt || !At || !dU) return MM_ERR_ARG;
   LoraCols cols;
   if (int rc = lora_check(ldq, M, D, n, c0, c1, c2, &cols)) return rc;
   const DropRng rng = make_drop_rng(seed, step, site, thresh, scale);
   const dim3 grid((unsigned)((M + 63) / 64));
   LORA_DISPATCH(lora_bwd_dx_kernel, grid, (const bf16_t*)dqkv, ldq, (const bf16_t*)Bt, (const bf16_t*)At, (bf16_t*)dU, (bf16_t*)dy, M, D, cols, s,
-                rng);
+                rng, rows_dev);
   return mm_check_launch();
+}
+extern "C" int medmoe_lora_bwd_dx(const void* dqkv, int ldq, const void* Bt, const void* At, void* dU, void* dy, int M, int D, int n, int c0,
+                                  int c1, int c2, float s, long long seed, long long step, long long site, long long thresh, float scale,
+                                  hipStream_t stream) {
+  return lora_bwd_dx_impl(dqkv, ldq, Bt, At, dU, dy, M, D, n, c0, c1, c2, s, seed, step, site, thresh, scale, nullptr, stream);
+}
+extern "C" int medmoe_lora_bwd_dx_rows(const void* dqkv, int ldq, const void* Bt, const void* At, void* dU, void* dy, int M, int D, int n, int c0,
+                                       int c1, int c2, float s, long long seed, long long step, long long site, long long thresh, float scale,
+                                       const int* rows_dev, hipStream_t stream) {
+  if (!rows_dev) return MM_ERR_ARG;
+  return lora_bwd_dx_impl(dqkv, ldq, Bt, At, dU, dy, M, D, n, c0, c1, c2, s, seed, step, site, thresh, scale, rows_dev, stream);
 }
 
 extern "C" long long medmoe_lora_wgrad_scratch(int M, int D, int n) {
@@ -348,9 +377,9 @@ extern "C" long long medmoe_lora_wgrad_scratch(int M, int D, int n) {
   return (long long)((M + WG_ROWS - 1) / WG_ROWS) * n * 2 * LR * D;
 }
 
-extern "C" int medmoe_lora_bwd_wgrad(const void* dqkv, int ldq, const void* X, const void* U, const void* dU, float* gA, float* gB, float* scratch,
-                                     long long scratch_floats, int M, int D, int n, int c0, int c1, int c2, float s, long long seed,
-                                     long long step, long long site, long long thresh, float scale, hipStream_t stream) {
+static int lora_bwd_wgrad_impl(const void* dqkv, int ldq, const void* X, const void* U, const void* dU, float* gA, float* gB, float* scratch,
+                               long long scratch_floats, int M, int D, int n, int c0, int c1, int c2, float s, long long seed,
+                               long long step, long long site, long long thresh, float scale, const int* rows_dev, hipStream_t stream) {
   if (!dqkv || !X || !U || !dU || !gA || !gB || !scratch) return MM_ERR_ARG;
   LoraCols cols;
   if (int rc = lora_check(ldq, M, D, n, c0, c1, c2, &cols)) return rc;
@@ -359,12 +388,27 @@ extern "C" int medmoe_lora_bwd_wgrad(const void* dqkv, int ldq, const void* X, c
   const int nchunk = (M + WG_ROWS - 1) / WG_ROWS;
   const dim3 grid((unsigned)nchunk, (unsigned)((D + WG_COLS - 1) / WG_COLS));
   LORA_DISPATCH(lora_bwd_wgrad_kernel, grid, (const bf16_t*)dqkv, ldq, (const bf16_t*)X, (const bf16_t*)U, (const bf16_t*)dU, scratch, M, D, cols,
-                s, rng);
+                s, rng, rows_dev);
   if (int rc = mm_check_launch()) return rc;
   const long long total = (long long)n * 2 * LR * D;
   hipLaunchKernelGGL(lora_wgrad_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, (const float*)scratch, nchunk, n, D, gA,
                      gB);
   return mm_check_launch();
+}
+extern "C" int medmoe_lora_bwd_wgrad(const void* dqkv, int ldq, const void* X, const void* U, const void* dU, float* gA, float* gB, float* scratch,
+                                     long long scratch_floats, int M, int D, int n, int c0, int c1, int c2, float s, long long seed,
+                                     long long step, long long site, long long thresh, float scale, hipStream_t stream) {
+  return lora_bwd_wgrad_impl(dqkv, ldq, X, U, dU, gA, gB, scratch, scratch_floats, M, D, n, c0, c1, c2, s, seed, step, site, thresh, scale, nullptr,
+                             stream);
+}
+// scratch: medmoe_lora_wgrad_scratch(M, D, n) floats (M chunks); a 256-row chunk past the count contributes exact zeros to the fixed-order sum
+extern "C" int medmoe_lora_bwd_wgrad_rows(const void* dqkv, int ldq, const void* X, const void* U, const void* dU, float* gA, float* gB,
+                                          float* scratch, long long scratch_floats, int M, int D, int n, int c0, int c1, int c2, float s,
+                                          long long seed, long long step, long long site, long long thresh, float scale, const int* rows_dev,
+                                          hipStream_t stream) {
+  if (!rows_dev) return MM_ERR_ARG;
+  return lora_bwd_wgrad_impl(dqkv, ldq, X, U, dU, gA, gB, scratch, scratch_floats, M, D, n, c0, c1, c2, s, seed, step, site, thresh, scale, rows_dev,
+                             stream);
 }
 
 extern "C" int medmoe_lora_merge(void* W, int ldw, const void* A, const void* Bw, int D, int n, int c0, int c1, int c2, float s,

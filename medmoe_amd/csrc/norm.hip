@@ -126,7 +126,8 @@ __global__ __launch_bounds__(LNB_WAVES * 64) void layernorm_bwd_kernel(const bf1
                                                             const float* __restrict__ mean, const float* __restrict__ rstd,
                                                             const float* __restrict__ gamma, const bf16_t* __restrict__ add,
                                                             bf16_t* __restrict__ dx, float* __restrict__ dgamma,
-                                                            float* __restrict__ dbeta, int rows, int D, float* __restrict__ part) {
+                                                            float* __restrict__ dbeta, int rows, int D, float* __restrict__ part,
+                                                            const int* __restrict__ rows_dev) {
   static_assert(LPR == 64 || NCH == 1, "several rows per wave only for rows of one chunk slot");
   constexpr int RPW = 64 / LPR;
   __shared__ float red[2][LNB_WAVES][512];   // [dgamma|dbeta][wave][lane*8+e] for one chunk slot at a time
@@ -138,6 +139,7 @@ __global__ __launch_bounds__(LNB_WAVES * 64) void layernorm_bwd_kernel(const bf1
   for (int i = 0; i < NCH; ++i)
 #pragma unroll
     for (int e = 0; e < 8; ++e) { ag[i][e] = 0.f; ab[i][e] = 0.f; }
+  if (rows_dev) rows = min(rows, *rows_dev);              // packed variable-length batches (layernorm_fwd_kernel): a workgroup past the count adds zeros
 
   for (int r0 = (blockIdx.x * LNB_WAVES + wid) * RPW; r0 < rows; r0 += gridDim.x * LNB_WAVES * RPW) {
     const int row = min(r0 + sub, rows - 1);
@@ -241,7 +243,8 @@ __global__ __launch_bounds__(1024) void layernorm_bwd_reduce_kernel(const float*
 
 static int layernorm_bwd_impl(const void* dy, const void* x, const float* mean, const float* rstd,
                               const float* gamma, const void* add, void* dx, float* dgamma,
-                              float* dbeta, int rows, int D, bool det, float* scratch, long long scratch_floats, hipStream_t stream) {
+                              float* dbeta, int rows, int D, bool det, float* scratch, long long scratch_floats, hipStream_t stream,
+                              const int* rows_dev = nullptr) {
   if (!dy || !x || !mean || !rstd || !gamma || !dx) return MM_ERR_ARG;
   if ((dgamma == nullptr) != (dbeta == nullptr)) return MM_ERR_ARG;
   if (rows <= 0 || D <= 0 || (D % 8) || D > 64 * 8 * LN_MAX_CHUNKS) return MM_ERR_SHAPE;
@@ -255,9 +258,9 @@ static int layernorm_bwd_impl(const void* dy, const void* x, const float* mean, 
     part = scratch;
   } else if (dgamma && grid > 1) ++g_mm_nondet;
 #define LN_BWD(N) hipLaunchKernelGGL((layernorm_bwd_kernel<N>), dim3(grid), dim3(LNB_WAVES * 64), 0, stream, (const bf16_t*)dy, \
-                                     (const bf16_t*)x, mean, rstd, gamma, (const bf16_t*)add, (bf16_t*)dx, dgamma, dbeta, rows, D, part)
+                                     (const bf16_t*)x, mean, rstd, gamma, (const bf16_t*)add, (bf16_t*)dx, dgamma, dbeta, rows, D, part, rows_dev)
 #define LN_BWD_L(L) hipLaunchKernelGGL((layernorm_bwd_kernel<1, L>), dim3(grid), dim3(LNB_WAVES * 64), 0, stream, (const bf16_t*)dy, \
-                                       (const bf16_t*)x, mean, rstd, gamma, (const bf16_t*)add, (bf16_t*)dx, dgamma, dbeta, rows, D, part)
+                                       (const bf16_t*)x, mean, rstd, gamma, (const bf16_t*)add, (bf16_t*)dx, dgamma, dbeta, rows, D, part, rows_dev)
   if (lpr == 16) LN_BWD_L(16); else if (lpr == 32) LN_BWD_L(32); else if (nch == 1) LN_BWD(1); else if (nch == 2) LN_BWD(2); else if (nch == 3) LN_BWD(3); else LN_BWD(4);
   if (part) hipLaunchKernelGGL(layernorm_bwd_reduce_kernel, dim3((2 * D / 4 + 63) / 64), dim3(64, 16), 0, stream, part, grid, D, dgamma, dbeta);
   return mm_check_launch();
@@ -275,6 +278,15 @@ extern "C" int medmoe_layernorm_bwd_det(const void* dy, const void* x, const flo
                                         const float* gamma, const void* add, void* dx, float* dgamma,
                                         float* dbeta, int rows, int D, float* scratch, long long scratch_floats, hipStream_t stream) {
   return layernorm_bwd_impl(dy, x, mean, rstd, gamma, add, dx, dgamma, dbeta, rows, D, true, scratch, scratch_floats, stream);
+}
+
+// medmoe_layernorm_bwd over the first min(rows, *rows_dev) rows (rows_dev: device int; the pattern of medmoe_layernorm_fwd_rows): the grid is
+// sized for `rows`, rows at and past the count are neither read nor written and reach no sum.  dgamma / dbeta may both be null.
+extern "C" int medmoe_layernorm_bwd_rows(const void* dy, const void* x, const float* mean, const float* rstd, const float* gamma,
+                                         const void* add, void* dx, float* dgamma, float* dbeta, int rows, int D, const int* rows_dev,
+                                         hipStream_t stream) {
+  if (!rows_dev) return MM_ERR_ARG;
+  return layernorm_bwd_impl(dy, x, mean, rstd, gamma, add, dx, dgamma, dbeta, rows, D, false, nullptr, 0, stream, rows_dev);
 }
 
 extern "C" long long medmoe_layernorm_bwd_det_scratch(int D) { return 512ll * 2 * D; }      // the grid never passes 512 workgroups

@@ -79,6 +79,51 @@ class VocabTables:
         return seg.to(I32).contiguous(), (n_real + 1).to(I32).contiguous()
 
 
+class _TextRows:
+    """The launches of a TRAINABLE text pass that depend on the row layout, for `_forward_text_train`, `backward_text` and `_backward_text_lora`
+    (one copy of the layer loops for both layouts).  padded: all B x T rows, key-masked attention - exactly the launches those functions made
+    before this class existed.  packed: `text_pack` runs here; every launch then takes the device-side row count `cnt` (the first
+    `cnt` rows of the same buffers hold the non-padding tokens in (caption, position) order), attention the sequence offsets, the weight
+    gradients one row range [0, cnt] - nothing is copied to the host."""
+
+    def __init__(self, eng, km: torch.Tensor, packed: bool):
+        c = eng.cfg
+        self.packed, self.km = packed, km
+        self.B, self.T, self.H, self.Dt, self.eps = eng.B, c.max_len, c.n_head_t, c.d_t, c.eps_t
+        self.tok_row = self.src_row = self.seq_off = self.row_off = self.cnt = None
+        if packed:
+            pk, Mt, B = eng.ws["tpack"], eng.B * c.max_len, eng.B
+            self.tok_row, self.src_row, self.seq_off = pk[:Mt], pk[Mt:2 * Mt], pk[2 * Mt:2 * Mt + B + 1]
+            self.row_off, self.cnt = pk[2 * Mt + B + 2:2 * Mt + B + 4], pk[2 * Mt + B + 3:2 * Mt + B + 4]      # [0, count] and its second element
+            ops.call("text_pack", km, self.tok_row, self.src_row, self.seq_off, self.cnt, B, self.T)
+
+    def gemm(self, a, w, out, **kw):
+        return ops.gemm_nt_rows(a, w, out, self.cnt, **kw) if self.packed else ops.gemm_nt(a, w, out, **kw)
+
+    def wgrad(self, g, x, dw, db=None):
+        if self.packed:            # the grouped form with ONE group: the row ranges are enumerated from row_off on the device, M bounds them
+            return ops.gemm_tn(g, x, dw, db=db, row_off=self.row_off, n_groups=1, M=self.B * self.T)
+        return ops.gemm_tn(g, x, dw, db=db)
+
+    def ln(self, x, gamma, beta, y, st):
+        if self.packed:
+            return ops.call("layernorm_fwd_rows", x, gamma, beta, y, st[0], st[1], self.B * self.T, self.Dt, self.eps, 0, self.cnt)
+        return ops.layernorm_fwd(x, gamma, beta, y, st[0], st[1], self.eps)
+
+    def ln_bwd(self, dy, x, mean, rstd, gamma, dx, dgamma=None, dbeta=None):
+        return ops.layernorm_bwd(dy, x, mean, rstd, gamma, dx, dgamma, dbeta, rows_dev=self.cnt)
+
+    def attn(self, qkv, out, lse):
+        if self.packed:
+            return ops.call("attn_fwd_varlen", qkv, out, lse, self.seq_off, self.B, self.T, self.H, 64)
+        return ops.attn_fwd(qkv, out, lse, self.km, self.B, self.T, self.H)
+
+    def attn_bwd(self, qkv, out, dout, lse, dqkv, delta):
+        if self.packed:
+            return ops.attn_bwd_varlen(qkv, out, dout, lse, self.seq_off, dqkv, delta, self.B, self.T, self.H)
+        return ops.attn_bwd(qkv, out, dout, lse, self.km, dqkv, delta, self.B, self.T, self.H)
+
+
 class Engine:
     def __init__(self, cfg: MedMoEConfig, device="cuda:0", seed: int = 0, vocab: Optional[VocabTables] = None):
         cfg.validate()
@@ -154,6 +199,14 @@ class Engine:
         # LDS-tiled pair kernels exist for 64 / 208 / 256 regions; any other geometry (576 regions of ViT-L/14 at 336 px) runs
         # the generic GEMM formulation (medmoe_amd/local_generic.py)
         self.text_varlen = os.environ.get("MEDMOE_TEXT_VARLEN", "1") != "0" and not self.train_text
+        # the TRAINABLE tower's packed pass (cfg.text_train_varlen or MEDMOE_TEXT_TRAIN_VARLEN=1): forward, backward and eval_step on the
+        # non-padding tokens, under the frozen path's rule (B <= 1024 and T <= 80, else the padded pass); text_train_varlen_active: which one ran
+        self.text_train_varlen = self.train_text and (bool(cfg.text_train_varlen) or os.environ.get("MEDMOE_TEXT_TRAIN_VARLEN", "0") == "1")
+        self.text_train_varlen_active = False
+        self._tp = None                                              # _TextRows of the last trainable text pass: backward_text takes the same launches
+        if self.text_train_varlen and cfg.text_attn_dropout > 0.0:
+            raise NotImplementedError("text_train_varlen (MEDMOE_TEXT_TRAIN_VARLEN=1) with text_attn_dropout > 0: the attention-probability "
+                                      "dropout kernels have no packed form yet (DESIGN 3i)")
         self.local_fast = ops.local_fast_path(cfg.n_patch, cfg.max_len)
         # transposed pair matrices + one wave per (image, caption, word tile): geometries pair3.hip is instantiated for (196 / 64
         # regions); MEDMOE_LOCAL_PAIR3=0 keeps the [region][word] kernels (local_pair2) for A/B runs
@@ -333,7 +386,9 @@ class Engine:
         Mt = B * T
         buf("tx0", (Mt, Dt)); buf("tx1", (Mt, Dt)); buf("tx2", (Mt, Dt)); buf("tr", (Mt, Dt)); buf("tqkv", (Mt, 3 * Dt)); buf("tatt", (Mt, Dt))
         buf("th", (Mt, c.ff_t)); buf("tlse", (B * c.n_head_t * T,), F32); buf("tstat", (2, Mt), F32)
-        ws["tpack"] = torch.zeros(2 * Mt + B + 2, device=dev, dtype=I32)           # text_pack: tok_row | src_of_row | seq_off | count
+        # text_pack: tok_row | src_of_row | seq_off | count, then (a trainable tower's packed pass) 0 | count - its count sits behind a zero that is
+        # never written, so the pair is the row_off = [0, count] of the one-group weight-gradient GEMMs
+        ws["tpack"] = torch.zeros(2 * Mt + B + 4, device=dev, dtype=I32)
         for j in range(min(c.last_n_layers, c.n_layer_t + 1)):
             buf(f"ths{j}", (Mt, Dt))
         buf("words", (B, T, Dt)); buf("words32", (B, T, Dt), F32); buf("txt_g", (B, Dt), F32)
@@ -570,7 +625,8 @@ class Engine:
 
     def _forward_text_train(self, ids, attn_mask, token_type, training: bool = False):
         """The text pass of a TRAINABLE tower (cfg.freeze_text = False): all B x T positions (key-masked attention, as the reference computes
-        them, text_encoder.py:92-117), every layer's activations kept in the workspace for `backward_text`.
+        them, text_encoder.py:92-117), every layer's activations kept in the workspace for `backward_text`.  With text_train_varlen the same
+        launches run on the packed non-padding tokens (_TextRows; the first `count` rows of the same buffers).
         `training` with a dropout probability > 0: BertModel's four train-mode dropouts - after the embedding LayerNorm, on the attention
         probabilities (medmoe_attn_drop_fwd), after the output projection and after FC2 (each fused with the residual add and the LayerNorm
         that follow: medmoe_dropout_add_layernorm_fwd on the GEMM's output without residual).  No mask is stored: `backward_text`
@@ -590,70 +646,76 @@ class Engine:
         self._lora_drop_step = self.dropout_step if (training and lo is not None and c.text_lora_dropout > 0.0) else None
         ph, pa = (c.text_hidden_dropout, c.text_attn_dropout) if drop else (0.0, 0.0)
         x = ws["t_x0"]
-        ops.call("text_embed_ln", ids32, tt32, t["word_embeddings"], t["position_embeddings"], t["token_type_embeddings"],
-                 t["emb_layernorm.weight"], t["emb_layernorm.bias"], x, B, T, Dt, c.vocab, c.eps_t)
+        tp = self._tp = _TextRows(self, km, self.text_train_varlen and B <= 1024 and T <= 80)
+        self.text_train_varlen_active = tp.packed
+        if tp.packed:
+            ops.call("text_embed_ln_packed", ids32, tt32, t["word_embeddings"], t["position_embeddings"], t["token_type_embeddings"],
+                     t["emb_layernorm.weight"], t["emb_layernorm.bias"], x, B, T, Dt, c.vocab, c.eps_t, tp.src_row, tp.cnt)
+        else:
+            ops.call("text_embed_ln", ids32, tt32, t["word_embeddings"], t["position_embeddings"], t["token_type_embeddings"],
+                     t["emb_layernorm.weight"], t["emb_layernorm.bias"], x, B, T, Dt, c.vocab, c.eps_t)
         if ph > 0.0:
             ops.dropout_apply(x, x, self._drop_rng(ops.DROPOUT_SITE_EMBED, ph))
         for l in range(L):
             b = f"layer.{l}."
             st1, st2 = ws[f"t_st1{l}"], ws[f"t_st2{l}"]
-            ops.gemm_nt(x, t[b + "attention.input_proj.weight"], ws[f"t_qkv{l}"], bias=t[b + "attention.input_proj.bias"])
+            tp.gemm(x, t[b + "attention.input_proj.weight"], ws[f"t_qkv{l}"], bias=t[b + "attention.input_proj.bias"])
             if lo is not None:     # qkv[:, target columns] += s (dropout(x) A^T) B^T, U kept for the backward: one launch
-                ops.lora_fwd(x, lo.A16(l), lo.B16(l), ws[f"t_lu{l}"], ws[f"t_qkv{l}"], lo.targets, lo.scale, self._lora_rng(l))
+                ops.lora_fwd(x, lo.A16(l), lo.B16(l), ws[f"t_lu{l}"], ws[f"t_qkv{l}"], lo.targets, lo.scale, self._lora_rng(l), rows_dev=tp.cnt)
             if drop:
                 if pa > 0.0:
                     ops.attn_drop_fwd(ws[f"t_qkv{l}"], ws[f"t_att{l}"], ws[f"t_lse{l}"], km, B, T, H, self._drop_rng(4 * l, pa))
                 else:
-                    ops.attn_fwd(ws[f"t_qkv{l}"], ws[f"t_att{l}"], ws[f"t_lse{l}"], km, B, T, H)
+                    tp.attn(ws[f"t_qkv{l}"], ws[f"t_att{l}"], ws[f"t_lse{l}"])
                 if ph > 0.0:
-                    ops.gemm_nt(ws[f"t_att{l}"], t[b + "attention.output_proj.weight"], ws["t_z"], bias=t[b + "attention.output_proj.bias"])
+                    tp.gemm(ws[f"t_att{l}"], t[b + "attention.output_proj.weight"], ws["t_z"], bias=t[b + "attention.output_proj.bias"])
                     ops.dropout_add_layernorm_fwd(ws["t_z"], x, t[b + "attention_layernorm.weight"], t[b + "attention_layernorm.bias"],
                                                   ws[f"t_x1{l}"], ws[f"t_r{l}"], st1[0], st1[1], c.eps_t, self._drop_rng(4 * l + 1, ph))
                 else:
-                    ops.gemm_nt(ws[f"t_att{l}"], t[b + "attention.output_proj.weight"], ws[f"t_x1{l}"], bias=t[b + "attention.output_proj.bias"],
+                    tp.gemm(ws[f"t_att{l}"], t[b + "attention.output_proj.weight"], ws[f"t_x1{l}"], bias=t[b + "attention.output_proj.bias"],
                                 residual=x)
-                    ops.layernorm_fwd(ws[f"t_x1{l}"], t[b + "attention_layernorm.weight"], t[b + "attention_layernorm.bias"], ws[f"t_r{l}"],
-                                      st1[0], st1[1], c.eps_t)
-                ops.gemm_nt(ws[f"t_r{l}"], t[b + "feedforward.model.0.weight"], ws[f"t_h{l}"], bias=t[b + "feedforward.model.0.bias"],
+                    tp.ln(ws[f"t_x1{l}"], t[b + "attention_layernorm.weight"], t[b + "attention_layernorm.bias"], ws[f"t_r{l}"], st1)
+                tp.gemm(ws[f"t_r{l}"], t[b + "feedforward.model.0.weight"], ws[f"t_h{l}"], bias=t[b + "feedforward.model.0.bias"],
                             aux=ws[f"t_dg{l}"], epi=ops.EPI_GELU_DAUX)
                 if ph > 0.0:
-                    ops.gemm_nt(ws[f"t_h{l}"], t[b + "feedforward.model.2.weight"], ws["t_z"], bias=t[b + "feedforward.model.2.bias"])
+                    tp.gemm(ws[f"t_h{l}"], t[b + "feedforward.model.2.weight"], ws["t_z"], bias=t[b + "feedforward.model.2.bias"])
                     ops.dropout_add_layernorm_fwd(ws["t_z"], ws[f"t_r{l}"], t[b + "feedforward_layernorm.weight"], t[b + "feedforward_layernorm.bias"],
                                                   ws[f"t_x2{l}"], ws[f"t_x{l + 1}"], st2[0], st2[1], c.eps_t, self._drop_rng(4 * l + 2, ph))
                 else:
-                    ops.gemm_nt(ws[f"t_h{l}"], t[b + "feedforward.model.2.weight"], ws[f"t_x2{l}"], bias=t[b + "feedforward.model.2.bias"],
+                    tp.gemm(ws[f"t_h{l}"], t[b + "feedforward.model.2.weight"], ws[f"t_x2{l}"], bias=t[b + "feedforward.model.2.bias"],
                                 residual=ws[f"t_r{l}"])
-                    ops.layernorm_fwd(ws[f"t_x2{l}"], t[b + "feedforward_layernorm.weight"], t[b + "feedforward_layernorm.bias"], ws[f"t_x{l + 1}"],
-                                      st2[0], st2[1], c.eps_t)
+                    tp.ln(ws[f"t_x2{l}"], t[b + "feedforward_layernorm.weight"], t[b + "feedforward_layernorm.bias"], ws[f"t_x{l + 1}"], st2)
                 x = ws[f"t_x{l + 1}"]
                 continue
-            ops.attn_fwd(ws[f"t_qkv{l}"], ws[f"t_att{l}"], ws[f"t_lse{l}"], km, B, T, H)
-            ops.gemm_nt(ws[f"t_att{l}"], t[b + "attention.output_proj.weight"], ws[f"t_x1{l}"], bias=t[b + "attention.output_proj.bias"], residual=x)
-            ops.layernorm_fwd(ws[f"t_x1{l}"], t[b + "attention_layernorm.weight"], t[b + "attention_layernorm.bias"], ws[f"t_r{l}"], st1[0], st1[1], c.eps_t)
-            ops.gemm_nt(ws[f"t_r{l}"], t[b + "feedforward.model.0.weight"], ws[f"t_h{l}"], bias=t[b + "feedforward.model.0.bias"],
+            tp.attn(ws[f"t_qkv{l}"], ws[f"t_att{l}"], ws[f"t_lse{l}"])
+            tp.gemm(ws[f"t_att{l}"], t[b + "attention.output_proj.weight"], ws[f"t_x1{l}"], bias=t[b + "attention.output_proj.bias"], residual=x)
+            tp.ln(ws[f"t_x1{l}"], t[b + "attention_layernorm.weight"], t[b + "attention_layernorm.bias"], ws[f"t_r{l}"], st1)
+            tp.gemm(ws[f"t_r{l}"], t[b + "feedforward.model.0.weight"], ws[f"t_h{l}"], bias=t[b + "feedforward.model.0.bias"],
                         aux=ws[f"t_dg{l}"], epi=ops.EPI_GELU_DAUX)
-            ops.gemm_nt(ws[f"t_h{l}"], t[b + "feedforward.model.2.weight"], ws[f"t_x2{l}"], bias=t[b + "feedforward.model.2.bias"], residual=ws[f"t_r{l}"])
-            ops.layernorm_fwd(ws[f"t_x2{l}"], t[b + "feedforward_layernorm.weight"], t[b + "feedforward_layernorm.bias"], ws[f"t_x{l + 1}"],
-                              st2[0], st2[1], c.eps_t)
+            tp.gemm(ws[f"t_h{l}"], t[b + "feedforward.model.2.weight"], ws[f"t_x2{l}"], bias=t[b + "feedforward.model.2.bias"], residual=ws[f"t_r{l}"])
+            tp.ln(ws[f"t_x2{l}"], t[b + "feedforward_layernorm.weight"], t[b + "feedforward_layernorm.bias"], ws[f"t_x{l + 1}"], st2)
             x = ws[f"t_x{l + 1}"]
         first_sel = max(0, L + 1 - last)                          # hidden_states[-last:] of [embedding output, layer 1 .. layer L]
         hs = [ws[f"t_x{j}"] for j in range(first_sel, L + 1)]
         self._text_first_sel = first_sel
-        self._text_last = (hs[-1], None)
+        self._text_last = (hs[-1], tp.seq_off)
         if self._seg is None:
             self.prefetch_cap_lens(ids)
         seg = self._seg
         self._seg = None
         self._seg_used = seg
         h = hs + [None] * (4 - len(hs))
-        ops.call("text_aggregate", h[0], h[1], h[2], h[3], len(hs), seg, ws["words"], ws["words32"], ws["txt_g"], B, T, Dt)
+        if tp.packed:
+            ops.call("text_aggregate_packed", h[0], h[1], h[2], h[3], len(hs), seg, tp.tok_row, ws["words"], ws["words32"], ws["txt_g"], B, T, Dt)
+        else:
+            ops.call("text_aggregate", h[0], h[1], h[2], h[3], len(hs), seg, ws["words"], ws["words32"], ws["txt_g"], B, T, Dt)
 
     def backward_text(self, d_words: Optional[torch.Tensor], d_txt_g: Optional[torch.Tensor]):
         """Back-propagate d loss / d word embeddings (fp32 [B, T, D]) and d loss / d sentence embeddings (fp32 [B, D]) through the aggregation,
         the post-norm blocks (transformer.py:116-130) and the embedding front-end into the text store's flat gradient buffer."""
         if self.lora is not None:
             return self._backward_text_lora(d_words, d_txt_g)
-        c, ws, ts = self.cfg, self.ws, self.tstore
+        c, ws, ts, tp = self.cfg, self.ws, self.tstore, self._tp
         B, T, Dt, H, L = self.B, c.max_len, c.d_t, c.n_head_t, c.n_layer_t
         ids32, tt32, km = self._tt_state
         w16t, grad, f32 = ts.w16t, ts.grad, ts.f32
@@ -662,41 +724,50 @@ class Engine:
         # residual branch takes d x1 unchanged
         drop = self._text_drop_step is not None
         ph, pa = (c.text_hidden_dropout, c.text_attn_dropout) if drop else (0.0, 0.0)
-        ops.call("text_aggregate_bwd", d_words, d_txt_g, self._seg_used, dH, B, T, Dt)
+        if tp.packed:
+            ops.call("text_aggregate_bwd_packed", d_words, d_txt_g, self._seg_used, tp.src_row, tp.cnt, dH, B, T, Dt)
+        else:
+            ops.call("text_aggregate_bwd", d_words, d_txt_g, self._seg_used, dH, B, T, Dt)
         dy, d1, d2 = ws["t_da"], ws["t_db"], ws["t_dc"]
         dy.copy_(dH)                                                 # the last layer's output is always among the summed states
         for l in range(L - 1, -1, -1):
             b = f"layer.{l}."
             st1, st2 = ws[f"t_st1{l}"], ws[f"t_st2{l}"]
             # y = LN2(x2), x2 = r + FC2(GELU(FC1(r)))
-            ops.layernorm_bwd(dy, ws[f"t_x2{l}"], st2[0], st2[1], f32(b + "feedforward_layernorm.weight"), d1,
+            tp.ln_bwd(dy, ws[f"t_x2{l}"], st2[0], st2[1], f32(b + "feedforward_layernorm.weight"), d1,
                               grad(b + "feedforward_layernorm.weight"), grad(b + "feedforward_layernorm.bias"))
             dz = ops.dropout_apply(d1, ws["t_dzd"], self._drop_rng(4 * l + 2, ph)) if ph > 0.0 else d1
-            ops.gemm_tn(dz, ws[f"t_h{l}"], grad(b + "feedforward.model.2.weight"), db=grad(b + "feedforward.model.2.bias"))
-            ops.gemm_nt(dz, w16t(b + "feedforward.model.2.weight"), ws["t_dz"], aux=ws[f"t_dg{l}"], epi=ops.EPI_MUL_AUX)
-            ops.gemm_tn(ws["t_dz"], ws[f"t_r{l}"], grad(b + "feedforward.model.0.weight"), db=grad(b + "feedforward.model.0.bias"))
-            ops.gemm_nt(ws["t_dz"], w16t(b + "feedforward.model.0.weight"), d2, residual=d1)                  # d r = d x2 + dz W1
+            tp.wgrad(dz, ws[f"t_h{l}"], grad(b + "feedforward.model.2.weight"), db=grad(b + "feedforward.model.2.bias"))
+            tp.gemm(dz, w16t(b + "feedforward.model.2.weight"), ws["t_dz"], aux=ws[f"t_dg{l}"], epi=ops.EPI_MUL_AUX)
+            tp.wgrad(ws["t_dz"], ws[f"t_r{l}"], grad(b + "feedforward.model.0.weight"), db=grad(b + "feedforward.model.0.bias"))
+            tp.gemm(ws["t_dz"], w16t(b + "feedforward.model.0.weight"), d2, residual=d1)                  # d r = d x2 + dz W1
             # r = LN1(x1), x1 = x + out_proj(attention(qkv(x)))
-            ops.layernorm_bwd(d2, ws[f"t_x1{l}"], st1[0], st1[1], f32(b + "attention_layernorm.weight"), d1,
+            tp.ln_bwd(d2, ws[f"t_x1{l}"], st1[0], st1[1], f32(b + "attention_layernorm.weight"), d1,
                               grad(b + "attention_layernorm.weight"), grad(b + "attention_layernorm.bias"))
             dz = ops.dropout_apply(d1, ws["t_dzd"], self._drop_rng(4 * l + 1, ph)) if ph > 0.0 else d1
-            ops.gemm_tn(dz, ws[f"t_att{l}"], grad(b + "attention.output_proj.weight"), db=grad(b + "attention.output_proj.bias"))
-            ops.gemm_nt(dz, w16t(b + "attention.output_proj.weight"), ws["t_datt"])
+            tp.wgrad(dz, ws[f"t_att{l}"], grad(b + "attention.output_proj.weight"), db=grad(b + "attention.output_proj.bias"))
+            tp.gemm(dz, w16t(b + "attention.output_proj.weight"), ws["t_datt"])
             if pa > 0.0:
                 ops.attn_drop_bwd(ws[f"t_qkv{l}"], ws[f"t_att{l}"], ws["t_datt"], ws[f"t_lse{l}"], km, ws["t_dqkv"], ws["t_delta"], B, T, H,
                                   self._drop_rng(4 * l, pa))
             else:
-                ops.attn_bwd(ws[f"t_qkv{l}"], ws[f"t_att{l}"], ws["t_datt"], ws[f"t_lse{l}"], km, ws["t_dqkv"], ws["t_delta"], B, T, H)
-            ops.gemm_tn(ws["t_dqkv"], ws[f"t_x{l}"], grad(b + "attention.input_proj.weight"), db=grad(b + "attention.input_proj.bias"))
-            ops.gemm_nt(ws["t_dqkv"], w16t(b + "attention.input_proj.weight"), dy, residual=d1)               # d x = d x1 + dqkv Wqkv
+                tp.attn_bwd(ws[f"t_qkv{l}"], ws[f"t_att{l}"], ws["t_datt"], ws[f"t_lse{l}"], ws["t_dqkv"], ws["t_delta"])
+            tp.wgrad(ws["t_dqkv"], ws[f"t_x{l}"], grad(b + "attention.input_proj.weight"), db=grad(b + "attention.input_proj.bias"))
+            tp.gemm(ws["t_dqkv"], w16t(b + "attention.input_proj.weight"), dy, residual=d1)               # d x = d x1 + dqkv Wqkv
             if l >= self._text_first_sel:                          # hidden_states[l] is one of the summed states too
                 dy.add_(dH)
         if ph > 0.0:                                              # hidden_states[0] is the embedding output AFTER its dropout
             ops.dropout_apply(dy, dy, self._drop_rng(ops.DROPOUT_SITE_EMBED, ph))
         g_word = grad("word_embeddings")
-        ops.call("text_embed_ln_bwd", ids32, tt32, f32("word_embeddings"), f32("position_embeddings"), f32("token_type_embeddings"),
-                 f32("emb_layernorm.weight"), dy, ws["t_dxemb"], grad("emb_layernorm.weight"), grad("emb_layernorm.bias"), g_word, B, T, Dt,
-                 c.vocab, c.eps_t)
+        if tp.packed:              # d x lands at the tokens' PADDED rows of the zeroed buffer: the position / token-type sums below stay as they are
+            ws["t_dxemb"].zero_()
+            ops.call("text_embed_ln_bwd_packed", ids32, tt32, f32("word_embeddings"), f32("position_embeddings"), f32("token_type_embeddings"),
+                     f32("emb_layernorm.weight"), dy, ws["t_dxemb"], grad("emb_layernorm.weight"), grad("emb_layernorm.bias"), g_word, B, T, Dt,
+                     c.vocab, c.eps_t, tp.src_row, tp.cnt)
+        else:
+            ops.call("text_embed_ln_bwd", ids32, tt32, f32("word_embeddings"), f32("position_embeddings"), f32("token_type_embeddings"),
+                     f32("emb_layernorm.weight"), dy, ws["t_dxemb"], grad("emb_layernorm.weight"), grad("emb_layernorm.bias"), g_word, B, T, Dt,
+                     c.vocab, c.eps_t)
         dxe = ws["t_dxemb"].view(B, T, Dt)
         grad("position_embeddings").add_(dxe.sum(dim=0))
         tt = tt32.view(-1).long() if tt32 is not None else torch.zeros(B * T, device=self.device, dtype=torch.long)
@@ -708,36 +779,39 @@ class Engine:
         backward.  Per layer, after the attention backward has written d qkv: medmoe_lora_bwd_dx (d U, and the adapters' term of d x added into
         the base dgrad GEMM's output) and medmoe_lora_bwd_wgrad (the adapters' gradients, += into the arena).  At layer 0 nothing below
         trains: the dgrad GEMM and the d x term are both skipped."""
-        c, ws, lo, t = self.cfg, self.ws, self.lora, self.params.text
+        c, ws, lo, t, tp = self.cfg, self.ws, self.lora, self.params.text, self._tp
         B, T, Dt, H, L = self.B, c.max_len, c.d_t, c.n_head_t, c.n_layer_t
         _, _, km = self._tt_state
         wt = self._base_wt
         dH = ws["t_dH"]
         drop = self._text_drop_step is not None
         ph, pa = (c.text_hidden_dropout, c.text_attn_dropout) if drop else (0.0, 0.0)
-        ops.call("text_aggregate_bwd", d_words, d_txt_g, self._seg_used, dH, B, T, Dt)
+        if tp.packed:
+            ops.call("text_aggregate_bwd_packed", d_words, d_txt_g, self._seg_used, tp.src_row, tp.cnt, dH, B, T, Dt)
+        else:
+            ops.call("text_aggregate_bwd", d_words, d_txt_g, self._seg_used, dH, B, T, Dt)
         dy, d1, d2 = ws["t_da"], ws["t_db"], ws["t_dc"]
         dy.copy_(dH)
         for l in range(L - 1, -1, -1):
             b = f"layer.{l}."
             st1, st2 = ws[f"t_st1{l}"], ws[f"t_st2{l}"]
-            ops.layernorm_bwd(dy, ws[f"t_x2{l}"], st2[0], st2[1], t[b + "feedforward_layernorm.weight"], d1)
+            tp.ln_bwd(dy, ws[f"t_x2{l}"], st2[0], st2[1], t[b + "feedforward_layernorm.weight"], d1)
             dz = ops.dropout_apply(d1, ws["t_dzd"], self._drop_rng(4 * l + 2, ph)) if ph > 0.0 else d1
-            ops.gemm_nt(dz, wt(b + "feedforward.model.2.weight"), ws["t_dz"], aux=ws[f"t_dg{l}"], epi=ops.EPI_MUL_AUX)
-            ops.gemm_nt(ws["t_dz"], wt(b + "feedforward.model.0.weight"), d2, residual=d1)
-            ops.layernorm_bwd(d2, ws[f"t_x1{l}"], st1[0], st1[1], t[b + "attention_layernorm.weight"], d1)
+            tp.gemm(dz, wt(b + "feedforward.model.2.weight"), ws["t_dz"], aux=ws[f"t_dg{l}"], epi=ops.EPI_MUL_AUX)
+            tp.gemm(ws["t_dz"], wt(b + "feedforward.model.0.weight"), d2, residual=d1)
+            tp.ln_bwd(d2, ws[f"t_x1{l}"], st1[0], st1[1], t[b + "attention_layernorm.weight"], d1)
             dz = ops.dropout_apply(d1, ws["t_dzd"], self._drop_rng(4 * l + 1, ph)) if ph > 0.0 else d1
-            ops.gemm_nt(dz, wt(b + "attention.output_proj.weight"), ws["t_datt"])
+            tp.gemm(dz, wt(b + "attention.output_proj.weight"), ws["t_datt"])
             if pa > 0.0:
                 ops.attn_drop_bwd(ws[f"t_qkv{l}"], ws[f"t_att{l}"], ws["t_datt"], ws[f"t_lse{l}"], km, ws["t_dqkv"], ws["t_delta"], B, T, H,
                                   self._drop_rng(4 * l, pa))
             else:
-                ops.attn_bwd(ws[f"t_qkv{l}"], ws[f"t_att{l}"], ws["t_datt"], ws[f"t_lse{l}"], km, ws["t_dqkv"], ws["t_delta"], B, T, H)
+                tp.attn_bwd(ws[f"t_qkv{l}"], ws[f"t_att{l}"], ws["t_datt"], ws[f"t_lse{l}"], ws["t_dqkv"], ws["t_delta"])
             rng = self._lora_rng(l)
             if l > 0:
-                ops.gemm_nt(ws["t_dqkv"], wt(b + "attention.input_proj.weight"), dy, residual=d1)           # d x = d x1 + dqkv Wqkv (base)
-            ops.lora_bwd_dx(ws["t_dqkv"], lo.B16t(l), lo.A16t(l), ws["t_ldu"], dy if l > 0 else None, lo.targets, lo.scale, rng)
-            ops.lora_bwd_wgrad(ws["t_dqkv"], ws[f"t_x{l}"], ws[f"t_lu{l}"], ws["t_ldu"], lo.gA(l), lo.gB(l), ws["t_lsc"], lo.targets, lo.scale, rng)
+                tp.gemm(ws["t_dqkv"], wt(b + "attention.input_proj.weight"), dy, residual=d1)           # d x = d x1 + dqkv Wqkv (base)
+            ops.lora_bwd_dx(ws["t_dqkv"], lo.B16t(l), lo.A16t(l), ws["t_ldu"], dy if l > 0 else None, lo.targets, lo.scale, rng, rows_dev=tp.cnt)
+            ops.lora_bwd_wgrad(ws["t_dqkv"], ws[f"t_x{l}"], ws[f"t_lu{l}"], ws["t_ldu"], lo.gA(l), lo.gB(l), ws["t_lsc"], lo.targets, lo.scale, rng, rows_dev=tp.cnt)
             if l > 0 and l >= self._text_first_sel:
                 dy.add_(dH)
 

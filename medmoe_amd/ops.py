@@ -327,14 +327,21 @@ def layernorm_fwd(x, gamma, beta, y, mean, rstd, eps):
     return y
 
 
-def layernorm_bwd(dy, x, mean, rstd, gamma, dx, dgamma=None, dbeta=None, add=None, det: Optional[DetScratch] = None):
-    """det (deterministic mode): dgamma / dbeta leave as per-workgroup partial rows summed in workgroup order (medmoe_layernorm_bwd_det)."""
+def layernorm_bwd(dy, x, mean, rstd, gamma, dx, dgamma=None, dbeta=None, add=None, det: Optional[DetScratch] = None, rows_dev=None):
+    """det (deterministic mode): dgamma / dbeta leave as per-workgroup partial rows summed in workgroup order (medmoe_layernorm_bwd_det).
+    rows_dev (int32 device tensor of one element): medmoe_layernorm_bwd_rows - the first min(rows, *rows_dev) rows only."""
     lib = load_library()
     for t, nm in ((dy, "dy"), (x, "x"), (dx, "dx")):
         _need(t, torch.bfloat16, nm)
         if not t.is_contiguous():
             raise ValueError(f"layernorm_bwd: {nm} must be contiguous")
     rows, D = x.numel() // x.shape[-1], x.shape[-1]
+    if rows_dev is not None:
+        if det is not None:
+            raise ValueError("layernorm_bwd: no deterministic form with a device row count")
+        _need(rows_dev, torch.int32, "rows_dev")
+        call("layernorm_bwd_rows", dy, x, mean, rstd, gamma, add, dx, dgamma, dbeta, rows, D, rows_dev)
+        return dx
     if det is not None and dgamma is not None:
         sc = det.get(_scratch_query("layernorm_bwd_det_scratch", D))
         with _Timed("layernorm_bwd_kernel + layernorm_bwd_reduce_kernel", (8.0 if add is not None else 6.0) * rows * D, "byte"):
@@ -378,6 +385,20 @@ def attn_bwd(qkv, out, dout, lse, key_mask, dqkv, delta, B, N, H):
         rc = lib.medmoe_attn_bwd(_ptr(qkv), _ptr(out), _ptr(dout), _ptr(lse), _ptr(key_mask), _ptr(dqkv), _ptr(delta),
                                  _c.c_int(B), _c.c_int(N), _c.c_int(H), _c.c_int(64), _stream())
         _chk(rc, "attn_bwd")
+    return dqkv
+
+
+def attn_bwd_varlen(qkv, out, dout, lse, seq_off, dqkv, delta, B, Nmax, H):
+    """attn_bwd over a packed variable-length batch (attn_fwd_varlen's layout): qkv / dqkv [rows, 3D], out / dout [rows, D] hold the sequences
+    back to back from row seq_off[b] on (rows >= seq_off[B]), lse / delta [B, H, Nmax]; Nmax <= 80."""
+    for t, nm in ((qkv, "qkv"), (out, "out"), (dout, "dout"), (dqkv, "dqkv")):
+        _need(t, torch.bfloat16, nm)
+    _need(lse, torch.float32, "lse"); _need(delta, torch.float32, "delta"); _need(seq_off, torch.int32, "seq_off")
+    D = H * 64
+    if qkv.shape[-1] != 3 * D or dqkv.numel() != qkv.numel() or out.shape[-1] != D or dout.numel() != out.numel() \
+            or out.numel() // D != qkv.numel() // (3 * D) or delta.numel() != B * H * Nmax or lse.numel() != B * H * Nmax or seq_off.numel() != B + 1:
+        raise ValueError("attn_bwd_varlen: buffer sizes do not match (rows, B, Nmax, H)")
+    call("attn_bwd_varlen", qkv, out, dout, lse, seq_off, dqkv, delta, B, Nmax, H, 64)
     return dqkv
 
 
@@ -494,23 +515,39 @@ def _lora_check(name, M, D, n, u_like, **bf16):
         raise ValueError(f"{name}: U / dU must be [M, n * {LORA_RANK_PAD}]")
 
 
-def lora_fwd(x, A, Bw, U, qkv, targets, s, rng=None):
-    """U = dropout(x) A^T (stored bf16 [M, n*16]); qkv[:, c_t : c_t + D] += s U_t B_t^T in place.  A [n*16, D], Bw [n*D, 16] bf16."""
+def _rows_dev(rows_dev):
+    if rows_dev is not None:
+        _need(rows_dev, torch.int32, "rows_dev")
+    return rows_dev
+
+
+def lora_fwd(x, A, Bw, U, qkv, targets, s, rng=None, rows_dev=None):
+    """U = dropout(x) A^T (stored bf16 [M, n*16]); qkv[:, c_t : c_t + D] += s U_t B_t^T in place.  A [n*16, D], Bw [n*D, 16] bf16.
+    rows_dev (here and in the two backward launches; int32 device tensor of one element): the *_rows entry point - the first
+    min(M, *rows_dev) rows only."""
     M, D, n = x.shape[0], x.shape[1], len(targets)
     _lora_check("lora_fwd", M, D, n, U, x=x, A=A, Bw=Bw, U=U, qkv=qkv)
     if A.numel() != n * LORA_RANK_PAD * D or Bw.numel() != A.numel() or qkv.shape[0] != M or qkv.shape[-1] != 3 * D:
         raise ValueError("lora_fwd: A [n*16, D], Bw [n*D, 16], qkv [M, 3D]")
-    call("lora_fwd", x, A, Bw, U, qkv, qkv.stride(-2), M, D, n, *lora_cols(targets, D), s, *(rng or _NO_DROP))
+    a = (x, A, Bw, U, qkv, qkv.stride(-2), M, D, n, *lora_cols(targets, D), s, *(rng or _NO_DROP))
+    if _rows_dev(rows_dev) is None:
+        call("lora_fwd", *a)
+    else:
+        call("lora_fwd_rows", *a, rows_dev)
     return qkv
 
 
-def lora_bwd_dx(dqkv, Bt, At, dU, dy, targets, s, rng=None):
+def lora_bwd_dx(dqkv, Bt, At, dU, dy, targets, s, rng=None, rows_dev=None):
     """dU_t = s dqkv_t B_t (stored bf16 [M, n*16]); dy [M, D] += dropout mask * (dU A) (dy None: skipped).  Bt [16, n*D], At [D, n*16] bf16."""
     M, D, n = dqkv.shape[0], dqkv.shape[-1] // 3, len(targets)
     _lora_check("lora_bwd_dx", M, D, n, dU, dqkv=dqkv, Bt=Bt, At=At, dU=dU, dy=dy)
     if Bt.numel() != n * LORA_RANK_PAD * D or At.numel() != Bt.numel() or dqkv.shape[-1] != 3 * D or (dy is not None and dy.numel() != M * D):
         raise ValueError("lora_bwd_dx: Bt [16, n*D], At [D, n*16], dqkv [M, 3D], dy [M, D]")
-    call("lora_bwd_dx", dqkv, dqkv.stride(-2), Bt, At, dU, dy, M, D, n, *lora_cols(targets, D), s, *(rng or _NO_DROP))
+    a = (dqkv, dqkv.stride(-2), Bt, At, dU, dy, M, D, n, *lora_cols(targets, D), s, *(rng or _NO_DROP))
+    if _rows_dev(rows_dev) is None:
+        call("lora_bwd_dx", *a)
+    else:
+        call("lora_bwd_dx_rows", *a, rows_dev)
     return dU
 
 
@@ -518,7 +555,7 @@ def lora_wgrad_scratch(M: int, D: int, n: int) -> int:
     return _scratch_query("lora_wgrad_scratch", M, D, n)
 
 
-def lora_bwd_wgrad(dqkv, x, U, dU, gA, gB, scratch, targets, s, rng=None):
+def lora_bwd_wgrad(dqkv, x, U, dU, gA, gB, scratch, targets, s, rng=None, rows_dev=None):
     """gB [n*D, 16] += s dqkv_t^T U_t, gA [n*16, D] += dU_t^T dropout(x) (fp32): per-chunk partial sums in `scratch`, summed in a fixed order."""
     M, D, n = x.shape[0], x.shape[1], len(targets)
     _lora_check("lora_bwd_wgrad", M, D, n, U, dqkv=dqkv, x=x, U=U, dU=dU)
@@ -527,7 +564,11 @@ def lora_bwd_wgrad(dqkv, x, U, dU, gA, gB, scratch, targets, s, rng=None):
     if gA.numel() != n * LORA_RANK_PAD * D or gB.numel() != gA.numel() or dU.numel() != U.numel() or dqkv.shape[0] != M or dqkv.shape[-1] != 3 * D \
             or not gA.is_contiguous() or not gB.is_contiguous() or scratch.numel() < lora_wgrad_scratch(M, D, n):
         raise ValueError("lora_bwd_wgrad: gA [n*16, D], gB [n*D, 16] contiguous, dqkv [M, 3D], scratch of lora_wgrad_scratch(M, D, n) floats")
-    call("lora_bwd_wgrad", dqkv, dqkv.stride(-2), x, U, dU, gA, gB, scratch, scratch.numel(), M, D, n, *lora_cols(targets, D), s, *(rng or _NO_DROP))
+    a = (dqkv, dqkv.stride(-2), x, U, dU, gA, gB, scratch, scratch.numel(), M, D, n, *lora_cols(targets, D), s, *(rng or _NO_DROP))
+    if _rows_dev(rows_dev) is None:
+        call("lora_bwd_wgrad", *a)
+    else:
+        call("lora_bwd_wgrad_rows", *a, rows_dev)
 
 
 def lora_merge(W, A, Bw, targets, s):
@@ -573,6 +614,9 @@ _SIGS = {
     "cos_scale_bwd_det": "ppppppiif",
     "sumsq": "plp", "sumsq_det": "plpp", "adam_step": "pppppldddddipff", "adam_groups_step": "ppppplpppidddddiipff", "cast_bf16": "ppl", "transpose_many": "pppii",
     "lora_fwd": "pppppiiiiiiifllllf", "lora_bwd_dx": "pippppiiiiiifllllf", "lora_bwd_wgrad": "pippppppliiiiiifllllf", "lora_merge": "pippiiiiif",
+    "attn_bwd_varlen": "pppppppiiii", "layernorm_bwd_rows": "pppppppppiip", "text_aggregate_bwd_packed": "ppppppiii",
+    "text_embed_ln_bwd_packed": "pppppppppppiiiifpp",
+    "lora_fwd_rows": "pppppiiiiiiifllllfp", "lora_bwd_dx_rows": "pippppiiiiiifllllfp", "lora_bwd_wgrad_rows": "pippppppliiiiiifllllfp",
     "grad_pack_bf16": "pplf", "sumsq_det_bf16": "plpp", "adam_step_g16": "pppppldddddipff", "adam_groups_step_g16": "ppppplpppidddddiipff",
 }
 
@@ -662,6 +706,11 @@ _COSTS = {
     "lora_fwd": lambda a: ("lora_fwd_kernel", 2.0 * a[6] * (a[7] + 2 * a[8] * a[7] + a[8] * 16), "byte"),
     "lora_bwd_dx": lambda a: ("lora_bwd_dx_kernel", 2.0 * a[6] * (a[8] * a[7] + a[8] * 16 + (2 * a[7] if a[5] is not None else 0)), "byte"),
     "lora_bwd_wgrad": lambda a: ("lora_bwd_wgrad_kernel + lora_wgrad_reduce_kernel", 2.0 * a[9] * (a[11] * a[10] + a[10] + 2 * a[11] * 16), "byte"),
+    "lora_fwd_rows": lambda a: ("lora_fwd_kernel (rows)", 2.0 * (ROWS_HINT or a[6]) * (a[7] + 2 * a[8] * a[7] + a[8] * 16), "byte"),
+    "lora_bwd_dx_rows": lambda a: ("lora_bwd_dx_kernel (rows)", 2.0 * (ROWS_HINT or a[6]) * (a[8] * a[7] + a[8] * 16 + (2 * a[7] if a[5] is not None else 0)), "byte"),
+    "lora_bwd_wgrad_rows": lambda a: ("lora_bwd_wgrad_kernel + lora_wgrad_reduce_kernel (rows)", 2.0 * (ROWS_HINT or a[9]) * (a[11] * a[10] + a[10] + 2 * a[11] * 16), "byte"),
+    "layernorm_bwd_rows": lambda a: ("layernorm_bwd_kernel (rows)", (8.0 if a[5] is not None else 6.0) * (ROWS_HINT or a[9]) * a[10], "byte"),
+    "attn_bwd_varlen": lambda a: ("attn_bwd_varlen (attn_bwd_dq_kernel + attn_bwd_dkv_kernel)", None, None),
     "layernorm_fwd_rows": lambda a: ("layernorm_fwd_kernel", 4.0 * (ROWS_HINT or a[6]) * a[7], "byte"),
 }
 

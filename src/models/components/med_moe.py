@@ -82,7 +82,8 @@ def _text_dropout(c: MedMoEConfig, text: Any) -> MedMoEConfig:
 
 def _text_lora(c: MedMoEConfig, text: Any) -> MedMoEConfig:
     """model.model.text.lora / lora_r / lora_alpha / lora_dropout / lora_targets (the reference's names, med-moe.yaml:27-30, on the text tower:
-    peft-style adapters on the attention projections of a frozen BERT).  Absent keys leave the defaults: no adapters."""
+    peft-style adapters on the attention projections of a frozen BERT).  Absent keys leave the defaults: no adapters.
+    model.model.text.train_varlen: the trainable tower's (full or LoRA) pass on the packed non-padding tokens."""
     c.text_lora = bool(_get(text, "lora", False))
     c.text_lora_r = int(_get(text, "lora_r", c.text_lora_r))
     c.text_lora_alpha = float(_get(text, "lora_alpha", c.text_lora_alpha))
@@ -90,6 +91,7 @@ def _text_lora(c: MedMoEConfig, text: Any) -> MedMoEConfig:
     tg = _get(text, "lora_targets", None)
     if tg is not None:
         c.text_lora_targets = (tg,) if isinstance(tg, str) else tuple(str(t) for t in tg)
+    c.text_train_varlen = bool(_get(text, "train_varlen", False))
     return c
 
 
