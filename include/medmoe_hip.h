@@ -352,6 +352,14 @@ int medmoe_dropout_add_layernorm_fwd(const void* z, const void* residual, const 
 int medmoe_attn_drop_fwd(const void* qkv, void* out, float* lse, const unsigned char* key_mask, int B, int N, int H, int head_dim, long long seed, long long step, long long site, long long thresh, float scale, hipStream_t stream);
 int medmoe_attn_drop_bwd(const void* qkv, const void* out, const void* dout, const float* lse, const unsigned char* key_mask, void* dqkv, float* delta, int B, int N, int H, int head_dim, long long seed, long long step, long long site, long long thresh, float scale, hipStream_t stream);
 
+/* Stochastic depth of the image tower (csrc/dropout.hip; the engine's sites are 0x40000000 + 2 * layer + {0 attention, 1 feed-forward}).  out[n_sites][B] fp32 = 0 | (float)(1 / (1 - p[s])): sample b survives at
+   site s iff medmoe_dropout_mask(rows 1, site site0 + s, thresh floor(p[s] * 2^32)) keeps column sample0 + b.  p_host: n_sites <= 128
+   probabilities in [0, 1) in HOST memory - they travel to the kernel by value, nothing is read back from the device. */
+int medmoe_drop_path_scales(float* out, const double* p_host, int n_sites, int B, long long sample0, long long seed, long long step, long long site0, hipStream_t stream);
+/* x1 = bf16(residual + scale[row / rows_per_sample] * z) (fp32 product and sum; a row whose scale is 0 copies residual and never reads z),
+   y = LayerNorm(x1) with medmoe_layernorm_fwd's layout and statistics.  rows % rows_per_sample == 0, D % 8 == 0, D <= 2048.  No atomics. */
+int medmoe_scale_add_layernorm_fwd(const void* z, const void* residual, const float* scale, int rows_per_sample, const float* gamma, const float* beta, void* x1, void* y, float* mean, float* rstd, int rows, int D, float eps, hipStream_t stream);
+
 /* ---- deterministic mode (MedMoEConfig.deterministic): the same results as the entry points they are named after, up to summation order, with
    no sum whose order depends on which workgroup or wave arrives first.  Two forms: STAGED - partial results leave with plain stores into a
    scratch buffer of the caller's (one per stream: launches that may overlap must not share it) and a second kernel adds them in index order;

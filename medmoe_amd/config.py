@@ -41,6 +41,10 @@ class MedMoEConfig:
     text_lora_alpha: float = 16.0
     text_lora_dropout: float = 0.0
     text_lora_targets: Tuple[str, ...] = ("query", "value")
+    # stochastic depth of the image tower (reference TransformerEncoder(drop_path_rate=), transformer.py:45-68, 188-192): in train mode
+    # sample b skips the attention / the feed-forward branch of layer l with probability p_l = linspace(0, vit_drop_path, n_layer_v)[l], survivors
+    # are scaled by 1 / (1 - p_l); the two branches draw independently.  The keep bits are a function of (dropout_seed, step, site, global sample)
+    vit_drop_path: float = 0.0
     # variable-length pass of the TRAINABLE text tower (full or LoRA): forward and backward run on the packed non-padding tokens,
     # as the frozen tower's forward does (same rule: B <= 1024 and T <= 80, else the padded pass).  Opt-in; MEDMOE_TEXT_TRAIN_VARLEN=1 switches
     # it on too.  Hidden / LoRA dropout masks are then functions of the PACKED (row, column); attention dropout has no packed kernels
@@ -113,7 +117,14 @@ class MedMoEConfig:
         L = self.n_layer_v
         return [max(1, (L * (s + 1)) // 4) for s in range(4)]
 
+    def vit_drop_path_rates(self) -> List[float]:
+        """torch.linspace(0, vit_drop_path, n_layer_v) as the reference computes it (fp32 values): one probability per layer."""
+        import torch
+        return [float(v) for v in torch.linspace(0, float(self.vit_drop_path), self.n_layer_v)]
+
     def validate(self):
+        if not 0.0 <= float(self.vit_drop_path) < 1.0:
+            raise ValueError(f"vit_drop_path must be in [0, 1), got {self.vit_drop_path}")
         if self.grad_comm_dtype not in ("fp32", "bf16"):
             raise ValueError(f"grad_comm_dtype must be 'fp32' or 'bf16', got {self.grad_comm_dtype!r}")
         if self.optimizer not in ("adam", "adamw"):

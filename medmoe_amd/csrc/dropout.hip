@@ -6,6 +6,8 @@
 //   medmoe_dropout_apply               y = keep * x / (1 - p): the embedding site's forward, every hidden site's backward
 //   medmoe_dropout_add_layernorm_fwd   x1 = residual + keep * z / (1 - p), y = LayerNorm(x1): the two post-norm sites of a block in one
 //                                      launch (layout and statistics of layernorm_fwd, so medmoe_layernorm_bwd runs on x1 unchanged)
+//   medmoe_drop_path_scales            stochastic depth of the image tower: the per-sample scales 0 | 1 / (1 - p) of every site of a step
+//   medmoe_scale_add_layernorm_fwd     x1 = residual + scale[sample] * z, y = LayerNorm(x1): the per-sample sibling of the launch above
 //   medmoe_attn_drop_fwd / _bwd        text-geometry attention (N <= 80 keys, head_dim 64, key mask) with dropout on the probabilities;
 //                                      one workgroup per (batch, head), the backward is ONE kernel that reads qkv once
 #include "common.h"
@@ -145,6 +147,132 @@ extern "C" int medmoe_dropout_add_layernorm_fwd(const void* z, const void* resid
   const int grid = min((rows + 3) / 4, 256 * 8);
   hipLaunchKernelGGL(dropout_add_layernorm_fwd_kernel, dim3(grid), dim3(256), 0, stream, (const bf16_t*)z, (const bf16_t*)residual, gamma, beta,
                      (bf16_t*)x1, (bf16_t*)y, mean, rstd, rows, D, eps, make_drop_rng(seed, step, site, thresh, scale));
+  return mm_check_launch();
+}
+
+// ------------------------------------------------------------------------------------------
+// Stochastic depth of the image tower (reference transformer.py:45-68: StochasticDepth(p_l, mode="row") on both branches of a pre-norm
+// layer).  out[site][b] = 0 | 1 / (1 - p_site): sample b survives at site s iff word (sample0 + b) % 4 of group (sample0 + b) / 4 of
+// site site0 + s is >= thresh_s - the bit medmoe_dropout_mask writes at (row 0, column sample0 + b).  The per-site thresholds and scales
+// travel by value in the launch arguments (computed on the host from the probabilities, as ops.dropout_thresh computes them).
+// ------------------------------------------------------------------------------------------
+#define DP_MAX_SITES 128
+struct DropPathSites {
+  uint32_t thresh[DP_MAX_SITES];
+  float scale[DP_MAX_SITES];
+};
+
+__global__ __launch_bounds__(256) void drop_path_scales_kernel(float* __restrict__ out, DropPathSites sites, int n_sites, int B,
+                                                               unsigned long long sample0, DropRng rng, uint32_t site0) {
+  const long long n = (long long)n_sites * B;
+  for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < n; idx += (long long)gridDim.x * 256) {
+    const int s = (int)(idx / B);
+    const unsigned long long col = sample0 + (unsigned long long)(idx - (long long)s * B);
+    DropRng r = rng;
+    r.site = site0 + (uint32_t)s;
+    const uint4 w = drop_words(r, col >> 2);
+    const uint32_t ww[4] = {w.x, w.y, w.z, w.w};
+    out[idx] = ww[col & 3] >= sites.thresh[s] ? sites.scale[s] : 0.f;
+  }
+}
+
+extern "C" int medmoe_drop_path_scales(float* out, const double* p_host, int n_sites, int B, long long sample0, long long seed, long long step,
+                                       long long site0, hipStream_t stream) {
+  if (!out || !p_host) return MM_ERR_ARG;
+  if (n_sites <= 0 || n_sites > DP_MAX_SITES || B <= 0 || sample0 < 0) return MM_ERR_SHAPE;
+  DropPathSites sites;
+  for (int s = 0; s < DP_MAX_SITES; ++s) { sites.thresh[s] = 0u; sites.scale[s] = 1.f; }
+  for (int s = 0; s < n_sites; ++s) {
+    const double p = p_host[s];
+    if (!(p >= 0.0 && p < 1.0)) return MM_ERR_ARG;
+    sites.thresh[s] = (uint32_t)(unsigned long long)(p * 4294967296.0);      // floor(p * 2^32), exact in a double
+    sites.scale[s] = (float)(1.0 / (1.0 - p));
+  }
+  const long long n = (long long)n_sites * B;
+  const int grid = (int)min((n + 255) / 256, (long long)256 * 16);
+  hipLaunchKernelGGL(drop_path_scales_kernel, dim3(grid), dim3(256), 0, stream, out, sites, n_sites, B, (unsigned long long)sample0,
+                     make_drop_rng(seed, step, site0, 0, 1.f), (uint32_t)site0);
+  return mm_check_launch();
+}
+
+// x1 = bf16(residual + scale[row / rows_per_sample] * z) (product and sum in fp32);  y = LayerNorm(x1) with the statistics of the
+// bf16-rounded x1.  Geometry of dropout_add_layernorm_fwd_kernel.  A row whose scale is 0 COPIES residual: z is not loaded, so whatever
+// it holds there (inf, nan) cannot reach x1.  The branch is uniform over the wave (one row per wave).
+__global__ __launch_bounds__(256) void scale_add_layernorm_fwd_kernel(const bf16_t* __restrict__ z, const bf16_t* __restrict__ res,
+                                                                      const float* __restrict__ scale, int rows_per_sample,
+                                                                      const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                      bf16_t* __restrict__ x1, bf16_t* __restrict__ y,
+                                                                      float* __restrict__ mean_out, float* __restrict__ rstd_out, int rows, int D,
+                                                                      float eps) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int nchunk = D >> 3;
+  for (int row = blockIdx.x * 4 + wid; row < rows; row += gridDim.x * 4) {
+    const long long ro = (long long)row * D;
+    const float sc = scale[row / rows_per_sample];
+    const bool kept = sc != 0.f;
+    float v[DLN_MAX_CHUNKS][8];
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < DLN_MAX_CHUNKS; ++i) {
+      const int c = lane + i * 64;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[i][e] = 0.f;
+      if (c < nchunk) {
+        const uint4 rr = *(const uint4*)(res + ro + c * 8);
+        uint32_t pk[4] = {rr.x, rr.y, rr.z, rr.w};
+        if (kept) {
+          const uint4 zr = *(const uint4*)(z + ro + c * 8);
+          const uint32_t zw[4] = {zr.x, zr.y, zr.z, zr.w};
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const float xa = __uint_as_float(pk[e] << 16) + sc * __uint_as_float(zw[e] << 16);
+            const float xb = __uint_as_float(pk[e] & 0xffff0000u) + sc * __uint_as_float(zw[e] & 0xffff0000u);
+            pk[e] = pack2bf(xa, xb);
+          }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          v[i][2 * e] = __uint_as_float(pk[e] << 16);
+          v[i][2 * e + 1] = __uint_as_float(pk[e] & 0xffff0000u);
+          s += v[i][2 * e] + v[i][2 * e + 1];
+        }
+        *(uint4*)(x1 + ro + c * 8) = make_uint4(pk[0], pk[1], pk[2], pk[3]);
+      }
+    }
+    const float mean = wave_sum(s) / (float)D;
+    float sq = 0.f;
+#pragma unroll
+    for (int i = 0; i < DLN_MAX_CHUNKS; ++i)
+      if (lane + i * 64 < nchunk)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { const float d = v[i][e] - mean; sq += d * d; }
+    const float rstd = rsqrtf(wave_sum(sq) / (float)D + eps);
+    if (lane == 0) { mean_out[row] = mean; rstd_out[row] = rstd; }
+#pragma unroll
+    for (int i = 0; i < DLN_MAX_CHUNKS; ++i) {
+      const int c = lane + i * 64;
+      if (c < nchunk) {
+        const float4 g0 = *(const float4*)(gamma + c * 8), g1 = *(const float4*)(gamma + c * 8 + 4);
+        const float4 b0 = *(const float4*)(beta + c * 8), b1 = *(const float4*)(beta + c * 8 + 4);
+        const float gg[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
+        const float bb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+        float o[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = (v[i][e] - mean) * rstd * gg[e] + bb[e];
+        *(uint4*)(y + ro + c * 8) = make_uint4(pack2bf(o[0], o[1]), pack2bf(o[2], o[3]), pack2bf(o[4], o[5]), pack2bf(o[6], o[7]));
+      }
+    }
+  }
+}
+
+extern "C" int medmoe_scale_add_layernorm_fwd(const void* z, const void* residual, const float* scale, int rows_per_sample, const float* gamma,
+                                              const float* beta, void* x1, void* y, float* mean, float* rstd, int rows, int D, float eps,
+                                              hipStream_t stream) {
+  if (!z || !residual || !scale || !gamma || !beta || !x1 || !y || !mean || !rstd) return MM_ERR_ARG;
+  if (rows <= 0 || rows_per_sample <= 0 || (rows % rows_per_sample) || D <= 0 || (D % 8) || D > 64 * 8 * DLN_MAX_CHUNKS) return MM_ERR_SHAPE;
+  const int grid = min((rows + 3) / 4, 256 * 8);
+  hipLaunchKernelGGL(scale_add_layernorm_fwd_kernel, dim3(grid), dim3(256), 0, stream, (const bf16_t*)z, (const bf16_t*)residual, scale,
+                     rows_per_sample, gamma, beta, (bf16_t*)x1, (bf16_t*)y, mean, rstd, rows, D, eps);
   return mm_check_launch();
 }
 

@@ -9,11 +9,14 @@
 //   keep     = word >= thresh,  thresh = floor(p * 2^32) computed on the host;  survivors are scaled by 1 / (1 - p) in fp32
 //   site     = 4 * layer + {0 attention probabilities, 1 after the output projection, 2 after FC2};  DROPOUT_SITE_EMBED for the
 //              embedding LayerNorm's output
+//   stochastic depth of the image tower: site = DROPOUT_SITE_VIT_DROP_PATH + 2 * layer + {0 attention branch, 1 feed-forward
+//              branch}; ONE draw per sample: the keep bit of global sample g is element (row 0, column g) of a [1][cols_padded] array
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #define DROPOUT_SITE_EMBED 0xffffffffu
+#define DROPOUT_SITE_VIT_DROP_PATH 0x40000000u
 
 struct DropRng {
   uint32_t k0, k1;      // the two halves of the seed

@@ -140,6 +140,15 @@ class Engine:
             raise NotImplementedError("text_hidden_dropout / text_attn_dropout > 0 (model.model.text.hidden_dropout_prob / "
                                       "attention_probs_dropout_prob) with MEDMOE_GRAPH=1: the dropout step counter is a by-value launch "
                                       "argument, a replayed graph would repeat one step's masks")
+        # stochastic depth of the image tower (cfg.vit_drop_path).  train_step draws the per-sample scales of every site of the step
+        # (ws["vit_dp"], [n_layer_v, 2, B] fp32: 0 | 1 / (1 - p_l); [:, 0] the attention branch, [:, 1] the feed-forward branch) and points
+        # vit_drop_scales at them for its own forward and backward; None everywhere else: eval_step, forward_image outside a training step and the
+        # exports never drop.  Tests (and callers that drive _vit_blocks / _vit_backward themselves) may assign a tensor of that shape: the layers
+        # with p_l > 0 then take the scaled launches with exactly these values, until it is set back to None.
+        self.vit_drop_scales: Optional[torch.Tensor] = None
+        if cfg.vit_drop_path > 0.0 and os.environ.get("MEDMOE_GRAPH", "0") == "1":
+            raise NotImplementedError("vit_drop_path > 0 (model.model.vision.drop_path_rate) with MEDMOE_GRAPH=1: the dropout step counter is a "
+                                      "by-value launch argument, a replayed graph would repeat one step's masks")
         if not torch.cuda.is_available():
             raise RuntimeError("medmoe_amd.Engine needs a GPU: the HIP path is the only path")
         self.cfg = cfg
@@ -358,6 +367,11 @@ class Engine:
         # backward scratch
         buf("dxa", (M, Dv)); buf("dxb", (M, Dv)); buf("dln", (M, Dv)); buf("dqkv", (M, 3 * Dv)); buf("datt", (M, Dv))
         buf("dz", (M, c.ff_v)); buf("delta", (B * H * Nt,), F32)
+        if c.vit_drop_path > 0.0:
+            # the scales of a step; dp_a: a branch's GEMM output before its scale + residual + LayerNorm launch (forward), the scaled out-proj
+            # gradient (backward); dp_b: the scaled FC2 gradient.  Two gradient copies: the side stream's FC2 wgrad may still read one while
+            # the main stream writes the other
+            buf("vit_dp", (L, 2, B), F32); buf("dp_a", (M, Dv)); buf("dp_b", (M, Dv))
         ws["rowmap_patch"] = (torch.arange(B * P, device=dev) // P * Nt + 1 + torch.arange(B * P, device=dev) % P).to(I32)
         # MoE
         E, k, Do, Dh = c.n_expert, c.top_k, c.d_out, c.d_out // 2
@@ -483,27 +497,60 @@ class Engine:
         intermediate the backward needs stays in the workspace.  tests/test_ref_fixtures_gpu.py feeds the reference's own
         TransformerEncoder fixture in here."""
         c, p, ws = self.cfg, self.params, self.ws
-        Nt, Dv, H = c.n_tok_v, c.d_v, c.n_head_v
-        for l in range(c.n_layer_v):
+        Nt, Dv, H, L = c.n_tok_v, c.d_v, c.n_head_v, c.n_layer_v
+        dp = self._vit_drop_layers()
+        ln_done = False                                      # the previous layer's feed-forward site already wrote this LayerNorm
+        for l in range(L):
             pre = f"vit.layer.{l}."
             x, xo = ws[f"x{l}"], ws[f"x{l + 1}"]
             st1, st2 = ws[f"st1_{l}"], ws[f"st2_{l}"]
-            ops.layernorm_fwd(x, p.f32(pre + "attention_layernorm.weight"), p.f32(pre + "attention_layernorm.bias"),
-                              ws[f"ln1_{l}"], st1[0], st1[1], c.eps_v)
+            if not ln_done:
+                ops.layernorm_fwd(x, p.f32(pre + "attention_layernorm.weight"), p.f32(pre + "attention_layernorm.bias"),
+                                  ws[f"ln1_{l}"], st1[0], st1[1], c.eps_v)
+            ln_done = False
             ops.gemm_nt(ws[f"ln1_{l}"], p.w16(pre + "attention.input_proj.weight"), ws[f"qkv{l}"],
                         bias=p.f32(pre + "attention.input_proj.bias"))
             ops.attn_fwd(ws[f"qkv{l}"], ws[f"att{l}"], ws[f"lse{l}"], None, B, Nt, H)
-            ops.gemm_nt(ws[f"att{l}"], p.w16(pre + "attention.output_proj.weight"), ws[f"xmid{l}"],
-                        bias=p.f32(pre + "attention.output_proj.bias"), residual=x)
-            ops.layernorm_fwd(ws[f"xmid{l}"], p.f32(pre + "feedforward_layernorm.weight"),
-                              p.f32(pre + "feedforward_layernorm.bias"), ws[f"ln2_{l}"], st2[0], st2[1], c.eps_v)
+            if dp[l] is None:
+                ops.gemm_nt(ws[f"att{l}"], p.w16(pre + "attention.output_proj.weight"), ws[f"xmid{l}"],
+                            bias=p.f32(pre + "attention.output_proj.bias"), residual=x)
+                ops.layernorm_fwd(ws[f"xmid{l}"], p.f32(pre + "feedforward_layernorm.weight"),
+                                  p.f32(pre + "feedforward_layernorm.bias"), ws[f"ln2_{l}"], st2[0], st2[1], c.eps_v)
+            else:
+                # stochastic depth (DESIGN 3j): the GEMM leaves the branch in dp_a; the per-sample scale, the residual add and the LayerNorm
+                # that follows it are one launch
+                ops.gemm_nt(ws[f"att{l}"], p.w16(pre + "attention.output_proj.weight"), ws["dp_a"], bias=p.f32(pre + "attention.output_proj.bias"))
+                ops.scale_add_layernorm_fwd(ws["dp_a"], x, dp[l][0], Nt, p.f32(pre + "feedforward_layernorm.weight"),
+                                            p.f32(pre + "feedforward_layernorm.bias"), ws[f"xmid{l}"], ws[f"ln2_{l}"], st2[0], st2[1], c.eps_v)
             ops.gemm_nt(ws[f"ln2_{l}"], p.w16(pre + "feedforward.model.0.weight"), ws[f"h{l}"],
                         bias=p.f32(pre + "feedforward.model.0.bias"), aux=ws[f"z{l}"], epi=ops.EPI_GELU_DAUX)    # aux <- GELU'(z): the backward epilogue is one multiply
-            ops.gemm_nt(ws[f"h{l}"], p.w16(pre + "feedforward.model.2.weight"), xo,
-                        bias=p.f32(pre + "feedforward.model.2.bias"), residual=ws[f"xmid{l}"])
-        xl = ws[f"x{c.n_layer_v}"]
-        ops.layernorm_fwd(xl, p.f32("vit.final_layer_norm.weight"), p.f32("vit.final_layer_norm.bias"), ws["lnf"],
-                          ws["stf"][0], ws["stf"][1], c.eps_v)
+            if dp[l] is None:
+                ops.gemm_nt(ws[f"h{l}"], p.w16(pre + "feedforward.model.2.weight"), xo,
+                            bias=p.f32(pre + "feedforward.model.2.bias"), residual=ws[f"xmid{l}"])
+            else:
+                # the feed-forward site writes the NEXT LayerNorm with it: ln1 of layer l + 1, or the final one
+                ops.gemm_nt(ws[f"h{l}"], p.w16(pre + "feedforward.model.2.weight"), ws["dp_a"], bias=p.f32(pre + "feedforward.model.2.bias"))
+                nxt = f"vit.layer.{l + 1}.attention_layernorm." if l + 1 < L else "vit.final_layer_norm."
+                y, st = (ws[f"ln1_{l + 1}"], ws[f"st1_{l + 1}"]) if l + 1 < L else (ws["lnf"], ws["stf"])
+                ops.scale_add_layernorm_fwd(ws["dp_a"], ws[f"xmid{l}"], dp[l][1], Nt, p.f32(nxt + "weight"), p.f32(nxt + "bias"), xo, y,
+                                            st[0], st[1], c.eps_v)
+                ln_done = True
+        if not ln_done:
+            xl = ws[f"x{L}"]
+            ops.layernorm_fwd(xl, p.f32("vit.final_layer_norm.weight"), p.f32("vit.final_layer_norm.bias"), ws["lnf"],
+                              ws["stf"][0], ws["stf"][1], c.eps_v)
+
+    def _vit_drop_layers(self):
+        """Per layer: None (today's launches) or the layer's [2, B] scales - the layers with p_l > 0 while self.vit_drop_scales is set."""
+        L = self.cfg.n_layer_v
+        sc = self.vit_drop_scales
+        if sc is None:
+            return [None] * L
+        if "dp_a" not in self.ws:
+            raise RuntimeError("vit_drop_scales is set on an engine built with vit_drop_path = 0: it has no buffers for the scaled launches")
+        if sc.dtype != F32 or tuple(sc.shape) != (L, 2, self.B) or not sc.is_contiguous():
+            raise ValueError(f"vit_drop_scales must be a contiguous fp32 [{L}, 2, {self.B}] tensor, got {sc.dtype} {tuple(sc.shape)}")
+        return [sc[l] if pl > 0.0 else None for l, pl in enumerate(self.cfg.vit_drop_path_rates())]
 
     def _moe_forward(self, B):
         c, p, ws = self.cfg, self.params, self.ws
@@ -1175,6 +1222,7 @@ class Engine:
             wait(w_moe)                  # the experts' weight gradients ran on the second stream
             bucket_ready(L + 1)          # final LN + router + experts: complete
         stage_of = {l: s for s, l in enumerate(c.stage_layers())} if stage_grads else {}
+        dp = self._vit_drop_layers()
         w_dz = w_dx2 = w_dqkv = None                       # last wgrad that READ the scratch buffer
         for l in range(L - 1, -1, -1):
             pre = f"vit.layer.{l}."
@@ -1182,22 +1230,34 @@ class Engine:
                 ops.call("stage_grad_add", ws["dF"][stage_of[l + 1]], ws["slot_of"], dx, B, k, P, Nt, Dv)
             st1, st2 = ws[f"st1_{l}"], ws[f"st2_{l}"]
             # FFN: x_out = h W2^T + b2 + xmid
-            w_dx = wgrad(dx, ws[f"h{l}"], p.grad(pre + "feedforward.model.2.weight"), db=p.grad(pre + "feedforward.model.2.bias"))
+            # stochastic depth: the branch gradient is s[l, 1] (.) dx, a copy of its own (after stage_grad_add; the LayerNorm-backward below
+            # keeps the unscaled dx for the identity path).  dp_b was last read by layer l + 1's FC2 wgrad, which that layer waited for
+            g2 = dx
+            if dp[l] is not None:
+                g2 = ws["dp_b"]
+                ops.call("drop_path", dx, None, dp[l][1], g2, B, Nt * Dv)
+            w_dx = wgrad(g2, ws[f"h{l}"], p.grad(pre + "feedforward.model.2.weight"), db=p.grad(pre + "feedforward.model.2.bias"))
             wait(w_dz)
-            ops.gemm_nt(dx, p.w16t(pre + "feedforward.model.2.weight"), ws["dz"], aux=ws[f"z{l}"], epi=ops.EPI_MUL_AUX)
+            ops.gemm_nt(g2, p.w16t(pre + "feedforward.model.2.weight"), ws["dz"], aux=ws[f"z{l}"], epi=ops.EPI_MUL_AUX)
             w_dz = wgrad(ws["dz"], ws[f"ln2_{l}"], p.grad(pre + "feedforward.model.0.weight"), db=p.grad(pre + "feedforward.model.0.bias"))
             ops.gemm_nt(ws["dz"], p.w16t(pre + "feedforward.model.0.weight"), ws["dln"])
             wait(w_dx2)
             ops.layernorm_bwd(ws["dln"], ws[f"xmid{l}"], st2[0], st2[1], p.f32(pre + "feedforward_layernorm.weight"), dx2,
                               p.grad(pre + "feedforward_layernorm.weight"), p.grad(pre + "feedforward_layernorm.bias"), add=dx, det=self._det)
             # attention: xmid = att Wo^T + bo + x
-            w_dx2 = wgrad(dx2, ws[f"att{l}"], p.grad(pre + "attention.output_proj.weight"), db=p.grad(pre + "attention.output_proj.bias"))
-            ops.gemm_nt(dx2, p.w16t(pre + "attention.output_proj.weight"), ws["datt"])
+            # dp_a was last read by layer l + 1's out-proj wgrad: wait(w_dx2) above covers it
+            g1 = dx2
+            if dp[l] is not None:
+                g1 = ws["dp_a"]
+                ops.call("drop_path", dx2, None, dp[l][0], g1, B, Nt * Dv)
+            w_dx2 = wgrad(g1, ws[f"att{l}"], p.grad(pre + "attention.output_proj.weight"), db=p.grad(pre + "attention.output_proj.bias"))
+            ops.gemm_nt(g1, p.w16t(pre + "attention.output_proj.weight"), ws["datt"])
             wait(w_dqkv)
             ops.attn_bwd(ws[f"qkv{l}"], ws[f"att{l}"], ws["datt"], ws[f"lse{l}"], None, ws["dqkv"], ws["delta"], B, Nt, H)
             w_dqkv = wgrad(ws["dqkv"], ws[f"ln1_{l}"], p.grad(pre + "attention.input_proj.weight"), db=p.grad(pre + "attention.input_proj.bias"))
             ops.gemm_nt(ws["dqkv"], p.w16t(pre + "attention.input_proj.weight"), ws["dln"])
-            wait(w_dx)                                       # the FC2 wgrad read dx: done before LayerNorm-backward rewrites it
+            wait(w_dx)                                       # the FC2 wgrad read dx (or dp_b): done before LayerNorm-backward rewrites dx
+                                                             # (and before the next layer rewrites dp_b)
             ops.layernorm_bwd(ws["dln"], ws[f"x{l}"], st1[0], st1[1], p.f32(pre + "attention_layernorm.weight"), dx,
                               p.grad(pre + "attention_layernorm.weight"), p.grad(pre + "attention_layernorm.bias"), add=dx2, det=self._det)
             if bucket_ready is not None:
@@ -1233,11 +1293,29 @@ class Engine:
             with torch.cuda.stream(side):
                 self.forward_text(batch["ids"], batch["attn_mask"], batch.get("token_type"), training=True)
                 done = torch.cuda.Event(); done.record(side)
-            self.forward_image(batch["image"])
+            self._forward_image_train(batch["image"])
             main.wait_event(done)
         else:
-            self.forward_image(batch["image"])
+            self._forward_image_train(batch["image"])
             self.forward_text(batch["ids"], batch["attn_mask"], batch.get("token_type"), training=True)
+        try:
+            return self._train_step_rest(batch, optimizer, loss_scale)
+        finally:
+            self.vit_drop_scales = None                             # whatever runs next (evaluation, a bare forward_image) drops nothing
+
+    def _forward_image_train(self, images: torch.Tensor):
+        """forward_image of a training step: with cfg.vit_drop_path > 0 under the stochastic-depth scales of self.dropout_step, drawn here by
+        ONE launch for all 2 L sites ahead of the tower (column offset = this rank's first sample; they stay in ws["vit_dp"] for the backward
+        of the same step)."""
+        c = self.cfg
+        if c.vit_drop_path > 0.0:
+            probs = [pl for pl in c.vit_drop_path_rates() for _ in range(2)]
+            ops.drop_path_scales(self.ws["vit_dp"], probs, self.B, self.rank * self.B, c.dropout_seed, self.dropout_step)
+            self.vit_drop_scales = self.ws["vit_dp"]
+        self.forward_image(images)
+
+    def _train_step_rest(self, batch: Dict[str, torch.Tensor], optimizer: bool, loss_scale: float):
+        """train_step from the losses on: backward, gradient exchange, optimiser."""
         self.forward_backward_losses(batch["label"], loss_scale)
         if self.dist:
             from . import dist as D_

@@ -460,6 +460,53 @@ def dropout_add_layernorm_fwd(z, residual, gamma, beta, x1, y, mean, rstd, eps, 
     return y
 
 
+# stochastic depth of the image tower: site DROPOUT_SITE_VIT_DROP_PATH + 2 * layer + {0 attention branch, 1 feed-forward branch},
+# one draw per sample - the keep bit of global sample g is element (0, g) of a one-row mask array
+DROPOUT_SITE_VIT_DROP_PATH = 0x40000000
+DROP_PATH_MAX_SITES = 128
+
+
+def drop_path_scales(out, probs, B, sample0, seed, step, site0=DROPOUT_SITE_VIT_DROP_PATH):
+    """out [len(probs), B] fp32 = 0 | fp32(1 / (1 - probs[s])): sample b survives at site s iff dropout_mask (one row, site site0 + s,
+    dropout_thresh(probs[s])) keeps column sample0 + b.  The probabilities are host floats and travel by value: ONE launch, no read-back."""
+    _need(out, torch.float32, "out")
+    probs = [float(p) for p in probs]
+    n = len(probs)
+    if not 1 <= n <= DROP_PATH_MAX_SITES or B <= 0 or sample0 < 0 or out.numel() != n * B or not out.is_contiguous():
+        raise ValueError(f"drop_path_scales: out must be contiguous [n_sites, B] with 1 <= n_sites <= {DROP_PATH_MAX_SITES}, sample0 >= 0")
+    for p in probs:
+        dropout_thresh(p)                                        # refuses a probability outside [0, 1)
+    host = (_c.c_double * n)(*probs)
+    seed = dropout_rng(seed, step, site0, 0.0)[0]
+    fn = _fn("drop_path_scales")
+    with _Timed("drop_path_scales_kernel", 4.0 * n * B, "byte"):
+        _chk(fn(out.data_ptr(), _c.addressof(host), n, int(B), int(sample0), seed, step & 0xFFFFFFFF, site0 & 0xFFFFFFFF, _stream_handle()),
+             "drop_path_scales")
+    return out
+
+
+def scale_add_layernorm_fwd(z, residual, scale, rows_per_sample, gamma, beta, x1, y, mean, rstd, eps):
+    """x1 = bf16(residual + scale[row // rows_per_sample] * z); y = LayerNorm(x1); mean / rstd as layernorm_fwd leaves them.  A row whose
+    scale is 0 copies residual (z is not read there).  D % 8 == 0, D <= 2048."""
+    for t, nm in ((z, "z"), (residual, "residual"), (x1, "x1"), (y, "y")):
+        _need(t, torch.bfloat16, nm)
+        if not t.is_contiguous() or t.numel() != z.numel():
+            raise ValueError(f"scale_add_layernorm_fwd: {nm} must be contiguous and sized like z")
+    for t, nm in ((scale, "scale"), (gamma, "gamma"), (beta, "beta"), (mean, "mean"), (rstd, "rstd")):
+        _need(t, torch.float32, nm)
+    D = z.shape[-1]
+    rows = z.numel() // D
+    if D % 8 or D > 2048:
+        raise ValueError(f"scale_add_layernorm_fwd: D must be a multiple of 8 and <= 2048, got {D}")
+    if rows_per_sample <= 0 or rows % rows_per_sample or scale.numel() != rows // rows_per_sample or not scale.is_contiguous():
+        raise ValueError(f"scale_add_layernorm_fwd: scale must hold one contiguous value per sample ({rows} rows / {rows_per_sample} per sample), "
+                         f"got {scale.numel()}")
+    if gamma.numel() != D or beta.numel() != D or mean.numel() < rows or rstd.numel() < rows:
+        raise ValueError("scale_add_layernorm_fwd: gamma / beta must hold D values, mean / rstd one per row")
+    call("scale_add_layernorm_fwd", z, residual, scale, rows_per_sample, gamma, beta, x1, y, mean, rstd, rows, D, eps)
+    return y
+
+
 def _attn_drop_check(name, qkv, out, lse, key_mask, B, N, H):
     _need(qkv, torch.bfloat16, "qkv"); _need(out, torch.bfloat16, "out"); _need(lse, torch.float32, "lse")
     D = H * 64
@@ -609,6 +656,7 @@ _SIGS = {
     "win_attn_fwd": "ppppiiiiii", "win_attn_bwd": "ppppppiiiiii", "patch_merge": "ppiiiii", "drop_path": "ppppil",
     "dropout_mask": "pliillll", "dropout_apply": "ppliillllf", "dropout_add_layernorm_fwd": "ppppppppiifllllf",
     "attn_drop_fwd": "ppppiiiillllf", "attn_drop_bwd": "pppppppiiiillllf",
+    "drop_path_scales": "ppiillll", "scale_add_layernorm_fwd": "pppippppppiif",
     "gemm_tn_cols_det": "pipipiiiiilllilpl", "gemm_tn_gram_det": "piplipiiiill", "scale_attn_bwd_det": "ppppppppppiipppppiiipipl",
     "router_bwd_det": "pppppppfpppiiiip", "ce_strided_det": "ppiilliffipp", "soft_xent_strided_det": "pppiillffffipp", "hardneg_strided_det": "ppiillffipp",
     "cos_scale_bwd_det": "ppppppiif",
@@ -700,6 +748,7 @@ _COSTS = {
     "scale_attn_bwd_det": lambda a: ("scale_attn_bwd_kernel<DET> + scale_attn_bwd_reduce_kernel", 2.0 * a[17] * (4 * (2 * a[18] + 2 * a[19]) + 2 * a[18]), "byte"),
     "scale_attn_fwd": lambda a: ("scale_attn_fwd_kernel", 2.0 * a[8] * (4 * (a[9] + a[10]) + a[9]), "byte"),
     "dropout_add_layernorm_fwd": lambda a: ("dropout_add_layernorm_fwd_kernel", 8.0 * a[8] * a[9], "byte"),    # z, residual read; x1, y written
+    "scale_add_layernorm_fwd": lambda a: ("scale_add_layernorm_fwd_kernel", 8.0 * a[10] * a[11], "byte"),       # z, residual read; x1, y written
     "attn_drop_fwd": lambda a: ("attn_drop_fwd_kernel", 4.0 * a[5] * a[5] * 64 * a[4] * a[6], "flop"),
     "attn_drop_bwd": lambda a: ("attn_drop_bwd_kernel", 10.0 * a[8] * a[8] * 64 * a[7] * a[9], "flop"),
     # the adapters' own algorithmic traffic (a = the launch arguments): X once, the targeted qkv / dqkv columns, U / dU, dy

@@ -53,7 +53,7 @@ def config_from_hydra(vision: Any, text: Any) -> MedMoEConfig:
     if name:
         c = config_by_name(name)
         c.freeze_text = bool(_get(text, "freeze_bert", True))
-        return _text_dropout(c, text)
+        return _text_dropout(_vit_drop_path(c, vision), text)
     c = MedMoEConfig(**_ARCH[_get(vision, "arch", "vit_b16")])
     c.n_expert = int(_get(vision, "num_experts", 6))          # swin.py:83 default K=6 modalities
     c.top_k = int(_get(vision, "top_k", 1))
@@ -69,7 +69,16 @@ def config_from_hydra(vision: Any, text: Any) -> MedMoEConfig:
                                   f"or mxfp8 (e4m3 with one power-of-two scale per block of 32, the block-scaled MFMA)")
     c.expert_fp8 = dt == "fp8"
     c.expert_mx = dt == "mxfp8"
-    return _text_dropout(c, text)
+    return _text_dropout(_vit_drop_path(c, vision), text)
+
+
+def _vit_drop_path(c: MedMoEConfig, vision: Any) -> MedMoEConfig:
+    """model.model.vision.drop_path_rate: stochastic depth of the ViT tower (the reference's TransformerEncoder(drop_path_rate=)).
+    Absent: 0.0, nothing changes.  With arch: swin_t the same key sets the Swin tower's rate instead (MedMoE.__init__): the engine's ViT is a
+    placeholder there."""
+    if _get(vision, "arch", "vit_b16") != "swin_t" or _get(vision, "config_name"):
+        c.vit_drop_path = float(_get(vision, "drop_path_rate", 0.0))
+    return c
 
 
 def _text_dropout(c: MedMoEConfig, text: Any) -> MedMoEConfig:
@@ -130,6 +139,11 @@ class MedMoE(nn.Module):
         if _get(vision, "arch", "vit_b16") == "swin_t" and not _get(vision, "config_name"):
             from .swin import SWIN
             self.swin = SWIN(num_experts=self.cfg.n_expert, state_dict=_get(vision, "state_dict")).to(self.device)
+            rate = _get(vision, "drop_path_rate")                   # absent: SwinConfig.drop_path_rate of the checkpoint's config (0.1)
+            if rate is not None:
+                if not 0.0 <= float(rate) < 1.0:
+                    raise ValueError(f"model.model.vision.drop_path_rate must be in [0, 1), got {rate}")
+                self.swin.drop_path_rate = float(rate)
         self.weights = nn.Parameter(self.engine.params.p32, requires_grad=self.swin is None)          # flat fp32 master, shared storage
         self._synced_version = self.weights._version                 # bf16 working copies are current for this version
         # medmoe_module.py:196 calls .image_encoder.train(), :208 reads .text_encoder.tokenizer: both towers live in this
@@ -228,6 +242,10 @@ class MedMoE(nn.Module):
         if self.swin is not None:                                    # (global [B,768], local [B,768,56,56], router probabilities), swin.py:149
             self.engine._alloc(images.shape[0])                      # the text pass' buffers
             return self.swin(images)
+        if self.cfg.vit_drop_path > 0.0 and self.training and torch.is_grad_enabled():
+            raise NotImplementedError("vit_drop_path > 0 (model.model.vision.drop_path_rate) trains through the fused step (model.fused_step=true "
+                                      "-> Engine.train_step draws the stochastic-depth masks and scales the branch gradients); the torch-autograd "
+                                      "mirror runs the tower without drops, which is right for evaluation only")
         self.refresh_working_copies()
         img_g, img_l, probs = _ImageTowerFn.apply(self.weights, images.contiguous(), self.engine)
         B, P, D = img_l.shape
