@@ -296,6 +296,16 @@ int medmoe_sumsq_det_bf16(const void* g_bf16, long long n, float* out, float* sc
 int medmoe_adam_step_g16(float* p, const void* g_bf16, float* m, float* v, void* p_bf16, long long n, double lr, double beta1, double beta2, double eps, double weight_decay, int step, const float* grad_normsq, float max_norm, float grad_scale, hipStream_t stream);
 int medmoe_adam_groups_step_g16(float* p, const void* g_bf16, float* m, float* v, void* p_bf16, long long n, const long long* run_end, const float* run_lr_mult, const float* run_wd_mult, int n_runs, double lr, double beta1, double beta2, double eps, double weight_decay, int decoupled, int step, const float* grad_normsq, float max_norm, float grad_scale, hipStream_t stream);
 
+/* weight EMA inside the optimiser launch (no reference counterpart): the four steps above with two more arguments, `ema` (fp32, the
+   arena's layout) and `one_minus_decay` (1 - decay of THIS update, formed by the host in double and rounded once; in [0, 1], MM_ERR_ARG
+   otherwise).  p, m, v and the bf16 copy are bit-identical to the sibling's; behind the update of an element the same lane computes
+   ema = fadd_rn(ema, fmul_rn(one_minus_decay, fsub_rn(p_new, ema))) - three separately rounded fp32 operations, no contraction - and moves
+   the average as whole float4s next to p, m, v (8 B/param more).  No atomics, nothing read from the host. */
+int medmoe_adam_step_ema(float* p, const float* g, float* m, float* v, void* p_bf16, long long n, double lr, double beta1, double beta2, double eps, double weight_decay, int step, const float* grad_normsq, float max_norm, float grad_scale, float* ema, float one_minus_decay, hipStream_t stream);
+int medmoe_adam_groups_step_ema(float* p, const float* g, float* m, float* v, void* p_bf16, long long n, const long long* run_end, const float* run_lr_mult, const float* run_wd_mult, int n_runs, double lr, double beta1, double beta2, double eps, double weight_decay, int decoupled, int step, const float* grad_normsq, float max_norm, float grad_scale, float* ema, float one_minus_decay, hipStream_t stream);
+int medmoe_adam_step_ema_g16(float* p, const void* g_bf16, float* m, float* v, void* p_bf16, long long n, double lr, double beta1, double beta2, double eps, double weight_decay, int step, const float* grad_normsq, float max_norm, float grad_scale, float* ema, float one_minus_decay, hipStream_t stream);
+int medmoe_adam_groups_step_ema_g16(float* p, const void* g_bf16, float* m, float* v, void* p_bf16, long long n, const long long* run_end, const float* run_lr_mult, const float* run_wd_mult, int n_runs, double lr, double beta1, double beta2, double eps, double weight_decay, int decoupled, int step, const float* grad_normsq, float max_norm, float grad_scale, float* ema, float one_minus_decay, hipStream_t stream);
+
 /* fp32 -> bf16 copy of the master weights */
 int medmoe_cast_bf16(const float* src, void* dst, long long n, hipStream_t stream);
 

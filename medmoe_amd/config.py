@@ -95,6 +95,11 @@ class MedMoEConfig:
     no_decay_1d: bool = False
     text_lr_mult: float = 1.0
     layer_decay: float = 1.0
+    # exponential moving average of the weights (no reference counterpart): 0 = off.  Every arena the fused step steps keeps an fp32
+    # average e <- e + (1 - d_t) (p - e), updated inside the Adam launch; d_t = ema_decay, or with ema_warmup min(ema_decay, (1 + t) / (10 + t))
+    # at the t-th update.  Engine.ema_weights() / eval_step(ema=True) evaluate on it, checkpoints and exports carry it
+    ema_decay: float = 0.0
+    ema_warmup: bool = False
 
     @property
     def n_patch(self) -> int:
@@ -127,6 +132,8 @@ class MedMoEConfig:
             raise ValueError(f"vit_drop_path must be in [0, 1), got {self.vit_drop_path}")
         if self.grad_comm_dtype not in ("fp32", "bf16"):
             raise ValueError(f"grad_comm_dtype must be 'fp32' or 'bf16', got {self.grad_comm_dtype!r}")
+        if not 0.0 <= float(self.ema_decay) < 1.0:
+            raise ValueError(f"ema_decay must be in [0, 1) (0 = off), got {self.ema_decay}")
         if self.optimizer not in ("adam", "adamw"):
             raise ValueError(f"optimizer must be 'adam' or 'adamw', got {self.optimizer!r}")
         if len(tuple(self.adam_betas)) != 2 or not all(0.0 <= float(b) < 1.0 for b in self.adam_betas):

@@ -103,12 +103,32 @@ __device__ __forceinline__ void adam_update(float& p, float g, float& m, float& 
   p -= step_size * (m / denom);
 }
 
-template <typename GT>
+// Weight EMA inside the Adam launch.  The EMA = true instantiations of the two kernels below take two more arguments, `float* ema`
+// (fp32, the arena's layout) and `float omd` (1 - decay of this update, formed on the host), and average the parameter they have just
+// updated while it is in registers: E <- fadd_rn(E, fmul_rn(omd, fsub_rn(P, E))).  Three separately rounded fp32 operations: the contraction
+// HIP applies by default is switched off for this one expression (the __f*_rn intrinsics are plain operators that it would still fuse), so
+// torch's e + omd * (p - e) in fp32 reproduces it bit for bit.  The average is moved as whole float4s next to p, m, v: 8 B/param on top of
+// the launch's 34.  The EMA = false instantiations have no such arguments and are the kernels as they were.
+__device__ __forceinline__ void ema_update(float& e, float p, float omd) {
+#pragma clang fp contract(off)
+  const float d = p - e;
+  const float s = omd * d;
+  e = e + s;
+}
+__device__ __forceinline__ float* ema_ptr() { return nullptr; }
+__device__ __forceinline__ float* ema_ptr(float* ema, float) { return ema; }
+__device__ __forceinline__ float ema_omd() { return 0.f; }
+__device__ __forceinline__ float ema_omd(float*, float omd) { return omd; }
+
+template <typename GT, bool EMA = false, typename... EA>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const GT* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, bf16_t* __restrict__ p16, long long n,
                                                    float b2, float omb1, float omb2, float eps, float wd, float step_size,
                                                    float bc2_sqrt, const float* __restrict__ normsq, float max_norm,
-                                                   float grad_scale) {
+                                                   float grad_scale, EA... ema_args) {
+  static_assert(sizeof...(EA) == (EMA ? 2 : 0), "EMA = true: (float* ema, float omd) behind grad_scale; EMA = false: nothing");
+  float* __restrict__ const ema = ema_ptr(ema_args...);
+  const float omd = ema_omd(ema_args...);
   float coef = grad_scale;
   if (normsq && max_norm > 0.f) {
     const float nrm = sqrtf(*normsq) * grad_scale;
@@ -120,24 +140,52 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
     const float4 gg = grad4(g, i);
     float4 mm = *(float4*)(m + i * 4), vv = *(float4*)(v + i * 4);
     float* P = (float*)&pp; const float* G = (const float*)&gg; float* M = (float*)&mm; float* V = (float*)&vv;
+    float4 ee;
+    if constexpr (EMA) ee = *(const float4*)(ema + i * 4);
 #pragma unroll
     for (int e = 0; e < 4; ++e) adam_update(P[e], G[e], M[e], V[e], coef, wd, b2, omb1, omb2, eps, step_size, bc2_sqrt);
     *(float4*)(p + i * 4) = pp; *(float4*)(m + i * 4) = mm; *(float4*)(v + i * 4) = vv;
     if (p16) { uint2 o; o.x = pack2bf(P[0], P[1]); o.y = pack2bf(P[2], P[3]); *(uint2*)(p16 + i * 4) = o; }
+    if constexpr (EMA) {
+      float* E = (float*)&ee;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) ema_update(E[e], P[e], omd);
+      *(float4*)(ema + i * 4) = ee;
+    }
   }
 }
+
+// Host side of the plain step, shared by the fp32 / bf16 gradient and the EMA forms: `ea` is empty, or (ema, one_minus_decay).
+template <typename GT, bool EMA, typename... EA>
+static int adam_launch(float* p, const GT* g, float* m, float* v, void* p_bf16, long long n, double lr, double beta1, double beta2, double eps,
+                       double weight_decay, int step, const float* grad_normsq, float max_norm, float grad_scale, hipStream_t stream, EA... ea) {
+  if (!p || !g || !m || !v || n <= 0 || step < 1) return MM_ERR_ARG;
+  if (sizeof(GT) == 2 && ((uintptr_t)g & 7)) return MM_ERR_ARG;  // 8-byte loads of the bf16 gradient
+  if (n % 4) return MM_ERR_SHAPE;   // flat buffers are padded to a multiple of 4 by the host
+  const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+  const int grid = (int)min((n / 4 + 255) / 256, (long long)256 * 8);
+  hipLaunchKernelGGL((adam_kernel<GT, EMA, EA...>), dim3(grid), dim3(256), 0, stream, p, g, m, v, (bf16_t*)p_bf16, n, (float)beta2,
+                     (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, (float)weight_decay, (float)(lr / bc1),
+                     (float)sqrt(bc2), grad_normsq, max_norm, grad_scale, ea...);
+  return mm_check_launch();
+}
+
+// The average's arguments: a buffer, and 1 - decay in [0, 1] (0 leaves the average as it is).
+static bool ema_args_ok(const float* ema, float one_minus_decay) { return ema && one_minus_decay >= 0.f && one_minus_decay <= 1.f; }
 
 extern "C" int medmoe_adam_step(float* p, const float* g, float* m, float* v, void* p_bf16, long long n, double lr,
                                 double beta1, double beta2, double eps, double weight_decay, int step,
                                 const float* grad_normsq, float max_norm, float grad_scale, hipStream_t stream) {
-  if (!p || !g || !m || !v || n <= 0 || step < 1) return MM_ERR_ARG;
-  if (n % 4) return MM_ERR_SHAPE;   // flat buffers are padded to a multiple of 4 by the host
-  const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-  const int grid = (int)min((n / 4 + 255) / 256, (long long)256 * 8);
-  hipLaunchKernelGGL(adam_kernel<float>, dim3(grid), dim3(256), 0, stream, p, g, m, v, (bf16_t*)p_bf16, n, (float)beta2,
-                     (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, (float)weight_decay, (float)(lr / bc1),
-                     (float)sqrt(bc2), grad_normsq, max_norm, grad_scale);
-  return mm_check_launch();
+  return adam_launch<float, false>(p, g, m, v, p_bf16, n, lr, beta1, beta2, eps, weight_decay, step, grad_normsq, max_norm, grad_scale, stream);
+}
+
+extern "C" int medmoe_adam_step_ema(float* p, const float* g, float* m, float* v, void* p_bf16, long long n, double lr,
+                                    double beta1, double beta2, double eps, double weight_decay, int step,
+                                    const float* grad_normsq, float max_norm, float grad_scale, float* ema, float one_minus_decay,
+                                    hipStream_t stream) {
+  if (!ema_args_ok(ema, one_minus_decay)) return MM_ERR_ARG;
+  return adam_launch<float, true>(p, g, m, v, p_bf16, n, lr, beta1, beta2, eps, weight_decay, step, grad_normsq, max_norm, grad_scale, stream,
+                                  ema, one_minus_decay);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -152,14 +200,17 @@ extern "C" int medmoe_adam_step(float* p, const float* g, float* m, float* v, vo
 // ---------------------------------------------------------------------------------------------
 #define ADAM_LDS_RUNS 1024
 
-template <bool LDS, typename GT>
+template <bool LDS, typename GT, bool EMA = false, typename... EA>
 __global__ __launch_bounds__(256) void adam_groups_kernel(float* __restrict__ p, const GT* __restrict__ g, float* __restrict__ m,
                                                           float* __restrict__ v, bf16_t* __restrict__ p16, long long n,
                                                           const long long* __restrict__ run_end, const float* __restrict__ run_lr,
                                                           const float* __restrict__ run_wd, int n_runs, float b2, float omb1, float omb2,
                                                           float eps, float wd, float step_size, float bc2_sqrt, double lr_d, double wd_d,
                                                           int decoupled, const float* __restrict__ normsq, float max_norm,
-                                                          float grad_scale) {
+                                                          float grad_scale, EA... ema_args) {
+  static_assert(sizeof...(EA) == (EMA ? 2 : 0), "EMA = true: (float* ema, float omd) behind grad_scale; EMA = false: nothing");
+  float* __restrict__ const ema = ema_ptr(ema_args...);
+  const float omd = ema_omd(ema_args...);
   __shared__ long long s_end[LDS ? ADAM_LDS_RUNS : 1];
   __shared__ float s_lr[LDS ? ADAM_LDS_RUNS : 1], s_wd[LDS ? ADAM_LDS_RUNS : 1];
   if (LDS) {
@@ -181,6 +232,8 @@ __global__ __launch_bounds__(256) void adam_groups_kernel(float* __restrict__ p,
     const float4 gg = grad4(g, i);
     float4 mm = *(float4*)(m + i * 4), vv = *(float4*)(v + i * 4);
     float* P = (float*)&pp; const float* G = (const float*)&gg; float* M = (float*)&mm; float* V = (float*)&vv;
+    float4 ee;
+    if constexpr (EMA) ee = *(const float4*)(ema + i * 4);
     const long long e0 = i * 4;
     int r = 0, hi = last;                                         // first run whose end lies behind e0 (r <= last whatever the table holds)
     while (r < hi) {
@@ -202,22 +255,47 @@ __global__ __launch_bounds__(256) void adam_groups_kernel(float* __restrict__ p,
     }
     *(float4*)(p + i * 4) = pp; *(float4*)(m + i * 4) = mm; *(float4*)(v + i * 4) = vv;
     if (p16) { uint2 o; o.x = pack2bf(P[0], P[1]); o.y = pack2bf(P[2], P[3]); *(uint2*)(p16 + i * 4) = o; }
+    if constexpr (EMA) {
+      float* E = (float*)&ee;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) ema_update(E[e], P[e], omd);
+      *(float4*)(ema + i * 4) = ee;
+    }
   }
+}
+
+template <typename GT, bool EMA, typename... EA>
+static int adam_groups_launch(float* p, const GT* g, float* m, float* v, void* p_bf16, long long n, const long long* run_end,
+                              const float* run_lr_mult, const float* run_wd_mult, int n_runs, double lr, double beta1, double beta2, double eps,
+                              double weight_decay, int decoupled, int step, const float* grad_normsq, float max_norm, float grad_scale,
+                              hipStream_t stream, EA... ea) {
+  if (!p || !g || !m || !v || !run_end || !run_lr_mult || !run_wd_mult || n <= 0 || n_runs < 1 || step < 1) return MM_ERR_ARG;
+  if (sizeof(GT) == 2 && ((uintptr_t)g & 7)) return MM_ERR_ARG;  // 8-byte loads of the bf16 gradient
+  if (n % 4) return MM_ERR_SHAPE;   // flat buffers are padded to a multiple of 4 by the host
+  const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+  const int grid = (int)min((n / 4 + 255) / 256, (long long)256 * 8);
+  auto kern = n_runs <= ADAM_LDS_RUNS ? adam_groups_kernel<true, GT, EMA, EA...> : adam_groups_kernel<false, GT, EMA, EA...>;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, stream, p, g, m, v, (bf16_t*)p_bf16, n, run_end, run_lr_mult, run_wd_mult, n_runs,
+                     (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, (float)weight_decay, (float)(lr / bc1),
+                     (float)sqrt(bc2), lr, weight_decay, decoupled ? 1 : 0, grad_normsq, max_norm, grad_scale, ea...);
+  return mm_check_launch();
 }
 
 extern "C" int medmoe_adam_groups_step(float* p, const float* g, float* m, float* v, void* p_bf16, long long n, const long long* run_end,
                                        const float* run_lr_mult, const float* run_wd_mult, int n_runs, double lr, double beta1,
                                        double beta2, double eps, double weight_decay, int decoupled, int step, const float* grad_normsq,
                                        float max_norm, float grad_scale, hipStream_t stream) {
-  if (!p || !g || !m || !v || !run_end || !run_lr_mult || !run_wd_mult || n <= 0 || n_runs < 1 || step < 1) return MM_ERR_ARG;
-  if (n % 4) return MM_ERR_SHAPE;   // flat buffers are padded to a multiple of 4 by the host
-  const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-  const int grid = (int)min((n / 4 + 255) / 256, (long long)256 * 8);
-  auto kern = n_runs <= ADAM_LDS_RUNS ? adam_groups_kernel<true, float> : adam_groups_kernel<false, float>;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, stream, p, g, m, v, (bf16_t*)p_bf16, n, run_end, run_lr_mult, run_wd_mult, n_runs,
-                     (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, (float)weight_decay, (float)(lr / bc1),
-                     (float)sqrt(bc2), lr, weight_decay, decoupled ? 1 : 0, grad_normsq, max_norm, grad_scale);
-  return mm_check_launch();
+  return adam_groups_launch<float, false>(p, g, m, v, p_bf16, n, run_end, run_lr_mult, run_wd_mult, n_runs, lr, beta1, beta2, eps, weight_decay,
+                                          decoupled, step, grad_normsq, max_norm, grad_scale, stream);
+}
+
+extern "C" int medmoe_adam_groups_step_ema(float* p, const float* g, float* m, float* v, void* p_bf16, long long n, const long long* run_end,
+                                           const float* run_lr_mult, const float* run_wd_mult, int n_runs, double lr, double beta1,
+                                           double beta2, double eps, double weight_decay, int decoupled, int step, const float* grad_normsq,
+                                           float max_norm, float grad_scale, float* ema, float one_minus_decay, hipStream_t stream) {
+  if (!ema_args_ok(ema, one_minus_decay)) return MM_ERR_ARG;
+  return adam_groups_launch<float, true>(p, g, m, v, p_bf16, n, run_end, run_lr_mult, run_wd_mult, n_runs, lr, beta1, beta2, eps, weight_decay,
+                                         decoupled, step, grad_normsq, max_norm, grad_scale, stream, ema, one_minus_decay);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -264,31 +342,35 @@ extern "C" int medmoe_sumsq_det_bf16(const void* g_bf16, long long n, float* out
 extern "C" int medmoe_adam_step_g16(float* p, const void* g_bf16, float* m, float* v, void* p_bf16, long long n, double lr,
                                     double beta1, double beta2, double eps, double weight_decay, int step,
                                     const float* grad_normsq, float max_norm, float grad_scale, hipStream_t stream) {
-  if (!p || !g_bf16 || !m || !v || n <= 0 || step < 1) return MM_ERR_ARG;
-  if ((uintptr_t)g_bf16 & 7) return MM_ERR_ARG;
-  if (n % 4) return MM_ERR_SHAPE;   // flat buffers are padded to a multiple of 4 by the host
-  const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-  const int grid = (int)min((n / 4 + 255) / 256, (long long)256 * 8);
-  hipLaunchKernelGGL(adam_kernel<bf16_t>, dim3(grid), dim3(256), 0, stream, p, (const bf16_t*)g_bf16, m, v, (bf16_t*)p_bf16, n, (float)beta2,
-                     (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, (float)weight_decay, (float)(lr / bc1),
-                     (float)sqrt(bc2), grad_normsq, max_norm, grad_scale);
-  return mm_check_launch();
+  return adam_launch<bf16_t, false>(p, (const bf16_t*)g_bf16, m, v, p_bf16, n, lr, beta1, beta2, eps, weight_decay, step, grad_normsq, max_norm,
+                                    grad_scale, stream);
+}
+
+extern "C" int medmoe_adam_step_ema_g16(float* p, const void* g_bf16, float* m, float* v, void* p_bf16, long long n, double lr,
+                                        double beta1, double beta2, double eps, double weight_decay, int step,
+                                        const float* grad_normsq, float max_norm, float grad_scale, float* ema, float one_minus_decay,
+                                        hipStream_t stream) {
+  if (!ema_args_ok(ema, one_minus_decay)) return MM_ERR_ARG;
+  return adam_launch<bf16_t, true>(p, (const bf16_t*)g_bf16, m, v, p_bf16, n, lr, beta1, beta2, eps, weight_decay, step, grad_normsq, max_norm,
+                                   grad_scale, stream, ema, one_minus_decay);
 }
 
 extern "C" int medmoe_adam_groups_step_g16(float* p, const void* g_bf16, float* m, float* v, void* p_bf16, long long n,
                                            const long long* run_end, const float* run_lr_mult, const float* run_wd_mult, int n_runs,
                                            double lr, double beta1, double beta2, double eps, double weight_decay, int decoupled, int step,
                                            const float* grad_normsq, float max_norm, float grad_scale, hipStream_t stream) {
-  if (!p || !g_bf16 || !m || !v || !run_end || !run_lr_mult || !run_wd_mult || n <= 0 || n_runs < 1 || step < 1) return MM_ERR_ARG;
-  if ((uintptr_t)g_bf16 & 7) return MM_ERR_ARG;
-  if (n % 4) return MM_ERR_SHAPE;   // flat buffers are padded to a multiple of 4 by the host
-  const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-  const int grid = (int)min((n / 4 + 255) / 256, (long long)256 * 8);
-  auto kern = n_runs <= ADAM_LDS_RUNS ? adam_groups_kernel<true, bf16_t> : adam_groups_kernel<false, bf16_t>;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, stream, p, (const bf16_t*)g_bf16, m, v, (bf16_t*)p_bf16, n, run_end, run_lr_mult,
-                     run_wd_mult, n_runs, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, (float)weight_decay,
-                     (float)(lr / bc1), (float)sqrt(bc2), lr, weight_decay, decoupled ? 1 : 0, grad_normsq, max_norm, grad_scale);
-  return mm_check_launch();
+  return adam_groups_launch<bf16_t, false>(p, (const bf16_t*)g_bf16, m, v, p_bf16, n, run_end, run_lr_mult, run_wd_mult, n_runs, lr, beta1, beta2,
+                                           eps, weight_decay, decoupled, step, grad_normsq, max_norm, grad_scale, stream);
+}
+
+extern "C" int medmoe_adam_groups_step_ema_g16(float* p, const void* g_bf16, float* m, float* v, void* p_bf16, long long n,
+                                               const long long* run_end, const float* run_lr_mult, const float* run_wd_mult, int n_runs,
+                                               double lr, double beta1, double beta2, double eps, double weight_decay, int decoupled,
+                                               int step, const float* grad_normsq, float max_norm, float grad_scale, float* ema,
+                                               float one_minus_decay, hipStream_t stream) {
+  if (!ema_args_ok(ema, one_minus_decay)) return MM_ERR_ARG;
+  return adam_groups_launch<bf16_t, true>(p, (const bf16_t*)g_bf16, m, v, p_bf16, n, run_end, run_lr_mult, run_wd_mult, n_runs, lr, beta1, beta2,
+                                          eps, weight_decay, decoupled, step, grad_normsq, max_norm, grad_scale, stream, ema, one_minus_decay);
 }
 
 __global__ __launch_bounds__(256) void cast_bf16_kernel(const float* __restrict__ s, bf16_t* __restrict__ d, long long n) {

@@ -9,12 +9,14 @@ encode_text / encode_image -> SWIN.forward (swin.py:130-149) -> MoE.forward (swi
 model_step (medmoe_module.py:284-316) -> GLORIA local/global losses (losses.py:757-794,
 954-1026) + CE on router probabilities (medmoe_module.py:235-237).
 """
+import contextlib
 import os
 from typing import Dict, Optional
 
 import numpy as np
 import torch
 
+from . import ema as ema_
 from . import ops
 from .local_generic import GenericLocalLoss
 from .local_ragged import RaggedLocalLoss
@@ -204,6 +206,11 @@ class Engine:
             self.tstore = TextStore(cfg, self.device, self.params.text)
             self.params.text = self.tstore.as_dict()             # views of the flat buffers: an optimiser step updates them in place
         self.apply_optimizer_groups()
+        # weight EMA (cfg.ema_decay > 0): every arena this engine steps keeps an fp32 average, updated by its Adam launch;
+        # ema_weights() points the working copies at it.  The Lightning module writes the key after the engine exists: optimizer_step looks
+        self._ema_active = False
+        if cfg.ema_decay > 0.0:
+            ema_.prepare(self.optimizer_stores().values())
         self.HWp, self.Tp, self.GW = ops.local_geometry(cfg.n_patch, cfg.max_len)
         # LDS-tiled pair kernels exist for 64 / 208 / 256 regions; any other geometry (576 regions of ViT-L/14 at 336 px) runs
         # the generic GEMM formulation (medmoe_amd/local_generic.py)
@@ -288,6 +295,49 @@ class Engine:
         lo, out = self.lora, {k: v.clone() for k, v in self.params.text.items()}
         for l in range(self.cfg.n_layer_t):
             ops.lora_merge(out[f"layer.{l}.attention.input_proj.weight"], lo.A16(l), lo.B16(l), lo.targets, lo.scale)
+        return out
+
+    # -- weight EMA --------------------------------------------------------------------------------------------------------------------------
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Context: the forward passes run on the AVERAGED weights (eval_step, forward_image, forward_text, merged_text_params).  On entry
+        every arena this engine steps loads its average into the working copies (FlatArena.load_ema), on exit - also when the body raises -
+        the master's come back.  No master, gradient or optimiser state is written; train_step / optimizer_step inside raise."""
+        if not self.cfg.ema_decay > 0.0:
+            raise RuntimeError("ema_weights: this engine keeps no average - cfg.ema_decay is 0 (model.ema.decay)")
+        if self._ema_active:
+            raise RuntimeError("ema_weights: already inside the context")
+        arenas = list(self.optimizer_stores().values())
+        ema_.prepare(arenas)
+        self._ema_active = True
+        try:
+            for a in arenas:
+                a.load_ema()
+            self._repoint_text()
+            yield self
+        finally:
+            for a in arenas:
+                if a.ema_loaded:
+                    a.restore_master()
+            self._ema_active = False
+            self._repoint_text()
+
+    def _repoint_text(self):
+        """The trainable text tower's name -> tensor dict holds fp32 VIEWS for embeddings, biases and LayerNorms: taken again whenever the
+        store switches between the master and the average."""
+        if self.tstore is not None:
+            self.params.text = self.tstore.as_dict()
+
+    def ema_params(self) -> Dict[str, torch.Tensor]:
+        """Reference-style names -> the fp32 averages (CPU tensors), for export: the image tower and MoE under their own names, the trainable
+        text tower's or the adapters' under `text.`.  A frozen base holds no average."""
+        if not self.cfg.ema_decay > 0.0:
+            raise RuntimeError("ema_params: this engine keeps no average - cfg.ema_decay is 0 (model.ema.decay)")
+        arenas = list(self.optimizer_stores().values())
+        ema_.prepare(arenas)
+        out = {}
+        for a in arenas:
+            out.update(a.export_named(a.e32))
         return out
 
     def apply_optimizer_groups(self):
@@ -1276,6 +1326,8 @@ class Engine:
         Gradient accumulation (accumulate_grad_batches of the trainer config): call with optimizer=False for all but the
         last micro-batch, zero_grad=False for all but the first, loss_scale = 1 / number of micro-batches; the reported
         losses are scaled the same way."""
+        if self._ema_active:
+            raise RuntimeError("train_step inside ema_weights(): the working copies hold the averaged weights - evaluate only")
         if self.use_graph and not self.dist and not self.train_text and batch["image"].is_cuda and ops.PROFILE is None:
             return self._train_step_graphed(batch, optimizer, zero_grad, loss_scale)
         B = batch["image"].shape[0]
@@ -1350,14 +1402,20 @@ class Engine:
     def optimizer_step(self, lr: Optional[float] = None):
         """clip_grad_norm_(cfg.clip) + torch.optim.Adam(lr, weight_decay) (cfg.optimizer = "adamw": torch.optim.AdamW; cfg.adam_betas /
         adam_eps; the parameter groups the stores carry), fused, on the gradients the stores hold; the working copies follow.  ONE clip
-        norm over both towers' gradients when the text tower trains, as clip_grad_norm_ over all parameters computes it."""
+        norm over both towers' gradients when the text tower trains, as clip_grad_norm_ over all parameters computes it.
+        cfg.ema_decay > 0: the same launches also advance every stepped arena's weight average."""
         c, image, text = self.cfg, self.params, self.text_arena() if self.train_text else None
+        if self._ema_active:
+            raise RuntimeError("optimizer_step inside ema_weights(): the working copies hold the averaged weights - evaluate only")
         lr = c.lr if lr is None else lr
         text_part = text.sumsq() if text is not None else None
         total = image.sumsq()
         if text is not None:
             total.add_(text_part)
         kw = dict(betas=tuple(c.adam_betas), eps=c.adam_eps, decoupled=c.optimizer == "adamw")
+        if c.ema_decay > 0.0:                                       # the same launches in their _ema form: every arena, the same decay arguments
+            ema_.prepare([image] if text is None else [image, text])
+            kw.update(ema_.step_kwargs(c))
         image.adam_step(total, lr, c.weight_decay, c.clip, **kw)
         if text is not None:
             text.adam_step(total, lr, c.weight_decay, c.clip, **kw)
@@ -1365,12 +1423,16 @@ class Engine:
     # ------------------------------------------------------------------------------------------
     # evaluation (medmoe_module.py:114-134 validation_step / test_step: model_step without a backward)
     # ------------------------------------------------------------------------------------------
-    def eval_step(self, batch: Dict[str, torch.Tensor]):
+    def eval_step(self, batch: Dict[str, torch.Tensor], ema: bool = False):
         """The losses of `train_step` on a batch, forward only: same dict, same weighting, device scalars.  No gradient, Adam moment, master
         or working parameter is written.  The towers and the global loss are the training launches; the local loss of the 196 / 64-region
         geometries runs medmoe_local_sim_fwd (csrc/local_eval.hip), which keeps a pair's scores and attention on the chip - an engine that
         only evaluates never allocates the ragged pair matrices; other geometries run the forward launches of the generic formulation.
-        The router's cross-entropy and accuracy come from medmoe_router_eval.  Always eager (no hipGraph replay)."""
+        The router's cross-entropy and accuracy come from medmoe_router_eval.  Always eager (no hipGraph replay).
+        ema=True: this one evaluation runs on the averaged weights (inside ema_weights())."""
+        if ema and not self._ema_active:
+            with self.ema_weights():
+                return self.eval_step(batch)
         c = self.cfg
         B = batch["image"].shape[0]
         self._alloc(B)

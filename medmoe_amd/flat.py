@@ -4,6 +4,9 @@ working copy `p16` in the nn.Linear [out, in] layout and a second one, `p16t`, h
 the same NT kernel as forward).  `refresh()` is two kernels (cast + batched transpose) whatever the number of parameters, the clip norm is
 summed in a fixed order (`sumsq`), and clip + Adam + the bf16 copy are one launch (`adam_step`) - also with parameter groups
 (`set_param_groups`: contiguous runs of the arena with their own learning-rate / weight-decay multipliers) and AdamW.
+With the weight EMA (`enable_ema`) an arena also holds `e32`, the fp32 average of the master in the same layout: `adam_step` takes the
+`_ema` form of its launch, which averages the parameter it has just updated, and `load_ema()` / `restore_master()` point the working copies at
+the average and back.
 With the bf16 gradient exchange an arena also holds `g16`, the bf16 copy that `pack` fills and the ranks all-reduce: `g32` keeps
 the rank-local fp32 sum (what accumulation over micro-batches needs), and while `g16_reduced` is set the clip norm and Adam read `g16`.
 
@@ -18,6 +21,7 @@ from typing import Dict, List, Sequence, Tuple
 import torch
 
 from . import ops
+from .ema import one_minus_decay
 
 _ALIGN = 8
 
@@ -81,6 +85,11 @@ class FlatArena:
         # then read it instead of g32.  g32 keeps the rank-local fp32 sum throughout: micro-batches accumulate there, unrounded.
         self._g16 = None
         self.g16_reduced = False
+        # weight EMA: `e32` (fp32, this layout) exists from enable_ema() on, `ema_updates` counts the updates it has seen (the
+        # warm-up schedule's t); `ema_loaded` says that the working copies currently hold the average (load_ema .. restore_master)
+        self.e32 = None
+        self.ema_updates = 0
+        self.ema_loaded = False
 
     # -- views: built once per buffer (a backward asks for a few hundred of them per step) -----------------------------------------------
     def view(self, flat, name, shape=None):
@@ -99,7 +108,16 @@ class FlatArena:
     def _form(self, name):
         return self._mat.get(name) or self.shapes[name]
 
-    def f32(self, name): return self._cached(0, self.p32, name)
+    def f32(self, name):
+        """fp32 view of `name` as the passes read it: of the master - of the average while load_ema() holds (biases, LayerNorms, embeddings
+        and the router are read in fp32, not from p16)."""
+        return self.ema(name) if self.ema_loaded else self._cached(0, self.p32, name)
+
+    def ema(self, name):
+        """fp32 view of `name`'s average (enable_ema() first)."""
+        if self.e32 is None:
+            raise RuntimeError("FlatArena.ema: this arena keeps no average (enable_ema())")
+        return self._cached(5, self.e32, name)
     def grad(self, name): return self._cached(1, self.g32, name)
 
     def w16(self, name):
@@ -122,14 +140,45 @@ class FlatArena:
 
     sync_working_copies = refresh                                   # the stores' earlier name for it: the same method
 
-    def _derive(self):
-        """What follows p16 after every update: the transposed copies, then the store's own derived copies."""
+    def _derive(self, src=None):
+        """What follows p16 after every update: the transposed copies, then the store's own derived copies.  `src`: the fp32 buffer p16 was
+        just cast from (None: the master)."""
         if self.tr_table is not None:
             ops.call("transpose_many", self.p16, self.p16t, self.tr_table, self.tr_table.shape[0], self.tr_max_tiles)
-        self.after_update()
+        if src is None:
+            self.after_update()
+        else:
+            self.after_update(src)
 
-    def after_update(self):
-        """Hook: copies a store derives from the fp32 master itself (ParamStore's 8-bit expert weights)."""
+    def after_update(self, src=None):
+        """Hook: copies a store derives from the fp32 buffer itself, not from p16 (ParamStore's 8-bit expert weights).  `src`: the flat fp32
+        buffer the working copies were just cast from - None: the master; load_ema() passes the average."""
+
+    # -- weight EMA ----------------------------------------------------------------------------------------------------------------------
+    def enable_ema(self):
+        """Keep an average of the master from here on: `e32` is allocated on the first call, and every call sets it to the master as it is
+        now with no update counted (so a call after a checkpoint was loaded drops whatever the average held before)."""
+        if self.ema_loaded:
+            raise RuntimeError("FlatArena.enable_ema: the working copies hold the average (restore_master() first)")
+        if self.e32 is None:
+            self.e32 = torch.zeros(self.numel, device=self.device, dtype=torch.float32)
+        self.e32.copy_(self.p32)
+        self.ema_updates = 0
+
+    def load_ema(self):
+        """The working copies (p16, p16t, the store's derived copies) from the average instead of the master, and f32() hands out views of
+        the average: the forward passes then run on the averaged weights.  The master, the gradient and Adam's state are not touched;
+        restore_master() undoes it.  Views of f32() taken BEFORE the call stay views of the master: whoever keeps some asks again."""
+        if self.e32 is None:
+            raise RuntimeError("FlatArena.load_ema: this arena keeps no average (enable_ema())")
+        ops.call("cast_bf16", self.e32, self.p16, self.numel)
+        self._derive(self.e32)
+        self.ema_loaded = True
+
+    def restore_master(self):
+        """The working copies from the master again (refresh())."""
+        self.ema_loaded = False                                     # first: the hook's f32() views are the master's again
+        self.refresh()
 
     # -- bf16 gradient exchange ----------------------------------------------------------------------------------------------------------
     @property
@@ -203,26 +252,41 @@ class FlatArena:
         self.runs = self._run_table = None
 
     def adam_step(self, normsq_total: torch.Tensor, lr: float, weight_decay: float, clip: float, grad_scale: float = 1.0, *,
-                  betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, decoupled: bool = False):
+                  betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, decoupled: bool = False, ema_decay: float = 0.0,
+                  ema_warmup: bool = False):
         """clip (against `normsq_total`, the squared norm over ALL arenas of the model, as clip_grad_norm_ over all parameters computes it)
         + torch.optim.Adam's update (L2 weight decay; decoupled: torch.optim.AdamW's) on the fp32 master, the bf16 copy written by the same
         kernel; the derived copies follow.  Without parameter groups, with Adam's default betas / eps and L2 decay this is medmoe_adam_step;
         anything else is ONE medmoe_adam_groups_step over the arena's run table (a single run when no groups are set).  Gradients must be
         in THIS arena's g32 (no new_grad_arena() since the backward) - or, after a bf16 gradient exchange (`g16_reduced`), in g16: the
-        same two launches in their _g16 form read it as bf16, and the flag is cleared with the step."""
+        same two launches in their _g16 form read it as bf16, and the flag is cleared with the step.
+        ema_decay > 0 (enable_ema() first): the `_ema` form of whichever launch this would have been - the same update, and
+        e32 <- e32 + (1 - d_t) (p32_new - e32) by the lane that holds the new parameter, d_t = ema.ema_decay_at(ema_updates, ema_decay,
+        ema_warmup); 1 - d_t is a by-value launch argument."""
+        if self.ema_loaded:
+            raise RuntimeError("FlatArena.adam_step: the working copies hold the average (restore_master() first)")
+        ema_args = ()
+        if float(ema_decay) > 0.0:
+            if self.e32 is None:
+                raise RuntimeError("FlatArena.adam_step(ema_decay > 0): this arena keeps no average (enable_ema())")
+            ema_args = (self.e32, one_minus_decay(self.ema_updates, ema_decay, ema_warmup))
         m, v = self.adam_state()
         self.step_count += 1
         b1, b2 = float(betas[0]), float(betas[1])
         g, sfx = (self.g16, "_g16") if self.g16_reduced else (self.g32, "")
+        if ema_args:
+            sfx = "_ema" + sfx
         if self.runs is None and not decoupled and (b1, b2) == (0.9, 0.999) and float(eps) == 1e-8:
             ops.call("adam_step" + sfx, self.p32, g, m, v, self.p16, self.numel, lr, 0.9, 0.999, 1e-8, weight_decay, self.step_count,
-                     normsq_total, clip, grad_scale)
+                     normsq_total, clip, grad_scale, *ema_args)
         else:
             if self.runs is None and self._one_run is None:
                 self._one_run = self._upload_runs([(self.numel, 1.0, 1.0)])
             ends, lrm, wdm = self._run_table if self.runs is not None else self._one_run
             ops.call("adam_groups_step" + sfx, self.p32, g, m, v, self.p16, self.numel, ends, lrm, wdm, ends.numel(), lr, b1, b2, eps,
-                     weight_decay, 1 if decoupled else 0, self.step_count, normsq_total, clip, grad_scale)
+                     weight_decay, 1 if decoupled else 0, self.step_count, normsq_total, clip, grad_scale, *ema_args)
+        if ema_args:
+            self.ema_updates += 1
         self.g16_reduced = False
         self._derive()
 

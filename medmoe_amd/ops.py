@@ -666,6 +666,9 @@ _SIGS = {
     "text_embed_ln_bwd_packed": "pppppppppppiiiifpp",
     "lora_fwd_rows": "pppppiiiiiiifllllfp", "lora_bwd_dx_rows": "pippppiiiiiifllllfp", "lora_bwd_wgrad_rows": "pippppppliiiiiifllllfp",
     "grad_pack_bf16": "pplf", "sumsq_det_bf16": "plpp", "adam_step_g16": "pppppldddddipff", "adam_groups_step_g16": "ppppplpppidddddiipff",
+    # the four optimiser steps with the weight EMA: their sibling's arguments + (ema, one_minus_decay)
+    "adam_step_ema": "pppppldddddipffpf", "adam_groups_step_ema": "ppppplpppidddddiipffpf",
+    "adam_step_ema_g16": "pppppldddddipffpf", "adam_groups_step_ema_g16": "ppppplpppidddddiipffpf",
 }
 
 
@@ -743,6 +746,10 @@ _COSTS = {
     "adam_groups_step": lambda a: ("adam_groups_kernel", 34.0 * a[5], "byte"),                     # the same traffic: the run table stays on chip
     "adam_step_g16": lambda a: ("adam_kernel<bf16>", 32.0 * a[5], "byte"),                           # the gradient read as bf16: 2 B/param less
     "adam_groups_step_g16": lambda a: ("adam_groups_kernel<LDS, bf16>", 32.0 * a[5], "byte"),
+    "adam_step_ema": lambda a: ("adam_kernel<float, EMA>", 42.0 * a[5], "byte"),                  # + the average read and written
+    "adam_groups_step_ema": lambda a: ("adam_groups_kernel<LDS, float, EMA>", 42.0 * a[5], "byte"),
+    "adam_step_ema_g16": lambda a: ("adam_kernel<bf16, EMA>", 40.0 * a[5], "byte"),
+    "adam_groups_step_ema_g16": lambda a: ("adam_groups_kernel<LDS, bf16, EMA>", 40.0 * a[5], "byte"),
     "grad_pack_bf16": lambda a: ("grad_pack_bf16_kernel", 6.0 * a[2], "byte"),                     # fp32 read, bf16 written
     "scale_attn_bwd": lambda a: ("scale_attn_bwd_kernel", 2.0 * a[17] * (4 * (2 * a[18] + 2 * a[19]) + 2 * a[18]), "byte"),    # G, dG, H1, dH1 x 4 scales + eout, d_img_l rows
     "scale_attn_bwd_det": lambda a: ("scale_attn_bwd_kernel<DET> + scale_attn_bwd_reduce_kernel", 2.0 * a[17] * (4 * (2 * a[18] + 2 * a[19]) + 2 * a[18]), "byte"),

@@ -123,19 +123,21 @@ class ParamStore(FlatArena):
             return w
         return torch.cat([w, w.new_zeros(c.d_v, c.patch_dim_pad - c.patch_dim)], 1)
 
-    def after_update(self):
-        self.requantise_experts()
+    def after_update(self, src=None):
+        self.requantise_experts(src)
 
-    def requantise_experts(self):
-        """The 8-bit expert copies from the fp32 master (after every refresh() / adam_step(): FlatArena's hook)."""
+    def requantise_experts(self, src=None):
+        """The 8-bit expert copies from the fp32 master (after every refresh() / adam_step(): FlatArena's hook) - or from `src`, the flat fp32
+        buffer of this layout the working copies were just cast from (load_ema(): the average)."""
         for name, copies in self.fp8.items():
             Eg, N, K = self.shapes[name]
+            w = self.f32(name) if src is None else self.view(src, name)
             if self.cfg.expert_mx:
                 q, sq, qT, sT = copies
-                ops.call("quant_weights_mx", self.f32(name), q, sq, qT, sT, Eg, N, K)
+                ops.call("quant_weights_mx", w, q, sq, qT, sT, Eg, N, K)
             else:
                 q, qT, s = copies
-                ops.call("quant_weights_e4m3", self.f32(name), q, qT, s, Eg, N, K)
+                ops.call("quant_weights_e4m3", w, q, qT, s, Eg, N, K)
 
     def q8(self, name): return self.fp8[name][0]
     def q8t(self, name): return self.fp8[name][1]

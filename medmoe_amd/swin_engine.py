@@ -23,6 +23,7 @@ from typing import Dict, Optional
 
 import torch
 
+from . import ema as ema_
 from . import ops
 from .engine import Engine
 from .local_generic import GenericLocalLoss
@@ -183,11 +184,28 @@ class SwinEngine:
         if self.train_text:
             self._normsq.add_(self.eng.text_arena().sumsq())
         kw = dict(betas=tuple(c.adam_betas), eps=c.adam_eps, decoupled=c.optimizer == "adamw")
+        if c.ema_decay > 0.0:                                       # weight EMA: every store's launch in its _ema form
+            ema_.prepare(self.optimizer_stores().values())
+            kw.update(ema_.step_kwargs(c))
         st_t.adam_step(self._normsq, lr, c.weight_decay, c.clip, **kw)
         st_m.adam_step(self._normsq, lr, c.weight_decay, c.clip, **kw)
         if self.train_text:
             self.eng.text_arena().adam_step(self._normsq, lr, c.weight_decay, c.clip, **kw)
         self.enc.tower.refresh(cast=False)                          # patch-embedding pad form, bias tables
+
+    def ema_weights(self):
+        """The Swin model keeps, checkpoints and exports its weight averages (optimizer_step, `ema_params`), but evaluating on them is not
+        built: the encoder's modules hold fp32 views of the masters, and the Lightning module validates this model through torch modules."""
+        raise NotImplementedError("ema_weights with the Swin-T encoder (vision.arch = swin_t, SwinEngine): evaluation on the averaged weights "
+                                  "is a named follow-up (DESIGN 3k); the averages are maintained, checkpointed and exportable (ema_params)")
+
+    def ema_params(self) -> Dict[str, Dict[str, torch.Tensor]]:
+        """store kind -> (the store's own names -> fp32 average, CPU), for export."""
+        if not self.cfg.ema_decay > 0.0:
+            raise RuntimeError("ema_params: this engine keeps no average - cfg.ema_decay is 0 (model.ema.decay)")
+        stores = self.optimizer_stores()
+        ema_.prepare(stores.values())
+        return {kind: {n: st.view(st.e32, n).detach().cpu().clone() for n in st.offsets if n not in st.groups} for kind, st in stores.items()}
 
     def eval_step(self, batch: Dict[str, torch.Tensor]):
         """Forward + losses without gradients reaching the parameters (validation): the same launch sequence minus the encoder backward."""

@@ -177,6 +177,30 @@ class MedMoE(nn.Module):
                 state_dict[prefix + "text_encoder." + n + ".weight"] = lo.true_view(lo.p32, n)
         return state_dict
 
+    def ema_state_dict(self) -> Dict[str, torch.Tensor]:
+        """state_dict() with the weights the fused step trains replaced by their fp32 averages (cfg.ema_decay > 0), under the
+        same reference keys: `image_encoder.*` from the image arena's average, `text_encoder.*` from the trainable text tower's or the
+        adapters'.  Clones: the dict stays what it was when the training goes on."""
+        from medmoe_amd import ema as ema_
+        eng = self.engine
+        if not eng.cfg.ema_decay > 0.0:
+            raise RuntimeError("ema_state_dict: cfg.ema_decay is 0 (model.ema.decay) - this model keeps no average")
+        if self.swin is not None:
+            raise NotImplementedError("ema_state_dict with vision.arch = swin_t: the Swin stores' averages are exported under the stores' own "
+                                      "names (SwinEngine.ema_params); the mapping to the module's keys is a named follow-up (DESIGN 3k)")
+        ema_.prepare(eng.optimizer_stores().values())
+        out = {k: v.detach().clone() for k, v in self.state_dict().items()}
+        p = eng.params
+        for k, v in p.named_views(p.e32).items():
+            out["image_encoder." + k] = v.detach().clone()
+        if eng.tstore is not None:
+            for n in eng.tstore.shapes:
+                out["text_encoder." + n] = eng.tstore.view(eng.tstore.e32, n).detach().clone()
+        if eng.lora is not None:
+            for n in eng.lora.true_names():
+                out["text_encoder." + n + ".weight"] = eng.lora.true_view(eng.lora.e32, n).detach().clone()
+        return out
+
     def _from_reference_keys(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
         ie, te = prefix + "image_encoder.", prefix + "text_encoder."
         named = {k[len(ie):]: state_dict.pop(k) for k in [k for k in state_dict if k.startswith(ie)]}

@@ -23,7 +23,7 @@ def _get(cfg: Any, key: str, default=None):
 class MedMoEPretrainingLightningModule(_Base):
     def __init__(self, model: nn.Module, loss: Any, optimizer: Any = None, scheduler: Any = None,
                  compile: bool = False, num_classes: int = 5, fused_step: bool = False, optimizer_groups: Any = None,
-                 grad_comm_dtype: str = "fp32"):
+                 grad_comm_dtype: str = "fp32", ema: Any = None):
         """`fused_step` (MI355X build, `model.fused_step` in the config tree): training steps run `Engine.train_step` - the hand-scheduled
         forward / losses / backward with the embedding all-gather, the reduce-scatter of the gathered-key gradients, the per-layer
         gradient all-reduce overlapped with backward and the fused clip + Adam - instead of torch autograd + a torch optimizer.
@@ -33,7 +33,11 @@ class MedMoEPretrainingLightningModule(_Base):
         text_lr_mult, layer_decay - that cuts the engine's flat stores into parameter groups; the scheduler keeps driving the base
         learning rate, the groups multiply it.
         `grad_comm_dtype` (`model.grad_comm_dtype`, fused step only): "fp32" or "bf16" - the number format of the data-parallel gradient
-        all-reduces (MedMoEConfig.grad_comm_dtype); a single process ignores it."""
+        all-reduces (MedMoEConfig.grad_comm_dtype); a single process ignores it.
+        `ema` (`+model.ema.decay=0.9999 +model.ema.warmup=true +model.ema.validate=true`, fused step only): an exponential moving average
+        of every trained weight, kept in fp32 next to the master and updated inside the fused Adam launch (MedMoEConfig.ema_decay /
+        ema_warmup); `validate`: validation_step / test_step evaluate on the average.  It travels with the checkpoint
+        (`fused_ema`) and `ema_state_dict()` exports it under the reference's key names."""
         super().__init__()
         self.model = model
         self.loss_cfg = loss
@@ -56,6 +60,19 @@ class MedMoEPretrainingLightningModule(_Base):
         if self._grad_comm_dtype != "fp32" and not self.fused_step:
             raise NotImplementedError("grad_comm_dtype needs fused_step=true: the bf16 exchange packs the engine's flat gradient arenas, the "
                                       "autograd path all-reduces torch's own .grad tensors in fp32")
+        unknown = set(dict(ema).keys()) - {"decay", "warmup", "validate"} if ema else set()
+        if unknown:
+            raise KeyError(f"model.ema: unknown keys {sorted(unknown)} (decay, warmup, validate)")
+        self._ema_decay = float(_get(ema, "decay", 0.0)) if ema else 0.0
+        self._ema_warmup = bool(_get(ema, "warmup", False)) if ema else False
+        self._ema_validate = bool(_get(ema, "validate", False)) if ema else False
+        if not 0.0 <= self._ema_decay < 1.0:
+            raise ValueError(f"model.ema.decay must be in [0, 1) (0 = off), got {self._ema_decay}")
+        if self._ema_decay > 0.0 and not self.fused_step:
+            raise NotImplementedError("model.ema.decay > 0 needs fused_step=true (model.fused_step=true): the average is kept in the engine's "
+                                      "flat stores and updated inside the fused Adam launch; the autograd path steps a torch optimizer")
+        if self._ema_validate and not self._ema_decay > 0.0:
+            raise ValueError("model.ema.validate=true needs model.ema.decay > 0: there is no average to validate on")
         if self.fused_step:
             self.automatic_optimization = False                                  # Lightning: manual optimisation (the engine steps itself)
             self._configure_engine()
@@ -149,10 +166,19 @@ class MedMoEPretrainingLightningModule(_Base):
         c.adam_betas = tuple(float(b) for b in opt.keywords.get("betas", (0.9, 0.999)))
         c.adam_eps = float(opt.keywords.get("eps", 1e-8))
         c.grad_comm_dtype = self._grad_comm_dtype
+        c.ema_decay, c.ema_warmup = self._ema_decay, self._ema_warmup
+        c.validate()
+        if self._ema_validate and getattr(self.model, "swin", None) is not None:
+            raise NotImplementedError("model.ema.validate=true with vision.arch = swin_t: this model validates through its torch modules, "
+                                      "which read the masters - evaluation on the averaged weights is a named follow-up (DESIGN 3k); the "
+                                      "average itself is maintained, checkpointed and exportable")
         from medmoe_amd.optim_groups import set_rules
         set_rules(c, self._optimizer_groups)                         # validates the rule set and the optimiser keys above
         if getattr(self.model, "swin", None) is None:                # arch = swin_t: the SwinEngine groups its own arenas when it is built
             eng.apply_optimizer_groups()
+            if c.ema_decay > 0.0:                                    # (and its stores start their averages at the first step)
+                from medmoe_amd import ema as ema_
+                ema_.prepare(eng.optimizer_stores().values())
 
     def set_deterministic(self, flag: bool):
         """trainer.deterministic: hand the flag to the HIP engine behind self.model (medmoe_amd.Engine.set_deterministic - every launch of
@@ -219,14 +245,16 @@ class MedMoEPretrainingLightningModule(_Base):
 
     def fused_eval_step(self, batch: Dict[str, Any]):
         """One batch through Engine.eval_step - the losses of `fused_training_step` forward only, nothing of the model or the optimiser
-        state written; returns the reference's loss names (device scalars).  With vision.arch = swin_t the batch takes the `model_step`
+        state written; returns the reference's loss names (device scalars); with model.ema.validate on the averaged weights
+        (eval_step(ema=True)).  With vision.arch = swin_t the batch takes the `model_step`
         route under no_grad: a SwinEngine.eval_step is a separate piece of work."""
         if not self.fused_step:
             raise RuntimeError("fused_eval_step: construct the module with fused_step=True (model.fused_step=true)")
         if getattr(self.model, "swin", None) is not None:
             with torch.no_grad():
                 return self.model_step(batch)
-        out = self._fused_engine().eval_step(self._engine_batch(batch))
+        eng, eb = self._fused_engine(), self._engine_batch(batch)
+        out = eng.eval_step(eb, ema=True) if self._ema_validate else eng.eval_step(eb)
         return {"loss": out["loss"], "l_loss": out["l_loss"], "g_loss": out["g_loss"], "classifier_loss": out["classifier_loss"],
                 "classifier_acc": out["classifier_acc"]}
 
@@ -268,17 +296,22 @@ class MedMoEPretrainingLightningModule(_Base):
             state[name] = {"step": int(st.step_count), "numel": int(m.numel()), "exp_avg": m.detach().cpu().clone(),
                            "exp_avg_sq": v.detach().cpu().clone()}
         checkpoint["fused_adam"] = state
+        # the weight averages (model.ema): per store that keeps one, the flat fp32 average in the store's layout + the number of
+        # updates it has seen.  One that has seen none is the master by definition (medmoe_amd.ema.prepare): saved as such
+        averaged = {name: st for name, st in self._fused_stores().items() if getattr(st, "e32", None) is not None}
+        if averaged:
+            checkpoint["fused_ema"] = {name: {"updates": int(st.ema_updates), "numel": int(st.e32.numel()),
+                                              "ema": (st.e32 if st.ema_updates else st.p32).detach().cpu().clone()} for name, st in averaged.items()}
         # the text tower's dropout masks are a function of (seed, step, site, element): the step counter resumes where it stopped
         checkpoint["text_dropout_step"] = int(self.model.engine.dropout_step)
 
     def on_load_checkpoint(self, checkpoint: Dict[str, Any]) -> None:
         if self.fused_step and "text_dropout_step" in checkpoint:
             self.model.engine.dropout_step = int(checkpoint["text_dropout_step"])
-        state = checkpoint.get("fused_adam") if self.fused_step else None
-        if not state:
+        if not self.fused_step:
             return
         stores = self._fused_stores()
-        for name, rec in state.items():
+        for name, rec in (checkpoint.get("fused_adam") or {}).items():
             if name not in stores:
                 raise KeyError(f"checkpoint holds fused Adam state for {name!r}; this module has {sorted(stores)}")
             st = stores[name]
@@ -287,6 +320,31 @@ class MedMoEPretrainingLightningModule(_Base):
                 raise ValueError(f"fused Adam state {name!r}: {rec['numel']} elements in the checkpoint, {m.numel()} in this model")
             m.copy_(rec["exp_avg"]); v.copy_(rec["exp_avg_sq"])
             st.step_count = int(rec["step"])
+        if getattr(self, "_ema_decay", 0.0) > 0.0:                   # a module without the key ignores a checkpoint's averages
+            self._load_fused_ema(checkpoint.get("fused_ema") or {}, stores)
+
+    def _load_fused_ema(self, state: Dict[str, Any], stores: Dict[str, Any]) -> None:
+        """The averages of a checkpoint into the stores.  A store the checkpoint holds no average for (one written with EMA off) starts
+        again from its master - the one the checkpoint's state dict has just loaded - with no update counted."""
+        for name in state:
+            if name not in stores:
+                raise KeyError(f"checkpoint holds a weight average for {name!r}; this module has {sorted(stores)}")
+        for name, st in stores.items():
+            st.enable_ema()
+            rec = state.get(name)
+            if rec is None:
+                continue
+            if int(rec["numel"]) != st.e32.numel():
+                raise ValueError(f"fused weight average {name!r}: {rec['numel']} elements in the checkpoint, {st.e32.numel()} in this model")
+            st.e32.copy_(rec["ema"])
+            st.ema_updates = int(rec["updates"])
+
+    def ema_state_dict(self) -> Dict[str, torch.Tensor]:
+        """`self.model.state_dict()` with every trained weight replaced by its average: the reference's key names, through the key mapping
+        of the model's own state-dict hook (MedMoE.ema_state_dict)."""
+        if not self._ema_decay > 0.0:
+            raise RuntimeError("ema_state_dict: model.ema.decay is 0 - this module keeps no average")
+        return self.model.ema_state_dict()
 
     def configure_optimizers(self):                                                      # :148-169
         opt = self._optimizer(params=self.parameters())
