@@ -9,6 +9,7 @@ encode_text / encode_image -> SWIN.forward (swin.py:130-149) -> MoE.forward (swi
 model_step (medmoe_module.py:284-316) -> GLORIA local/global losses (losses.py:757-794,
 954-1026) + CE on router probabilities (medmoe_module.py:235-237).
 """
+import collections
 import contextlib
 import os
 from typing import Dict, Optional
@@ -82,27 +83,48 @@ class VocabTables:
 
 
 class _TextRows:
-    """The launches of a TRAINABLE text pass that depend on the row layout, for `_forward_text_train`, `backward_text` and `_backward_text_lora`
-    (one copy of the layer loops for both layouts).  padded: all B x T rows, key-masked attention - exactly the launches those functions made
-    before this class existed.  packed: `text_pack` runs here; every launch then takes the device-side row count `cnt` (the first
-    `cnt` rows of the same buffers hold the non-padding tokens in (caption, position) order), attention the sequence offsets, the weight
-    gradients one row range [0, cnt] - nothing is copied to the host."""
+    """One text pass: the launches that depend on its row layout, and what the pass leaves for whoever runs after it.  Every pass builds one -
+    the frozen tower's, a trainable tower's, the frozen-style pass of forward_text(embedded=...) - and the block loops (`Engine._text_blocks`,
+    `Engine.backward_text`) are written once against it.
+    padded: all B x T rows, key-masked attention.  packed (only up to B <= 1024 and T <= 80, else the pass is padded): `text_pack`
+    runs here; every launch then takes the device-side row count `cnt` (the first `cnt` rows of the same buffers hold the non-padding tokens
+    in (caption, position) order), attention the sequence offsets, the weight gradients one row range [0, cnt] - nothing is copied to the host.
+    Left by the pass: `last` (the last hidden state; with `seq_off` what text_soft_target reads), and for `backward_text`, which takes the same
+    launches under the same masks: `ids32` / `tt32` / `km`, `seg` (the segment map the aggregation consumed), `first_sel` (the first summed
+    hidden state), `drop_step` / `lora_drop_step` (the step whose hidden + attention / LoRA dropout masks the pass applied; None: none)."""
 
-    def __init__(self, eng, km: torch.Tensor, packed: bool):
+    def __init__(self, eng, km: torch.Tensor, packed: bool, trainable: bool):
         c = eng.cfg
-        self.packed, self.km = packed, km
+        self.cfg, self.km = c, km
+        self.packed = packed = packed and eng.B <= 1024 and c.max_len <= 80
         self.B, self.T, self.H, self.Dt, self.eps = eng.B, c.max_len, c.n_head_t, c.d_t, c.eps_t
         self.tok_row = self.src_row = self.seq_off = self.row_off = self.cnt = None
+        self.ids32 = self.tt32 = self.seg = self.first_sel = self.last = self.drop_step = self.lora_drop_step = None
         if packed:
+            # ws["tpack"]: tok_row | src_of_row | seq_off | the frozen pass' count | 0 | a trainable pass' count
             pk, Mt, B = eng.ws["tpack"], eng.B * c.max_len, eng.B
             self.tok_row, self.src_row, self.seq_off = pk[:Mt], pk[Mt:2 * Mt], pk[2 * Mt:2 * Mt + B + 1]
-            self.row_off, self.cnt = pk[2 * Mt + B + 2:2 * Mt + B + 4], pk[2 * Mt + B + 3:2 * Mt + B + 4]      # [0, count] and its second element
+            if trainable:
+                self.row_off, self.cnt = pk[2 * Mt + B + 2:2 * Mt + B + 4], pk[2 * Mt + B + 3:2 * Mt + B + 4]  # [0, count] and its second element
+            else:
+                self.cnt = pk[2 * Mt + B + 1:2 * Mt + B + 2]
             ops.call("text_pack", km, self.tok_row, self.src_row, self.seq_off, self.cnt, B, self.T)
+
+    def rng(self, site: int, p: float):
+        """The generator of a hidden / attention dropout site under this pass' masks; None: the site drops nothing."""
+        return ops.dropout_rng(self.cfg.dropout_seed, self.drop_step, site, p) if self.drop_step is not None and p > 0.0 else None
+
+    def lora_rng(self, l: int):
+        if self.lora_drop_step is None:
+            return None
+        return ops.dropout_rng(self.cfg.dropout_seed, self.lora_drop_step, 4 * l + ops.DROPOUT_SITE_LORA, self.cfg.text_lora_dropout)
 
     def gemm(self, a, w, out, **kw):
         return ops.gemm_nt_rows(a, w, out, self.cnt, **kw) if self.packed else ops.gemm_nt(a, w, out, **kw)
 
     def wgrad(self, g, x, dw, db=None):
+        if dw is None:             # no gradient target (a frozen base under LoRA adapters): no launch
+            return None
         if self.packed:            # the grouped form with ONE group: the row ranges are enumerated from row_off on the device, M bounds them
             return ops.gemm_tn(g, x, dw, db=db, row_off=self.row_off, n_groups=1, M=self.B * self.T)
         return ops.gemm_tn(g, x, dw, db=db)
@@ -115,15 +137,26 @@ class _TextRows:
     def ln_bwd(self, dy, x, mean, rstd, gamma, dx, dgamma=None, dbeta=None):
         return ops.layernorm_bwd(dy, x, mean, rstd, gamma, dx, dgamma, dbeta, rows_dev=self.cnt)
 
-    def attn(self, qkv, out, lse):
+    def attn(self, qkv, out, lse, rng=None):
+        """rng: the attention-probability dropout's generator (padded passes only: Engine.__init__ refuses it with the packed one)."""
+        if rng is not None:
+            return ops.attn_drop_fwd(qkv, out, lse, self.km, self.B, self.T, self.H, rng)
         if self.packed:
             return ops.call("attn_fwd_varlen", qkv, out, lse, self.seq_off, self.B, self.T, self.H, 64)
         return ops.attn_fwd(qkv, out, lse, self.km, self.B, self.T, self.H)
 
-    def attn_bwd(self, qkv, out, dout, lse, dqkv, delta):
+    def attn_bwd(self, qkv, out, dout, lse, dqkv, delta, rng=None):
+        if rng is not None:
+            return ops.attn_drop_bwd(qkv, out, dout, lse, self.km, dqkv, delta, self.B, self.T, self.H, rng)
         if self.packed:
             return ops.attn_bwd_varlen(qkv, out, dout, lse, self.seq_off, dqkv, delta, self.B, self.T, self.H)
         return ops.attn_bwd(qkv, out, dout, lse, self.km, dqkv, delta, self.B, self.T, self.H)
+
+
+# The buffers of one block of a forward pass (`Engine._text_blocks`): x -> qkv -> att (+ lse) -> x1 = x + out_proj -> r = LN1(x1) (st1) ->
+# h = GELU(FC1 r) (aux: the GELU derivative, kept for the backward, or None) -> x2 = r + FC2 h -> out = LN2(x2) (st2); lu: the adapters' U
+# (None: the pass takes no adapter launch)
+_TextBufs = collections.namedtuple("_TextBufs", "qkv att lse x1 st1 r h aux x2 st2 out lu")
 
 
 class Engine:
@@ -133,24 +166,20 @@ class Engine:
         # train_step and in backward_text only; the mask is a function of (cfg.dropout_seed, self.dropout_step, site, element)
         self.text_dropout = cfg.text_hidden_dropout > 0.0 or cfg.text_attn_dropout > 0.0
         self.dropout_step = 0                                        # one per train_step call, counted on the host; travels with the checkpoint
-        self._text_drop_step = None                                  # the step whose masks the last text pass applied (None: it applied none)
         if self.text_dropout and cfg.freeze_text and not cfg.text_lora:
             raise NotImplementedError("text_hidden_dropout / text_attn_dropout > 0 (model.model.text.hidden_dropout_prob / "
                                       "attention_probs_dropout_prob) with freeze_text=True (text.freeze_bert: true): dropout is built for the "
                                       "trainable tower's padded pass, not for the packed frozen one")
-        if self.text_dropout and os.environ.get("MEDMOE_GRAPH", "0") == "1":
-            raise NotImplementedError("text_hidden_dropout / text_attn_dropout > 0 (model.model.text.hidden_dropout_prob / "
-                                      "attention_probs_dropout_prob) with MEDMOE_GRAPH=1: the dropout step counter is a by-value launch "
-                                      "argument, a replayed graph would repeat one step's masks")
+        if self.text_dropout:
+            self._refuse_with_graph("text_hidden_dropout / text_attn_dropout", "model.model.text.hidden_dropout_prob / attention_probs_dropout_prob")
         # stochastic depth of the image tower (cfg.vit_drop_path).  train_step draws the per-sample scales of every site of the step
         # (ws["vit_dp"], [n_layer_v, 2, B] fp32: 0 | 1 / (1 - p_l); [:, 0] the attention branch, [:, 1] the feed-forward branch) and points
         # vit_drop_scales at them for its own forward and backward; None everywhere else: eval_step, forward_image outside a training step and the
         # exports never drop.  Tests (and callers that drive _vit_blocks / _vit_backward themselves) may assign a tensor of that shape: the layers
         # with p_l > 0 then take the scaled launches with exactly these values, until it is set back to None.
         self.vit_drop_scales: Optional[torch.Tensor] = None
-        if cfg.vit_drop_path > 0.0 and os.environ.get("MEDMOE_GRAPH", "0") == "1":
-            raise NotImplementedError("vit_drop_path > 0 (model.model.vision.drop_path_rate) with MEDMOE_GRAPH=1: the dropout step counter is a "
-                                      "by-value launch argument, a replayed graph would repeat one step's masks")
+        if cfg.vit_drop_path > 0.0:
+            self._refuse_with_graph("vit_drop_path", "model.model.vision.drop_path_rate")
         if not torch.cuda.is_available():
             raise RuntimeError("medmoe_amd.Engine needs a GPU: the HIP path is the only path")
         self.cfg = cfg
@@ -189,15 +218,13 @@ class Engine:
         self.train_text = (not cfg.freeze_text) or self.text_lora
         self.tstore = None
         self.lora = None
-        self._lora_drop_step = None                                  # the step whose LoRA dropout mask the last text pass applied (None: none)
         self._base_t: Dict[str, tuple] = {}                          # LoRA: transposed bf16 copies of the frozen base's GEMM weights (dgrad operands)
         if self.train_text and cfg.soft_label:
             raise NotImplementedError("soft_label with a trainable text tower: the reference scores captions with a SEPARATE frozen BERT "
                                       "(medmoe_module.py:207-210); this build takes them from the tower itself, which must then stay frozen")
         if self.text_lora:
-            if cfg.text_lora_dropout > 0.0 and os.environ.get("MEDMOE_GRAPH", "0") == "1":
-                raise NotImplementedError("text_lora_dropout > 0 (model.model.text.lora_dropout) with MEDMOE_GRAPH=1: the dropout step counter is a "
-                                          "by-value launch argument, a replayed graph would repeat one step's masks")
+            if cfg.text_lora_dropout > 0.0:
+                self._refuse_with_graph("text_lora_dropout", "model.model.text.lora_dropout")
             from .text_lora import LoraStore
             self.lora = LoraStore(cfg, self.device, seed)
             self.refresh_text_base()
@@ -216,10 +243,13 @@ class Engine:
         # the generic GEMM formulation (medmoe_amd/local_generic.py)
         self.text_varlen = os.environ.get("MEDMOE_TEXT_VARLEN", "1") != "0" and not self.train_text
         # the TRAINABLE tower's packed pass (cfg.text_train_varlen or MEDMOE_TEXT_TRAIN_VARLEN=1): forward, backward and eval_step on the
-        # non-padding tokens, under the frozen path's rule (B <= 1024 and T <= 80, else the padded pass); text_train_varlen_active: which one ran
+        # non-padding tokens, under the rule of every packed pass (_TextRows: else the padded pass); text_train_varlen_active: which one ran
         self.text_train_varlen = self.train_text and (bool(cfg.text_train_varlen) or os.environ.get("MEDMOE_TEXT_TRAIN_VARLEN", "0") == "1")
         self.text_train_varlen_active = False
-        self._tp = None                                              # _TextRows of the last trainable text pass: backward_text takes the same launches
+        # every text pass builds a _TextRows (its row layout, and what it leaves behind): _tp is the last TRAINABLE pass' - backward_text takes
+        # the same launches under the same masks, and a frozen-style pass in between (forward_text(embedded=...)) leaves it alone; _rows is
+        # the most recent pass' of either kind (text_soft_target)
+        self._tp = self._rows = None
         if self.text_train_varlen and cfg.text_attn_dropout > 0.0:
             raise NotImplementedError("text_train_varlen (MEDMOE_TEXT_TRAIN_VARLEN=1) with text_attn_dropout > 0: the attention-probability "
                                       "dropout kernels have no packed form yet (DESIGN 3i)")
@@ -253,6 +283,12 @@ class Engine:
         self.use_graph = os.environ.get("MEDMOE_GRAPH", "0") == "1"
         self._graph = None
 
+    @staticmethod
+    def _refuse_with_graph(keys: str, hydra_keys: str):
+        if os.environ.get("MEDMOE_GRAPH", "0") == "1":
+            raise NotImplementedError(f"{keys} > 0 ({hydra_keys}) with MEDMOE_GRAPH=1: the dropout step counter is a by-value launch "
+                                      "argument, a replayed graph would repeat one step's masks")
+
     def optimizer_stores(self) -> Dict[str, object]:
         """kind (medmoe_amd.optim_groups) -> the arenas this engine steps."""
         out = {"vit": self.params}
@@ -281,11 +317,6 @@ class Engine:
         if hit is None or hit[0] is not w:
             hit = self._base_t[name] = (w, w.t().contiguous())
         return hit[1]
-
-    def _lora_rng(self, l: int):
-        if self._lora_drop_step is None:
-            return None
-        return ops.dropout_rng(self.cfg.dropout_seed, self._lora_drop_step, 4 * l + ops.DROPOUT_SITE_LORA, self.cfg.text_lora_dropout)
 
     def merged_text_params(self) -> Dict[str, torch.Tensor]:
         """The frozen-tower parameter dict (names and dtypes of params.text) with the adapters merged into the fused projections:
@@ -637,287 +668,222 @@ class Engine:
         ops.call("mean_tokens", ws["img_l"], ws["img_g"], B, P, Do, 0, P)              # swin.py:112
 
     # ------------------------------------------------------------------------------------------
-    # text tower forward (frozen; transformer.py:116-130 post-norm; text_encoder.py:92-144)
+    # text tower (transformer.py:116-130 post-norm; text_encoder.py:92-144): ONE block loop per direction for every mode - frozen or trainable,
+    # padded or packed, with or without the dropouts and the LoRA adapters.  What a mode changes is data: the buffers (_TextBufs), the row
+    # layout and the dropout generators (_TextRows), the gradient targets and the adapters
     # ------------------------------------------------------------------------------------------
     def forward_text(self, ids: torch.Tensor, attn_mask: torch.Tensor, token_type: Optional[torch.Tensor] = None,
                      embedded: Optional[torch.Tensor] = None, training: bool = False):
-        """`training`: the pass of a training step - a trainable tower then applies its dropout (cfg.text_hidden_dropout / text_attn_dropout) with
+        """The frozen tower's pass: activations in the rotating scratch, nothing kept for a backward.  A trainable tower takes
+        `_forward_text_train` instead, unless `embedded` is given.
+        `training`: the pass of a training step - a trainable tower then applies its dropout (cfg.text_hidden_dropout / text_attn_dropout) with
         the masks of self.dropout_step; evaluation passes never do.
         `embedded` [B, T, d_t] bf16: use these rows as the encoder's input instead of the embedding front-end's output (the
         reference's TransformerEncoder fixture is fed to the post-norm blocks this way, tests/test_ref_fixtures_gpu.py)."""
-        c, ws, t = self.cfg, self.ws, self.params.text
+        c, ws = self.cfg, self.ws
         B, T = ids.shape
         if B != self.B or T != c.max_len:
             raise ValueError("forward_text: call forward_image first with the same batch; T must equal cfg.max_len")
-        if self.train_text and embedded is None:
-            return self._forward_text_train(ids, attn_mask, token_type, training)
-        Dt, H = c.d_t, c.n_head_t
+        if c.last_n_layers < 1 or c.last_n_layers > 4:
+            raise ValueError("last_n_layers must be in 1..4")
         ids32 = ids.to(I32).contiguous()
         tt32 = token_type.to(I32).contiguous() if token_type is not None else None
         km = attn_mask.to(torch.uint8).contiguous()
-        st = ws["tstat"]
-        L, last = c.n_layer_t, c.last_n_layers
-        if last < 1 or last > 4:
-            raise ValueError("last_n_layers must be in 1..4")
-        # hidden_states = [embedding output, layer 1 .. layer L]; the reference sums hidden_states[-last:]
-        # (text_encoder.py:97-103), which includes the embedding output when last > L
-        first_sel = max(0, L + 1 - last)
-        n_sel = L + 1 - first_sel
-        hs = []
-        x = ws["ths0"] if first_sel == 0 else ws["tx0"]
+        if self.train_text and embedded is None:
+            return self._forward_text_train(ids, ids32, tt32, km, training)
         # VARIABLE LENGTH: the tower runs on the tokens with attention mask 1 only (55 % of the B x T positions for captions of 8..77 words),
         # packed in (caption, position) order by a device-side scan - GEMM / LayerNorm row counts and the attention's sequence offsets stay
         # on the device, nothing is copied to the host.  Padding tokens never reach a result: they are masked keys and carry no word
         # (text_encoder.py:32-90).  MEDMOE_TEXT_VARLEN=0 computes all B x T positions as the reference does.
-        vl = self.text_varlen and B <= 1024 and T <= 80
-        if vl:
-            pk = ws["tpack"]
-            tok_row, src_row, seq_off, cnt = pk[:B * T], pk[B * T:2 * B * T], pk[2 * B * T:2 * B * T + B + 1], pk[2 * B * T + B + 1:2 * B * T + B + 2]
-            ops.call("text_pack", km, tok_row, src_row, seq_off, cnt, B, T)
-            ops.call("text_embed_ln_packed", ids32, tt32, t["word_embeddings"], t["position_embeddings"], t["token_type_embeddings"],
-                     t["emb_layernorm.weight"], t["emb_layernorm.bias"], x, B, T, Dt, c.vocab, c.eps_t, src_row, cnt)
-            if embedded is not None:       # packed rows of the given input (rows past the count are never read)
-                x[:B * T].copy_(embedded.reshape(B * T, Dt).to(BF).index_select(0, src_row.long()))
-            gemm = lambda a, w_, out, **kw: ops.gemm_nt_rows(a, w_, out, cnt, **kw)
-            ln = lambda xin, g_, b_, y: ops.call("layernorm_fwd_rows", xin, g_, b_, y, st[0], st[1], B * T, Dt, c.eps_t, 0, cnt)
-            attn = lambda: ops.call("attn_fwd_varlen", ws["tqkv"], ws["tatt"], ws["tlse"], seq_off, B, T, H, 64)
-        else:
-            ops.call("text_embed_ln", ids32, tt32, t["word_embeddings"], t["position_embeddings"], t["token_type_embeddings"],
-                     t["emb_layernorm.weight"], t["emb_layernorm.bias"], x, B, T, Dt, c.vocab, c.eps_t)
-            if embedded is not None:
-                x[:B * T].copy_(embedded.reshape(B * T, Dt).to(BF))
-            gemm = lambda a, w_, out, **kw: ops.gemm_nt(a, w_, out, **kw)
-            ln = lambda xin, g_, b_, y: ops.layernorm_fwd(xin, g_, b_, y, st[0], st[1], c.eps_t)
-            attn = lambda: ops.attn_fwd(ws["tqkv"], ws["tatt"], ws["tlse"], km, B, T, H)
-        if first_sel == 0:
-            hs.append(x)
-        for l in range(L):
-            b = f"layer.{l}."
-            gemm(x, t[b + "attention.input_proj.weight"], ws["tqkv"], bias=t[b + "attention.input_proj.bias"])
-            attn()
-            gemm(ws["tatt"], t[b + "attention.output_proj.weight"], ws["tx1"], bias=t[b + "attention.output_proj.bias"], residual=x)
-            ln(ws["tx1"], t[b + "attention_layernorm.weight"], t[b + "attention_layernorm.bias"], ws["tr"])
-            gemm(ws["tr"], t[b + "feedforward.model.0.weight"], ws["th"], bias=t[b + "feedforward.model.0.bias"], epi=ops.EPI_GELU)
-            gemm(ws["th"], t[b + "feedforward.model.2.weight"], ws["tx1"], bias=t[b + "feedforward.model.2.bias"], residual=ws["tr"])
+        rows = _TextRows(self, km, self.text_varlen, trainable=False)
+        # hidden_states = [embedding output, layer 1 .. layer L]; the reference sums hidden_states[-last:]
+        # (text_encoder.py:97-103), which includes the embedding output when last > L
+        first_sel = max(0, c.n_layer_t + 1 - c.last_n_layers)
+        x = ws["ths0"] if first_sel == 0 else ws["tx0"]
+        self._text_embed(rows, ids32, tt32, x)
+        if embedded is not None:           # packed: the rows of the given input in packed order (rows past the count are never read)
+            e = embedded.reshape(B * T, c.d_t).to(BF)
+            x[:B * T].copy_(e.index_select(0, rows.src_row.long()) if rows.packed else e)
+
+        def bufs(l, x):            # a summed state goes to its own buffer, any other layer's output ping-pongs between tx0 and tx2
             j = l + 1 - first_sel
             out = ws[f"ths{j}"] if j >= 0 else (ws["tx2"] if x is ws["tx0"] else ws["tx0"])
-            ln(ws["tx1"], t[b + "feedforward_layernorm.weight"], t[b + "feedforward_layernorm.bias"], out)
-            if j >= 0:
-                hs.append(out)
-            x = out
-        assert len(hs) == n_sel
-        self._text_last = (hs[-1], seq_off if vl else None)
-        if self._seg is None:
-            self.prefetch_cap_lens(ids)
-        seg = self._seg
-        self._seg = None
-        h = hs + [None] * (4 - len(hs))
-        if vl:
-            ops.call("text_aggregate_packed", h[0], h[1], h[2], h[3], len(hs), seg, tok_row, ws["words"], ws["words32"], ws["txt_g"], B, T, Dt)
-        else:
-            ops.call("text_aggregate", h[0], h[1], h[2], h[3], len(hs), seg, ws["words"], ws["words32"], ws["txt_g"], B, T, Dt)
+            return _TextBufs(ws["tqkv"], ws["tatt"], ws["tlse"], ws["tx1"], ws["tstat"], ws["tr"], ws["th"], None, ws["tx1"], ws["tstat"], out, None)
+        self._text_tail(rows, ids, self._text_blocks(rows, x, bufs))
 
-    def _drop_rng(self, site: int, p: float):
-        return ops.dropout_rng(self.cfg.dropout_seed, self._text_drop_step, site, p)
-
-    def _forward_text_train(self, ids, attn_mask, token_type, training: bool = False):
-        """The text pass of a TRAINABLE tower (cfg.freeze_text = False): all B x T positions (key-masked attention, as the reference computes
-        them, text_encoder.py:92-117), every layer's activations kept in the workspace for `backward_text`.  With text_train_varlen the same
-        launches run on the packed non-padding tokens (_TextRows; the first `count` rows of the same buffers).
+    def _forward_text_train(self, ids, ids32, tt32, km, training: bool = False):
+        """The text pass of a TRAINABLE tower (cfg.freeze_text = False, or LoRA adapters on a frozen base): all B x T positions (key-masked
+        attention, as the reference computes them, text_encoder.py:92-117) or, with text_train_varlen, the packed non-padding tokens (the
+        first `count` rows of the same buffers); every layer's activations are kept in the workspace, and the pass' _TextRows in self._tp,
+        for `backward_text`.
         `training` with a dropout probability > 0: BertModel's four train-mode dropouts - after the embedding LayerNorm, on the attention
         probabilities (medmoe_attn_drop_fwd), after the output projection and after FC2 (each fused with the residual add and the LayerNorm
         that follow: medmoe_dropout_add_layernorm_fwd on the GEMM's output without residual).  No mask is stored: `backward_text`
         regenerates them from (cfg.dropout_seed, the step, the site)."""
-        c, ws, t = self.cfg, self.ws, self.params.text
-        B, T = ids.shape
-        Dt, H, L, last = c.d_t, c.n_head_t, c.n_layer_t, c.last_n_layers
-        if last < 1 or last > 4:
-            raise ValueError("last_n_layers must be in 1..4")
-        ids32 = ids.to(I32).contiguous()
-        tt32 = token_type.to(I32).contiguous() if token_type is not None else None
-        km = attn_mask.to(torch.uint8).contiguous()
-        self._tt_state = (ids32, tt32, km)
-        drop = training and self.text_dropout
-        self._text_drop_step = self.dropout_step if drop else None
-        lo = self.lora
-        self._lora_drop_step = self.dropout_step if (training and lo is not None and c.text_lora_dropout > 0.0) else None
-        ph, pa = (c.text_hidden_dropout, c.text_attn_dropout) if drop else (0.0, 0.0)
+        c, ws, lo = self.cfg, self.ws, self.lora
+        rows = _TextRows(self, km, self.text_train_varlen, trainable=True)
+        rows.ids32, rows.tt32 = ids32, tt32
+        rows.drop_step = self.dropout_step if training and self.text_dropout else None
+        rows.lora_drop_step = self.dropout_step if training and lo is not None and c.text_lora_dropout > 0.0 else None
+        self.text_train_varlen_active = rows.packed
         x = ws["t_x0"]
-        tp = self._tp = _TextRows(self, km, self.text_train_varlen and B <= 1024 and T <= 80)
-        self.text_train_varlen_active = tp.packed
-        if tp.packed:
-            ops.call("text_embed_ln_packed", ids32, tt32, t["word_embeddings"], t["position_embeddings"], t["token_type_embeddings"],
-                     t["emb_layernorm.weight"], t["emb_layernorm.bias"], x, B, T, Dt, c.vocab, c.eps_t, tp.src_row, tp.cnt)
+        self._text_embed(rows, ids32, tt32, x)
+        rng = rows.rng(ops.DROPOUT_SITE_EMBED, c.text_hidden_dropout)
+        if rng is not None:
+            ops.dropout_apply(x, x, rng)
+
+        def bufs(l, x):
+            return _TextBufs(ws[f"t_qkv{l}"], ws[f"t_att{l}"], ws[f"t_lse{l}"], ws[f"t_x1{l}"], ws[f"t_st1{l}"], ws[f"t_r{l}"], ws[f"t_h{l}"],
+                             ws[f"t_dg{l}"], ws[f"t_x2{l}"], ws[f"t_st2{l}"], ws[f"t_x{l + 1}"], ws[f"t_lu{l}"] if lo is not None else None)
+        self._tp = rows
+        self._text_tail(rows, ids, self._text_blocks(rows, x, bufs))
+
+    def _text_embed(self, rows, ids32, tt32, x):
+        """x = LayerNorm(word + position + token-type embeddings), on all B x T rows or packed."""
+        c, t = self.cfg, self.params.text
+        a = (ids32, tt32, t["word_embeddings"], t["position_embeddings"], t["token_type_embeddings"], t["emb_layernorm.weight"],
+             t["emb_layernorm.bias"], x, rows.B, rows.T, c.d_t, c.vocab, c.eps_t)
+        if rows.packed:
+            ops.call("text_embed_ln_packed", *a, rows.src_row, rows.cnt)
         else:
-            ops.call("text_embed_ln", ids32, tt32, t["word_embeddings"], t["position_embeddings"], t["token_type_embeddings"],
-                     t["emb_layernorm.weight"], t["emb_layernorm.bias"], x, B, T, Dt, c.vocab, c.eps_t)
-        if ph > 0.0:
-            ops.dropout_apply(x, x, self._drop_rng(ops.DROPOUT_SITE_EMBED, ph))
-        for l in range(L):
-            b = f"layer.{l}."
-            st1, st2 = ws[f"t_st1{l}"], ws[f"t_st2{l}"]
-            tp.gemm(x, t[b + "attention.input_proj.weight"], ws[f"t_qkv{l}"], bias=t[b + "attention.input_proj.bias"])
-            if lo is not None:     # qkv[:, target columns] += s (dropout(x) A^T) B^T, U kept for the backward: one launch
-                ops.lora_fwd(x, lo.A16(l), lo.B16(l), ws[f"t_lu{l}"], ws[f"t_qkv{l}"], lo.targets, lo.scale, self._lora_rng(l), rows_dev=tp.cnt)
-            if drop:
-                if pa > 0.0:
-                    ops.attn_drop_fwd(ws[f"t_qkv{l}"], ws[f"t_att{l}"], ws[f"t_lse{l}"], km, B, T, H, self._drop_rng(4 * l, pa))
-                else:
-                    tp.attn(ws[f"t_qkv{l}"], ws[f"t_att{l}"], ws[f"t_lse{l}"])
-                if ph > 0.0:
-                    tp.gemm(ws[f"t_att{l}"], t[b + "attention.output_proj.weight"], ws["t_z"], bias=t[b + "attention.output_proj.bias"])
-                    ops.dropout_add_layernorm_fwd(ws["t_z"], x, t[b + "attention_layernorm.weight"], t[b + "attention_layernorm.bias"],
-                                                  ws[f"t_x1{l}"], ws[f"t_r{l}"], st1[0], st1[1], c.eps_t, self._drop_rng(4 * l + 1, ph))
-                else:
-                    tp.gemm(ws[f"t_att{l}"], t[b + "attention.output_proj.weight"], ws[f"t_x1{l}"], bias=t[b + "attention.output_proj.bias"],
-                                residual=x)
-                    tp.ln(ws[f"t_x1{l}"], t[b + "attention_layernorm.weight"], t[b + "attention_layernorm.bias"], ws[f"t_r{l}"], st1)
-                tp.gemm(ws[f"t_r{l}"], t[b + "feedforward.model.0.weight"], ws[f"t_h{l}"], bias=t[b + "feedforward.model.0.bias"],
-                            aux=ws[f"t_dg{l}"], epi=ops.EPI_GELU_DAUX)
-                if ph > 0.0:
-                    tp.gemm(ws[f"t_h{l}"], t[b + "feedforward.model.2.weight"], ws["t_z"], bias=t[b + "feedforward.model.2.bias"])
-                    ops.dropout_add_layernorm_fwd(ws["t_z"], ws[f"t_r{l}"], t[b + "feedforward_layernorm.weight"], t[b + "feedforward_layernorm.bias"],
-                                                  ws[f"t_x2{l}"], ws[f"t_x{l + 1}"], st2[0], st2[1], c.eps_t, self._drop_rng(4 * l + 2, ph))
-                else:
-                    tp.gemm(ws[f"t_h{l}"], t[b + "feedforward.model.2.weight"], ws[f"t_x2{l}"], bias=t[b + "feedforward.model.2.bias"],
-                                residual=ws[f"t_r{l}"])
-                    tp.ln(ws[f"t_x2{l}"], t[b + "feedforward_layernorm.weight"], t[b + "feedforward_layernorm.bias"], ws[f"t_x{l + 1}"], st2)
-                x = ws[f"t_x{l + 1}"]
-                continue
-            tp.attn(ws[f"t_qkv{l}"], ws[f"t_att{l}"], ws[f"t_lse{l}"])
-            tp.gemm(ws[f"t_att{l}"], t[b + "attention.output_proj.weight"], ws[f"t_x1{l}"], bias=t[b + "attention.output_proj.bias"], residual=x)
-            tp.ln(ws[f"t_x1{l}"], t[b + "attention_layernorm.weight"], t[b + "attention_layernorm.bias"], ws[f"t_r{l}"], st1)
-            tp.gemm(ws[f"t_r{l}"], t[b + "feedforward.model.0.weight"], ws[f"t_h{l}"], bias=t[b + "feedforward.model.0.bias"],
-                        aux=ws[f"t_dg{l}"], epi=ops.EPI_GELU_DAUX)
-            tp.gemm(ws[f"t_h{l}"], t[b + "feedforward.model.2.weight"], ws[f"t_x2{l}"], bias=t[b + "feedforward.model.2.bias"], residual=ws[f"t_r{l}"])
-            tp.ln(ws[f"t_x2{l}"], t[b + "feedforward_layernorm.weight"], t[b + "feedforward_layernorm.bias"], ws[f"t_x{l + 1}"], st2)
-            x = ws[f"t_x{l + 1}"]
-        first_sel = max(0, L + 1 - last)                          # hidden_states[-last:] of [embedding output, layer 1 .. layer L]
-        hs = [ws[f"t_x{j}"] for j in range(first_sel, L + 1)]
-        self._text_first_sel = first_sel
-        self._text_last = (hs[-1], tp.seq_off)
+            ops.call("text_embed_ln", *a)
+
+    def _text_blocks(self, rows, x, bufs):
+        """THE forward loop over the L post-norm blocks, for every pass.  `rows`: the pass' layout and dropout steps; `bufs(l, x)`: the
+        _TextBufs of layer l, whose input is x.  Returns hidden_states = [x, layer 1's output, ..., layer L's]."""
+        c, t, lo = self.cfg, self.params.text, self.lora
+        ph, pa = c.text_hidden_dropout, c.text_attn_dropout
+        hidden = [x]
+        for l in range(c.n_layer_t):
+            b, k = f"layer.{l}.", bufs(l, x)
+            rows.gemm(x, t[b + "attention.input_proj.weight"], k.qkv, bias=t[b + "attention.input_proj.bias"])
+            if k.lu is not None:   # qkv[:, target columns] += s (dropout(x) A^T) B^T, U kept for the backward: one launch
+                ops.lora_fwd(x, lo.A16(l), lo.B16(l), k.lu, k.qkv, lo.targets, lo.scale, rows.lora_rng(l), rows_dev=rows.cnt)
+            rows.attn(k.qkv, k.att, k.lse, rows.rng(4 * l, pa))
+            self._text_res_ln(rows, k.att, b + "attention.output_proj", x, b + "attention_layernorm", k.x1, k.st1, k.r, rows.rng(4 * l + 1, ph))
+            rows.gemm(k.r, t[b + "feedforward.model.0.weight"], k.h, bias=t[b + "feedforward.model.0.bias"], aux=k.aux,
+                      epi=ops.EPI_GELU if k.aux is None else ops.EPI_GELU_DAUX)
+            self._text_res_ln(rows, k.h, b + "feedforward.model.2", k.r, b + "feedforward_layernorm", k.x2, k.st2, k.out, rows.rng(4 * l + 2, ph))
+            x = k.out
+            hidden.append(x)
+        return hidden
+
+    def _text_res_ln(self, rows, a, linear, res, norm, x1, st, y, rng):
+        """A residual + LayerNorm site (two per block): x1 = res + a W^T + b of Linear `linear`, y = LayerNorm `norm`(x1).  With a hidden
+        dropout generator: the GEMM's output without residual goes to t_z, and ONE launch drops, adds and normalises."""
+        t = self.params.text
+        w, bias, gamma, beta = t[linear + ".weight"], t[linear + ".bias"], t[norm + ".weight"], t[norm + ".bias"]
+        if rng is None:
+            rows.gemm(a, w, x1, bias=bias, residual=res)
+            rows.ln(x1, gamma, beta, y, st)
+        else:
+            rows.gemm(a, w, self.ws["t_z"], bias=bias)
+            ops.dropout_add_layernorm_fwd(self.ws["t_z"], res, gamma, beta, x1, y, st[0], st[1], self.cfg.eps_t, rng)
+
+    def _text_tail(self, rows, ids, hidden):
+        """The end of every text pass: hidden_states[-last_n_layers:] summed and aggregated to words (text_encoder.py:97-144) under the
+        prefetched segment map, which the pass consumes; `rows` keeps what text_soft_target and backward_text read."""
+        c, ws = self.cfg, self.ws
+        rows.first_sel = max(0, c.n_layer_t + 1 - c.last_n_layers)
+        hs = hidden[rows.first_sel:]
+        rows.last = hs[-1]
+        self._rows = rows
         if self._seg is None:
             self.prefetch_cap_lens(ids)
-        seg = self._seg
-        self._seg = None
-        self._seg_used = seg
+        rows.seg, self._seg = self._seg, None
         h = hs + [None] * (4 - len(hs))
-        if tp.packed:
-            ops.call("text_aggregate_packed", h[0], h[1], h[2], h[3], len(hs), seg, tp.tok_row, ws["words"], ws["words32"], ws["txt_g"], B, T, Dt)
+        out = (ws["words"], ws["words32"], ws["txt_g"], rows.B, rows.T, c.d_t)
+        if rows.packed:
+            ops.call("text_aggregate_packed", h[0], h[1], h[2], h[3], len(hs), rows.seg, rows.tok_row, *out)
         else:
-            ops.call("text_aggregate", h[0], h[1], h[2], h[3], len(hs), seg, ws["words"], ws["words32"], ws["txt_g"], B, T, Dt)
+            ops.call("text_aggregate", h[0], h[1], h[2], h[3], len(hs), rows.seg, *out)
 
     def backward_text(self, d_words: Optional[torch.Tensor], d_txt_g: Optional[torch.Tensor]):
         """Back-propagate d loss / d word embeddings (fp32 [B, T, D]) and d loss / d sentence embeddings (fp32 [B, D]) through the aggregation,
-        the post-norm blocks (transformer.py:116-130) and the embedding front-end into the text store's flat gradient buffer."""
-        if self.lora is not None:
-            return self._backward_text_lora(d_words, d_txt_g)
-        c, ws, ts, tp = self.cfg, self.ws, self.tstore, self._tp
-        B, T, Dt, H, L = self.B, c.max_len, c.d_t, c.n_head_t, c.n_layer_t
-        ids32, tt32, km = self._tt_state
-        w16t, grad, f32 = ts.w16t, ts.grad, ts.f32
+        the post-norm blocks (transformer.py:116-130) and the embedding front-end, under the layout and the masks of the last trainable pass
+        (self._tp).  THE backward loop over the blocks, for both trainable modes:
+        full tower: every parameter's gradient into the text store's flat gradient buffer - each weight-gradient GEMM ahead of the dgrad GEMM
+        of the same operand, the dgrad GEMMs on the store's transposed copies, the embedding backward at the end.
+        LoRA adapters on a frozen base: the same chain of dgrad GEMMs (on the base's transposed copies, `_base_wt`), LayerNorm and attention
+        backwards WITHOUT any base parameter gradient - the gradient targets are None, which skips the weight-gradient GEMMs and the
+        LayerNorm gamma / beta sums - and no embedding backward.  Per layer, after the attention backward has written d qkv:
+        medmoe_lora_bwd_dx (d U, and the adapters' term of d x added into the base dgrad GEMM's output) and medmoe_lora_bwd_wgrad (the
+        adapters' gradients, += into the arena).  At layer 0 nothing below trains: the dgrad GEMM and the d x term are both skipped.
+        LayerNorm gammas come from params.text in both modes: a trainable tower's entries ARE the store's fp32 views (TextStore.as_dict)."""
+        c, ws, ts, lo, t, tp = self.cfg, self.ws, self.tstore, self.lora, self.params.text, self._tp
+        B, T, Dt = self.B, c.max_len, c.d_t
+        grad = ts.grad if lo is None else (lambda name: None)
+        wt = ts.w16t if lo is None else self._base_wt
         dH = ws["t_dH"]
-        # the masks of the forward pass just run (None: it applied none): d z = keep * d x1 / (1 - p) feeds the two GEMMs of a hidden site, the
-        # residual branch takes d x1 unchanged
-        drop = self._text_drop_step is not None
-        ph, pa = (c.text_hidden_dropout, c.text_attn_dropout) if drop else (0.0, 0.0)
+        # the masks of the forward pass just run (tp.rng gives None where it applied none): d z = keep * d x1 / (1 - p) feeds the two GEMMs of
+        # a hidden site, the residual branch takes d x1 unchanged
+        ph, pa = c.text_hidden_dropout, c.text_attn_dropout
         if tp.packed:
-            ops.call("text_aggregate_bwd_packed", d_words, d_txt_g, self._seg_used, tp.src_row, tp.cnt, dH, B, T, Dt)
+            ops.call("text_aggregate_bwd_packed", d_words, d_txt_g, tp.seg, tp.src_row, tp.cnt, dH, B, T, Dt)
         else:
-            ops.call("text_aggregate_bwd", d_words, d_txt_g, self._seg_used, dH, B, T, Dt)
+            ops.call("text_aggregate_bwd", d_words, d_txt_g, tp.seg, dH, B, T, Dt)
         dy, d1, d2 = ws["t_da"], ws["t_db"], ws["t_dc"]
         dy.copy_(dH)                                                 # the last layer's output is always among the summed states
-        for l in range(L - 1, -1, -1):
+        for l in range(c.n_layer_t - 1, -1, -1):
             b = f"layer.{l}."
             st1, st2 = ws[f"t_st1{l}"], ws[f"t_st2{l}"]
+            below = lo is None or l > 0                              # something that trains reads this layer's input
             # y = LN2(x2), x2 = r + FC2(GELU(FC1(r)))
-            tp.ln_bwd(dy, ws[f"t_x2{l}"], st2[0], st2[1], f32(b + "feedforward_layernorm.weight"), d1,
-                              grad(b + "feedforward_layernorm.weight"), grad(b + "feedforward_layernorm.bias"))
-            dz = ops.dropout_apply(d1, ws["t_dzd"], self._drop_rng(4 * l + 2, ph)) if ph > 0.0 else d1
+            tp.ln_bwd(dy, ws[f"t_x2{l}"], st2[0], st2[1], t[b + "feedforward_layernorm.weight"], d1,
+                      grad(b + "feedforward_layernorm.weight"), grad(b + "feedforward_layernorm.bias"))
+            rng = tp.rng(4 * l + 2, ph)
+            dz = ops.dropout_apply(d1, ws["t_dzd"], rng) if rng is not None else d1
             tp.wgrad(dz, ws[f"t_h{l}"], grad(b + "feedforward.model.2.weight"), db=grad(b + "feedforward.model.2.bias"))
-            tp.gemm(dz, w16t(b + "feedforward.model.2.weight"), ws["t_dz"], aux=ws[f"t_dg{l}"], epi=ops.EPI_MUL_AUX)
+            tp.gemm(dz, wt(b + "feedforward.model.2.weight"), ws["t_dz"], aux=ws[f"t_dg{l}"], epi=ops.EPI_MUL_AUX)
             tp.wgrad(ws["t_dz"], ws[f"t_r{l}"], grad(b + "feedforward.model.0.weight"), db=grad(b + "feedforward.model.0.bias"))
-            tp.gemm(ws["t_dz"], w16t(b + "feedforward.model.0.weight"), d2, residual=d1)                  # d r = d x2 + dz W1
+            tp.gemm(ws["t_dz"], wt(b + "feedforward.model.0.weight"), d2, residual=d1)                    # d r = d x2 + dz W1
             # r = LN1(x1), x1 = x + out_proj(attention(qkv(x)))
-            tp.ln_bwd(d2, ws[f"t_x1{l}"], st1[0], st1[1], f32(b + "attention_layernorm.weight"), d1,
-                              grad(b + "attention_layernorm.weight"), grad(b + "attention_layernorm.bias"))
-            dz = ops.dropout_apply(d1, ws["t_dzd"], self._drop_rng(4 * l + 1, ph)) if ph > 0.0 else d1
+            tp.ln_bwd(d2, ws[f"t_x1{l}"], st1[0], st1[1], t[b + "attention_layernorm.weight"], d1,
+                      grad(b + "attention_layernorm.weight"), grad(b + "attention_layernorm.bias"))
+            rng = tp.rng(4 * l + 1, ph)
+            dz = ops.dropout_apply(d1, ws["t_dzd"], rng) if rng is not None else d1
             tp.wgrad(dz, ws[f"t_att{l}"], grad(b + "attention.output_proj.weight"), db=grad(b + "attention.output_proj.bias"))
-            tp.gemm(dz, w16t(b + "attention.output_proj.weight"), ws["t_datt"])
-            if pa > 0.0:
-                ops.attn_drop_bwd(ws[f"t_qkv{l}"], ws[f"t_att{l}"], ws["t_datt"], ws[f"t_lse{l}"], km, ws["t_dqkv"], ws["t_delta"], B, T, H,
-                                  self._drop_rng(4 * l, pa))
-            else:
-                tp.attn_bwd(ws[f"t_qkv{l}"], ws[f"t_att{l}"], ws["t_datt"], ws[f"t_lse{l}"], ws["t_dqkv"], ws["t_delta"])
+            tp.gemm(dz, wt(b + "attention.output_proj.weight"), ws["t_datt"])
+            tp.attn_bwd(ws[f"t_qkv{l}"], ws[f"t_att{l}"], ws["t_datt"], ws[f"t_lse{l}"], ws["t_dqkv"], ws["t_delta"], tp.rng(4 * l, pa))
             tp.wgrad(ws["t_dqkv"], ws[f"t_x{l}"], grad(b + "attention.input_proj.weight"), db=grad(b + "attention.input_proj.bias"))
-            tp.gemm(ws["t_dqkv"], w16t(b + "attention.input_proj.weight"), dy, residual=d1)               # d x = d x1 + dqkv Wqkv
-            if l >= self._text_first_sel:                          # hidden_states[l] is one of the summed states too
+            if below:
+                tp.gemm(ws["t_dqkv"], wt(b + "attention.input_proj.weight"), dy, residual=d1)             # d x = d x1 + dqkv Wqkv
+            if lo is not None:
+                rng = tp.lora_rng(l)
+                ops.lora_bwd_dx(ws["t_dqkv"], lo.B16t(l), lo.A16t(l), ws["t_ldu"], dy if below else None, lo.targets, lo.scale, rng, rows_dev=tp.cnt)
+                ops.lora_bwd_wgrad(ws["t_dqkv"], ws[f"t_x{l}"], ws[f"t_lu{l}"], ws["t_ldu"], lo.gA(l), lo.gB(l), ws["t_lsc"], lo.targets, lo.scale, rng,
+                                   rows_dev=tp.cnt)
+            if below and l >= tp.first_sel:                          # hidden_states[l] is one of the summed states too
                 dy.add_(dH)
-        if ph > 0.0:                                              # hidden_states[0] is the embedding output AFTER its dropout
-            ops.dropout_apply(dy, dy, self._drop_rng(ops.DROPOUT_SITE_EMBED, ph))
-        g_word = grad("word_embeddings")
+        if lo is None:
+            self._text_embed_backward(tp, dy)
+
+    def _text_embed_backward(self, tp, dy):
+        """d hidden_states[0] -> the gradients of the embedding LayerNorm and the three embedding tables (full tower only)."""
+        c, ws = self.cfg, self.ws
+        B, T, Dt = self.B, c.max_len, c.d_t
+        f32, grad = self.tstore.f32, self.tstore.grad
+        rng = tp.rng(ops.DROPOUT_SITE_EMBED, c.text_hidden_dropout)
+        if rng is not None:                                       # hidden_states[0] is the embedding output AFTER its dropout
+            ops.dropout_apply(dy, dy, rng)
+        a = (tp.ids32, tp.tt32, f32("word_embeddings"), f32("position_embeddings"), f32("token_type_embeddings"), f32("emb_layernorm.weight"), dy,
+             ws["t_dxemb"], grad("emb_layernorm.weight"), grad("emb_layernorm.bias"), grad("word_embeddings"), B, T, Dt, c.vocab, c.eps_t)
         if tp.packed:              # d x lands at the tokens' PADDED rows of the zeroed buffer: the position / token-type sums below stay as they are
             ws["t_dxemb"].zero_()
-            ops.call("text_embed_ln_bwd_packed", ids32, tt32, f32("word_embeddings"), f32("position_embeddings"), f32("token_type_embeddings"),
-                     f32("emb_layernorm.weight"), dy, ws["t_dxemb"], grad("emb_layernorm.weight"), grad("emb_layernorm.bias"), g_word, B, T, Dt,
-                     c.vocab, c.eps_t, tp.src_row, tp.cnt)
+            ops.call("text_embed_ln_bwd_packed", *a, tp.src_row, tp.cnt)
         else:
-            ops.call("text_embed_ln_bwd", ids32, tt32, f32("word_embeddings"), f32("position_embeddings"), f32("token_type_embeddings"),
-                     f32("emb_layernorm.weight"), dy, ws["t_dxemb"], grad("emb_layernorm.weight"), grad("emb_layernorm.bias"), g_word, B, T, Dt,
-                     c.vocab, c.eps_t)
+            ops.call("text_embed_ln_bwd", *a)
         dxe = ws["t_dxemb"].view(B, T, Dt)
         grad("position_embeddings").add_(dxe.sum(dim=0))
-        tt = tt32.view(-1).long() if tt32 is not None else torch.zeros(B * T, device=self.device, dtype=torch.long)
+        tt = tp.tt32.view(-1).long() if tp.tt32 is not None else torch.zeros(B * T, device=self.device, dtype=torch.long)
         grad("token_type_embeddings").index_add_(0, tt, ws["t_dxemb"])
-
-    def _backward_text_lora(self, d_words: Optional[torch.Tensor], d_txt_g: Optional[torch.Tensor]):
-        """backward_text with LoRA adapters on a frozen base: the same chain of dgrad GEMMs (on the base's transposed copies), LayerNorm and
-        attention backwards, WITHOUT any base parameter gradient - no weight-gradient GEMM, no LayerNorm gamma / beta sums, no embedding
-        backward.  Per layer, after the attention backward has written d qkv: medmoe_lora_bwd_dx (d U, and the adapters' term of d x added into
-        the base dgrad GEMM's output) and medmoe_lora_bwd_wgrad (the adapters' gradients, += into the arena).  At layer 0 nothing below
-        trains: the dgrad GEMM and the d x term are both skipped."""
-        c, ws, lo, t, tp = self.cfg, self.ws, self.lora, self.params.text, self._tp
-        B, T, Dt, H, L = self.B, c.max_len, c.d_t, c.n_head_t, c.n_layer_t
-        _, _, km = self._tt_state
-        wt = self._base_wt
-        dH = ws["t_dH"]
-        drop = self._text_drop_step is not None
-        ph, pa = (c.text_hidden_dropout, c.text_attn_dropout) if drop else (0.0, 0.0)
-        if tp.packed:
-            ops.call("text_aggregate_bwd_packed", d_words, d_txt_g, self._seg_used, tp.src_row, tp.cnt, dH, B, T, Dt)
-        else:
-            ops.call("text_aggregate_bwd", d_words, d_txt_g, self._seg_used, dH, B, T, Dt)
-        dy, d1, d2 = ws["t_da"], ws["t_db"], ws["t_dc"]
-        dy.copy_(dH)
-        for l in range(L - 1, -1, -1):
-            b = f"layer.{l}."
-            st1, st2 = ws[f"t_st1{l}"], ws[f"t_st2{l}"]
-            tp.ln_bwd(dy, ws[f"t_x2{l}"], st2[0], st2[1], t[b + "feedforward_layernorm.weight"], d1)
-            dz = ops.dropout_apply(d1, ws["t_dzd"], self._drop_rng(4 * l + 2, ph)) if ph > 0.0 else d1
-            tp.gemm(dz, wt(b + "feedforward.model.2.weight"), ws["t_dz"], aux=ws[f"t_dg{l}"], epi=ops.EPI_MUL_AUX)
-            tp.gemm(ws["t_dz"], wt(b + "feedforward.model.0.weight"), d2, residual=d1)
-            tp.ln_bwd(d2, ws[f"t_x1{l}"], st1[0], st1[1], t[b + "attention_layernorm.weight"], d1)
-            dz = ops.dropout_apply(d1, ws["t_dzd"], self._drop_rng(4 * l + 1, ph)) if ph > 0.0 else d1
-            tp.gemm(dz, wt(b + "attention.output_proj.weight"), ws["t_datt"])
-            if pa > 0.0:
-                ops.attn_drop_bwd(ws[f"t_qkv{l}"], ws[f"t_att{l}"], ws["t_datt"], ws[f"t_lse{l}"], km, ws["t_dqkv"], ws["t_delta"], B, T, H,
-                                  self._drop_rng(4 * l, pa))
-            else:
-                tp.attn_bwd(ws[f"t_qkv{l}"], ws[f"t_att{l}"], ws["t_datt"], ws[f"t_lse{l}"], ws["t_dqkv"], ws["t_delta"])
-            rng = self._lora_rng(l)
-            if l > 0:
-                tp.gemm(ws["t_dqkv"], wt(b + "attention.input_proj.weight"), dy, residual=d1)           # d x = d x1 + dqkv Wqkv (base)
-            ops.lora_bwd_dx(ws["t_dqkv"], lo.B16t(l), lo.A16t(l), ws["t_ldu"], dy if l > 0 else None, lo.targets, lo.scale, rng, rows_dev=tp.cnt)
-            ops.lora_bwd_wgrad(ws["t_dqkv"], ws[f"t_x{l}"], ws[f"t_lu{l}"], ws["t_ldu"], lo.gA(l), lo.gB(l), ws["t_lsc"], lo.targets, lo.scale, rng, rows_dev=tp.cnt)
-            if l > 0 and l >= self._text_first_sel:
-                dy.add_(dH)
 
     def text_soft_target(self) -> torch.Tensor:
         """Caption-to-caption scores of the Soft-GLoRIA losses (medmoe_module.py:258-281 get_text_soft_target): the frozen text model's last
         hidden state at [CLS] (token_pooling :243-244), L2-normalised, all pairwise products -> fp32 [B, B].  The reference runs a second
         pretrained BertModel (`tool_bert`) for it; with `freeze_bert: true` that is the text tower's own BERT, whose last layer the
         forward pass just produced.  Call after forward_text."""
-        h, seq_off = self._text_last
+        h, seq_off = self._rows.last, self._rows.seq_off
         B, T, Dt = self.B, self.cfg.max_len, self.cfg.d_t
         rows = seq_off[:B].long() if seq_off is not None else torch.arange(B, device=self.device) * T
         cls = h.view(-1, Dt).index_select(0, rows).float().contiguous()
@@ -1337,19 +1303,7 @@ class Engine:
             self.params.zero_grad()
             if self.train_text:
                 self.text_arena().zero_grad()
-        if self.overlap_wgrad and batch["image"].is_cuda and B * self.cfg.n_tok_v <= 131072:
-            # the frozen text tower is independent of the image tower: at small per-rank batches its GEMMs (77 tokens per pair) fill
-            # a fraction of the chip, so it runs on the second stream underneath the image tower
-            main, side = torch.cuda.current_stream(), self._side_stream()
-            ev = torch.cuda.Event(); ev.record(main); side.wait_event(ev)
-            with torch.cuda.stream(side):
-                self.forward_text(batch["ids"], batch["attn_mask"], batch.get("token_type"), training=True)
-                done = torch.cuda.Event(); done.record(side)
-            self._forward_image_train(batch["image"])
-            main.wait_event(done)
-        else:
-            self._forward_image_train(batch["image"])
-            self.forward_text(batch["ids"], batch["attn_mask"], batch.get("token_type"), training=True)
+        self._forward_both(batch, training=True)
         try:
             return self._train_step_rest(batch, optimizer, loss_scale)
         finally:
@@ -1391,11 +1345,14 @@ class Engine:
         self.dropout_step += 1                                      # the next call draws new masks (evaluation never advances it)
         if optimizer:
             self.optimizer_step()
-        lp = self.ws["loss_parts"]
-        c = self.cfg
-        # loss_parts hold the WEIGHTED global/local parts; report the reference's unweighted names too
-        # (the router CE kernel reports the plain mean: scale it here so that every reported loss follows loss_scale)
-        cls = lp[0] * loss_scale
+        return self._step_result(loss_scale)
+
+    def _step_result(self, loss_scale: Optional[float]):
+        """The dict a step returns (device scalars).  loss_parts hold the WEIGHTED global/local parts; report the reference's unweighted
+        names too.  The router CE kernel reports the plain mean: a training step scales it here so that every reported loss follows
+        loss_scale; an evaluation (None) reports a copy of it as it is."""
+        lp, c = self.ws["loss_parts"], self.cfg
+        cls = lp[0].clone() if loss_scale is None else lp[0] * loss_scale
         return {"loss": c.w_cls * cls + lp[2] + lp[3], "classifier_loss": cls, "classifier_acc": lp[1],
                 "g_loss": lp[2] / c.w_global, "l_loss": lp[3] / c.w_local}
 
@@ -1440,10 +1397,8 @@ class Engine:
         self._forward_both(batch)
         self.global_loss(grad=False)
         self._local_loss_eval()
-        lp = self.ws["loss_parts"]
-        ops.call("router_eval", self.ws["probs"], batch["label"].to(I32).contiguous(), lp, B, c.n_expert)
-        return {"loss": c.w_cls * lp[0] + lp[2] + lp[3], "classifier_loss": lp[0].clone(), "classifier_acc": lp[1],
-                "g_loss": lp[2] / c.w_global, "l_loss": lp[3] / c.w_local}
+        ops.call("router_eval", self.ws["probs"], batch["label"].to(I32).contiguous(), self.ws["loss_parts"], B, c.n_expert)
+        return self._step_result(None)
 
     def _local_loss_eval(self):
         """GLoRIA local loss value (losses.py:961-1026) of ws["img_l"] against ws["words"] into loss_parts[3]; ws["gsim"] is the heads' scratch.
@@ -1473,18 +1428,22 @@ class Engine:
         else:
             self._local_heads(sim, ws["gsim"], c.w_local / B)
 
-    def _forward_both(self, b):
+    def _forward_both(self, b, training: bool = False):
+        """Both towers' forward passes; `training`: those of a training step (the image tower's stochastic depth, the text tower's dropouts)."""
+        forward_image = self._forward_image_train if training else self.forward_image
         if self.overlap_wgrad and b["image"].is_cuda and self.B * self.cfg.n_tok_v <= 131072:
+            # the text tower is independent of the image tower: at small per-rank batches its GEMMs (77 tokens per pair) fill
+            # a fraction of the chip, so it runs on the second stream underneath the image tower
             main, side = torch.cuda.current_stream(), self._side_stream()
             ev = torch.cuda.Event(); ev.record(main); side.wait_event(ev)
             with torch.cuda.stream(side):
-                self.forward_text(b["ids"], b["attn_mask"], b.get("token_type"))
+                self.forward_text(b["ids"], b["attn_mask"], b.get("token_type"), training=training)
                 done = torch.cuda.Event(); done.record(side)
-            self.forward_image(b["image"])
+            forward_image(b["image"])
             main.wait_event(done)
         else:
-            self.forward_image(b["image"])
-            self.forward_text(b["ids"], b["attn_mask"], b.get("token_type"))
+            forward_image(b["image"])
+            self.forward_text(b["ids"], b["attn_mask"], b.get("token_type"), training=training)
 
     def _train_step_graphed(self, batch, optimizer, zero_grad, loss_scale):
         """train_step with the forward and the backward replayed from hipGraphs (MEDMOE_GRAPH=1).  The first two steps of a (batch size,
@@ -1527,10 +1486,7 @@ class Engine:
             st["bwd"].replay()
         if optimizer:
             self.optimizer_step()
-        lp, c = self.ws["loss_parts"], self.cfg
-        cls = lp[0] * loss_scale
-        return {"loss": c.w_cls * cls + lp[2] + lp[3], "classifier_loss": cls, "classifier_acc": lp[1],
-                "g_loss": lp[2] / c.w_global, "l_loss": lp[3] / c.w_local}
+        return self._step_result(loss_scale)
 
     # reference-layout views (med_moe.py:102-108)
     def outputs(self):
