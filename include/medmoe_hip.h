@@ -263,6 +263,10 @@ int medmoe_stage_grad_add(const void* dF, const int* slot_of, void* dx, int B, i
 /* Fp32LayerNorm forward (normalizations.py:8-19; transformer.py:78-79) */
 int medmoe_layernorm_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, int rows, int D, float eps, int out_f32, hipStream_t stream);
 
+/* y = bf16((x - mean) * rstd * gamma + beta) from the per-row statistics a LayerNorm forward launch saved: bit-identical to the y that launch
+   wrote (activation recomputation).  x, y bf16 [rows, D]; D % 8 == 0, D <= 2048.  One streaming pass, no atomics. */
+int medmoe_layernorm_apply(const void* x, const float* mean, const float* rstd, const float* gamma, const float* beta, void* y, int rows, int D, hipStream_t stream);
+
 /* Fp32LayerNorm backward (+ fused residual-gradient add) */
 int medmoe_layernorm_bwd(const void* dy, const void* x, const float* mean, const float* rstd, const float* gamma, const void* add, void* dx, float* dgamma, float* dbeta, int rows, int D, hipStream_t stream);
 

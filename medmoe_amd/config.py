@@ -4,6 +4,8 @@ BASELINE.json configs)."""
 from dataclasses import dataclass
 from typing import List, Tuple
 
+VIT_CHECKPOINT_MODES = ("none", "selective", "full")
+
 
 @dataclass
 class MedMoEConfig:
@@ -45,6 +47,12 @@ class MedMoEConfig:
     # sample b skips the attention / the feed-forward branch of layer l with probability p_l = linspace(0, vit_drop_path, n_layer_v)[l], survivors
     # are scaled by 1 / (1 - p_l); the two branches draw independently.  The keep bits are a function of (dropout_seed, step, site, global sample)
     vit_drop_path: float = 0.0
+    # activation recomputation of the image tower (open_clip's --grad-checkpointing).  "none": every layer keeps all its
+    # activations for the backward (16 d_v bf16 per token and layer).  "selective": the layer input, qkv, the attention output and the
+    # mid-block residual stay (6 d_v); both LayerNorm outputs come back from the saved statistics and FC1 is run again before the layer's
+    # backward.  "full": only the layer input stays (1 d_v); the layer's forward up to FC1 is run again.  MEDMOE_VIT_CHECKPOINT=selective|full
+    # switches it on too (vit_checkpoint_mode).  The text tower is not checkpointed
+    vit_checkpoint: str = "none"
     # variable-length pass of the TRAINABLE text tower (full or LoRA): forward and backward run on the packed non-padding tokens,
     # as the frozen tower's forward does (same rule: B <= 1024 and T <= 80, else the padded pass).  Opt-in; MEDMOE_TEXT_TRAIN_VARLEN=1 switches
     # it on too.  Hidden / LoRA dropout masks are then functions of the PACKED (row, column); attention dropout has no packed kernels
@@ -127,9 +135,21 @@ class MedMoEConfig:
         import torch
         return [float(v) for v in torch.linspace(0, float(self.vit_drop_path), self.n_layer_v)]
 
+    def vit_checkpoint_mode(self) -> str:
+        """The recomputation mode an engine built from this config runs: MEDMOE_VIT_CHECKPOINT (none | selective | full) when set, else
+        vit_checkpoint."""
+        import os
+        env = os.environ.get("MEDMOE_VIT_CHECKPOINT", "")
+        if env not in ("",) + VIT_CHECKPOINT_MODES:
+            raise ValueError(f"MEDMOE_VIT_CHECKPOINT must be one of {VIT_CHECKPOINT_MODES}, got {env!r}")
+        return env or self.vit_checkpoint
+
     def validate(self):
         if not 0.0 <= float(self.vit_drop_path) < 1.0:
             raise ValueError(f"vit_drop_path must be in [0, 1), got {self.vit_drop_path}")
+        if self.vit_checkpoint not in VIT_CHECKPOINT_MODES:
+            raise ValueError(f"vit_checkpoint (model.model.vision.grad_checkpointing) must be one of {VIT_CHECKPOINT_MODES}, "
+                             f"got {self.vit_checkpoint!r}")
         if self.grad_comm_dtype not in ("fp32", "bf16"):
             raise ValueError(f"grad_comm_dtype must be 'fp32' or 'bf16', got {self.grad_comm_dtype!r}")
         if not 0.0 <= float(self.ema_decay) < 1.0:

@@ -116,6 +116,58 @@ static int layernorm_fwd_impl(const void* x, const float* gamma, const float* be
   return mm_check_launch();
 }
 
+// y = bf16((x - mean) * rstd * gamma + beta) from SAVED per-row statistics (activation recomputation): what layernorm_fwd_kernel
+// (and the fused LayerNorm launches of dropout.hip) wrote into y for the same x, mean, rstd - the normalisation is the same expression in
+// the same order, so the bits agree.  No reduction, no LDS: the [rows, D] matrix is one flat run of 16-byte chunks, a workgroup takes
+// 256 * LNA_U consecutive ones (every lane busy whatever D is; LNA_U independent loads in flight per lane) and finds its first row by ONE
+// 64-bit division of a workgroup-uniform value; per chunk the row and column follow from a 32-bit one.
+constexpr int LNA_U = 4;
+__global__ __launch_bounds__(256) void layernorm_apply_kernel(const bf16_t* __restrict__ x, const float* __restrict__ mean,
+                                                              const float* __restrict__ rstd, const float* __restrict__ gamma,
+                                                              const float* __restrict__ beta, bf16_t* __restrict__ y, long long total,
+                                                              int nchunk) {
+  const long long c0 = (long long)blockIdx.x * (256 * LNA_U);      // first chunk of this workgroup; total = rows * nchunk
+  const long long row0 = c0 / nchunk;
+  const unsigned off0 = (unsigned)(c0 - row0 * nchunk) + threadIdx.x;
+  uint4 raw[LNA_U];
+#pragma unroll
+  for (int u = 0; u < LNA_U; ++u) {
+    const long long i = c0 + u * 256 + threadIdx.x;
+    raw[u] = i < total ? *(const uint4*)(x + i * 8) : make_uint4(0u, 0u, 0u, 0u);
+  }
+#pragma unroll
+  for (int u = 0; u < LNA_U; ++u) {
+    const long long i = c0 + u * 256 + threadIdx.x;
+    if (i >= total) break;
+    const unsigned t = off0 + u * 256, dr = t / (unsigned)nchunk, c = t - dr * (unsigned)nchunk;
+    const float mu = mean[row0 + dr], rs = rstd[row0 + dr];
+    const float4 g0 = *(const float4*)(gamma + c * 8), g1 = *(const float4*)(gamma + c * 8 + 4);
+    const float4 b0 = *(const float4*)(beta + c * 8), b1 = *(const float4*)(beta + c * 8 + 4);
+    const float gg[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
+    const float bb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+    const uint32_t w[4] = {raw[u].x, raw[u].y, raw[u].z, raw[u].w};
+    float v[8], o[8];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      v[2 * e] = __uint_as_float(w[e] << 16);
+      v[2 * e + 1] = __uint_as_float(w[e] & 0xffff0000u);
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = (v[e] - mu) * rs * gg[e] + bb[e];
+    *(uint4*)(y + i * 8) = make_uint4(pack2bf(o[0], o[1]), pack2bf(o[2], o[3]), pack2bf(o[4], o[5]), pack2bf(o[6], o[7]));
+  }
+}
+
+extern "C" int medmoe_layernorm_apply(const void* x, const float* mean, const float* rstd, const float* gamma, const float* beta, void* y,
+                                      int rows, int D, hipStream_t stream) {
+  if (!x || !mean || !rstd || !gamma || !beta || !y) return MM_ERR_ARG;
+  if (rows <= 0 || D <= 0 || (D % 8) || D > 64 * 8 * LN_MAX_CHUNKS) return MM_ERR_SHAPE;
+  const long long total = (long long)rows * (D / 8), per = 256 * LNA_U;
+  hipLaunchKernelGGL(layernorm_apply_kernel, dim3((unsigned)((total + per - 1) / per)), dim3(256), 0, stream, (const bf16_t*)x, mean, rstd,
+                     gamma, beta, (bf16_t*)y, total, D / 8);
+  return mm_check_launch();
+}
+
 // dx = rstd * (dy*g - mean(dy*g) - xhat * mean(dy*g*xhat)) [+ add];  dgamma += dy*xhat; dbeta += dy
 // LNB_WAVES waves per workgroup: the dgamma / dbeta partials of a workgroup's waves meet in LDS and leave as ONE atomic per column and
 // workgroup.  With 4-wave workgroups (1024 of them) every launch ended in 1.57 M atomics onto the same 1536 addresses - serialised at the

@@ -159,6 +159,45 @@ class _TextRows:
 _TextBufs = collections.namedtuple("_TextBufs", "qkv att lse x1 st1 r h aux x2 st2 out lu")
 
 
+# Activation recomputation of the image tower (cfg.vit_checkpoint).  A layer's eight bf16 activations and where a mode keeps them:
+# per layer under the names below, or (the names listed for the mode) in one of TWO shared sets "ck{l % 2}_<name>", filled again before the
+# layer's backward.  The LayerNorm statistics st1_{l} / st2_{l} and lse{l} are kept per layer in every mode.
+_VIT_ACT = {"x": "x{}", "ln1": "ln1_{}", "qkv": "qkv{}", "att": "att{}", "xmid": "xmid{}", "ln2": "ln2_{}", "z": "z{}", "h": "h{}"}
+_VIT_SHARED = {"none": (), "selective": ("ln1", "ln2", "z", "h"), "full": ("ln1", "qkv", "att", "xmid", "ln2", "z", "h")}
+
+
+def vit_activation_plan(cfg: MedMoEConfig, B: int, mode: str) -> Dict[str, tuple]:
+    """Buffer name -> (shape, dtype) of everything `Engine._alloc` allocates for the image tower's activations at batch B under
+    cfg.vit_checkpoint = mode: the layer inputs x0 .. x{L}, per layer what the mode keeps, the statistics and lse, and the two shared sets
+    of what it recomputes.  Pure host arithmetic (no GPU, no library): the memory a mode needs can be read off before anything is built."""
+    if mode not in _VIT_SHARED:
+        raise ValueError(f"vit_checkpoint must be one of {tuple(_VIT_SHARED)}, got {mode!r}")
+    Nt, Dv, L, H = cfg.n_tok_v, cfg.d_v, cfg.n_layer_v, cfg.n_head_v
+    M = B * Nt
+    width = {"x": Dv, "ln1": Dv, "qkv": 3 * Dv, "att": Dv, "xmid": Dv, "ln2": Dv, "z": cfg.ff_v, "h": cfg.ff_v}
+    shared = _VIT_SHARED[mode]
+    plan = {}
+    for l in range(L + 1):
+        plan[f"x{l}"] = ((M, Dv), BF)
+    for l in range(L):
+        for n in ("ln1", "st1", "qkv", "att", "lse", "xmid", "ln2", "st2", "z", "h"):      # the order of the workspace before the modes existed
+            if n in ("st1", "st2"):
+                plan[f"{n}_{l}"] = ((2, M), F32)
+            elif n == "lse":
+                plan[f"lse{l}"] = ((B * H * Nt,), F32)
+            elif n not in shared:
+                plan[_VIT_ACT[n].format(l)] = ((M, width[n]), BF)
+    for s in range(2 if shared else 0):
+        for n in shared:
+            plan[f"ck{s}_{n}"] = ((M, width[n]), BF)
+    return plan
+
+
+def plan_bytes(plan: Dict[str, tuple]) -> int:
+    """Total bytes of a buffer plan (vit_activation_plan)."""
+    return sum(int(np.prod(shape)) * {BF: 2, F32: 4}[dt] for shape, dt in plan.values())
+
+
 class Engine:
     def __init__(self, cfg: MedMoEConfig, device="cuda:0", seed: int = 0, vocab: Optional[VocabTables] = None):
         cfg.validate()
@@ -180,6 +219,14 @@ class Engine:
         self.vit_drop_scales: Optional[torch.Tensor] = None
         if cfg.vit_drop_path > 0.0:
             self._refuse_with_graph("vit_drop_path", "model.model.vision.drop_path_rate")
+        # activation recomputation of the image tower (cfg.vit_checkpoint or MEDMOE_VIT_CHECKPOINT): fixed for the engine's life,
+        # the workspace is laid out for it (_alloc) and every _vit_backward recomputes what the mode did not keep
+        self.vit_checkpoint = cfg.vit_checkpoint_mode()
+        self._ck_shared = _VIT_SHARED[self.vit_checkpoint]
+        if self.vit_checkpoint != "none" and os.environ.get("MEDMOE_GRAPH", "0") == "1":
+            raise NotImplementedError(f"vit_checkpoint={self.vit_checkpoint!r} (model.model.vision.grad_checkpointing, MEDMOE_VIT_CHECKPOINT) with "
+                                      "MEDMOE_GRAPH=1: the recomputation's waits on the second stream have not been verified under hipGraph "
+                                      "capture")
         if not torch.cuda.is_available():
             raise RuntimeError("medmoe_amd.Engine needs a GPU: the HIP path is the only path")
         self.cfg = cfg
@@ -437,13 +484,10 @@ class Engine:
         def buf(name, shape, dtype=BF):
             ws[name] = torch.empty(shape, device=dev, dtype=dtype)
         ws["im2col"] = torch.zeros((B * P, c.patch_dim_pad), device=dev, dtype=BF)    # pad columns (patch 14: 588..639) stay zero
-        for l in range(L + 1):
-            buf(f"x{l}", (M, Dv))
-        for l in range(L):
-            buf(f"ln1_{l}", (M, Dv)); buf(f"st1_{l}", (2, M), F32)
-            buf(f"qkv{l}", (M, 3 * Dv)); buf(f"att{l}", (M, Dv)); buf(f"lse{l}", (B * H * Nt,), F32)
-            buf(f"xmid{l}", (M, Dv)); buf(f"ln2_{l}", (M, Dv)); buf(f"st2_{l}", (2, M), F32)
-            buf(f"z{l}", (M, c.ff_v)); buf(f"h{l}", (M, c.ff_v))
+        # the tower's activations: x{l}, per layer ln1 / st1 / qkv / att / lse / xmid / ln2 / st2 / z / h - or, under cfg.vit_checkpoint, the
+        # kept ones and the two shared sets (vit_activation_plan; _act finds a layer's buffer)
+        for name, (shape, dtype) in vit_activation_plan(c, B, self.vit_checkpoint).items():
+            buf(name, shape, dtype)
         buf("lnf", (M, Dv)); buf("stf", (2, M), F32)
         # backward scratch
         buf("dxa", (M, Dv)); buf("dxb", (M, Dv)); buf("dln", (M, Dv)); buf("dqkv", (M, 3 * Dv)); buf("datt", (M, Dv))
@@ -573,53 +617,83 @@ class Engine:
         ops.call("mean_tokens", ws["lnf"], ws["router_in"], B, Nt, Dv, 1, P)          # swin.py:137
         self._moe_forward(B)
 
+    def _act(self, l: int, name: str) -> torch.Tensor:
+        """Layer l's activation `name` (x | ln1 | qkv | att | xmid | ln2 | z | h): the layer's own buffer, or - when cfg.vit_checkpoint does
+        not keep it - the one of the shared set the layer's parity selects.  "none" keeps everything: ws["ln1_{l}"] and so on."""
+        if name in self._ck_shared:
+            return self.ws[f"ck{l & 1}_{name}"]
+        return self.ws[_VIT_ACT[name].format(l)]
+
     def _vit_blocks(self, B):
         """The pre-norm blocks (transformer.py:98-114) from ws["x0"] to ws["x{L}"] and the final LayerNorm (-> ws["lnf"]); every
-        intermediate the backward needs stays in the workspace.  tests/test_ref_fixtures_gpu.py feeds the reference's own
-        TransformerEncoder fixture in here."""
+        intermediate the backward needs stays in the workspace (cfg.vit_checkpoint: the kept ones; the rest passes through the shared sets
+        and is recomputed by _vit_backward).  tests/test_ref_fixtures_gpu.py feeds the reference's own TransformerEncoder fixture in here."""
         c, p, ws = self.cfg, self.params, self.ws
-        Nt, Dv, H, L = c.n_tok_v, c.d_v, c.n_head_v, c.n_layer_v
+        L = c.n_layer_v
         dp = self._vit_drop_layers()
         ln_done = False                                      # the previous layer's feed-forward site already wrote this LayerNorm
         for l in range(L):
-            pre = f"vit.layer.{l}."
-            x, xo = ws[f"x{l}"], ws[f"x{l + 1}"]
-            st1, st2 = ws[f"st1_{l}"], ws[f"st2_{l}"]
-            if not ln_done:
-                ops.layernorm_fwd(x, p.f32(pre + "attention_layernorm.weight"), p.f32(pre + "attention_layernorm.bias"),
-                                  ws[f"ln1_{l}"], st1[0], st1[1], c.eps_v)
-            ln_done = False
-            ops.gemm_nt(ws[f"ln1_{l}"], p.w16(pre + "attention.input_proj.weight"), ws[f"qkv{l}"],
-                        bias=p.f32(pre + "attention.input_proj.bias"))
-            ops.attn_fwd(ws[f"qkv{l}"], ws[f"att{l}"], ws[f"lse{l}"], None, B, Nt, H)
-            if dp[l] is None:
-                ops.gemm_nt(ws[f"att{l}"], p.w16(pre + "attention.output_proj.weight"), ws[f"xmid{l}"],
-                            bias=p.f32(pre + "attention.output_proj.bias"), residual=x)
-                ops.layernorm_fwd(ws[f"xmid{l}"], p.f32(pre + "feedforward_layernorm.weight"),
-                                  p.f32(pre + "feedforward_layernorm.bias"), ws[f"ln2_{l}"], st2[0], st2[1], c.eps_v)
-            else:
-                # stochastic depth (DESIGN 3j): the GEMM leaves the branch in dp_a; the per-sample scale, the residual add and the LayerNorm
-                # that follows it are one launch
-                ops.gemm_nt(ws[f"att{l}"], p.w16(pre + "attention.output_proj.weight"), ws["dp_a"], bias=p.f32(pre + "attention.output_proj.bias"))
-                ops.scale_add_layernorm_fwd(ws["dp_a"], x, dp[l][0], Nt, p.f32(pre + "feedforward_layernorm.weight"),
-                                            p.f32(pre + "feedforward_layernorm.bias"), ws[f"xmid{l}"], ws[f"ln2_{l}"], st2[0], st2[1], c.eps_v)
-            ops.gemm_nt(ws[f"ln2_{l}"], p.w16(pre + "feedforward.model.0.weight"), ws[f"h{l}"],
-                        bias=p.f32(pre + "feedforward.model.0.bias"), aux=ws[f"z{l}"], epi=ops.EPI_GELU_DAUX)    # aux <- GELU'(z): the backward epilogue is one multiply
-            if dp[l] is None:
-                ops.gemm_nt(ws[f"h{l}"], p.w16(pre + "feedforward.model.2.weight"), xo,
-                            bias=p.f32(pre + "feedforward.model.2.bias"), residual=ws[f"xmid{l}"])
-            else:
-                # the feed-forward site writes the NEXT LayerNorm with it: ln1 of layer l + 1, or the final one
-                ops.gemm_nt(ws[f"h{l}"], p.w16(pre + "feedforward.model.2.weight"), ws["dp_a"], bias=p.f32(pre + "feedforward.model.2.bias"))
-                nxt = f"vit.layer.{l + 1}.attention_layernorm." if l + 1 < L else "vit.final_layer_norm."
-                y, st = (ws[f"ln1_{l + 1}"], ws[f"st1_{l + 1}"]) if l + 1 < L else (ws["lnf"], ws["stf"])
-                ops.scale_add_layernorm_fwd(ws["dp_a"], ws[f"xmid{l}"], dp[l][1], Nt, p.f32(nxt + "weight"), p.f32(nxt + "bias"), xo, y,
-                                            st[0], st[1], c.eps_v)
-                ln_done = True
+            ln_done = self._vit_layer_forward(l, dp[l], ln_done)
         if not ln_done:
             xl = ws[f"x{L}"]
             ops.layernorm_fwd(xl, p.f32("vit.final_layer_norm.weight"), p.f32("vit.final_layer_norm.bias"), ws["lnf"],
                               ws["stf"][0], ws["stf"][1], c.eps_v)
+
+    def _vit_layer_forward(self, l: int, dp_l, ln_done: bool = False, recompute: bool = False) -> bool:
+        """Layer l's forward launches from ws["x{l}"]; dp_l: the layer's stochastic-depth scales or None (_vit_drop_layers).
+        The forward pass (recompute=False) runs them all, to ws["x{l + 1}"]; ln_done: the previous layer's feed-forward site already wrote
+        this layer's first LayerNorm.  Returns whether this layer's feed-forward site wrote the NEXT LayerNorm.
+        recompute (cfg.vit_checkpoint, ahead of the layer's backward): the launches up to FC1 again, into the layer's shared set.  Both
+        LayerNorm outputs come from the kept input and the kept statistics (layernorm_apply: the bits of the forward's); "selective" kept
+        qkv / att / xmid and skips the attention half, "full" runs it again from x{l} - the same launches on the same inputs, so the same
+        bits (the stochastic-depth site under the step's scales; it rewrites st2 and attn_fwd rewrites lse with the values they hold).
+        FC2 and the next layer's LayerNorm are not run again: x{l + 1} is kept and the backward reads nothing else of theirs."""
+        c, p, ws = self.cfg, self.params, self.ws
+        B, Nt, H, L = self.B, c.n_tok_v, c.n_head_v, c.n_layer_v
+        pre = f"vit.layer.{l}."
+        act = lambda name: self._act(l, name)
+        x, xo = ws[f"x{l}"], ws[f"x{l + 1}"]
+        st1, st2 = ws[f"st1_{l}"], ws[f"st2_{l}"]
+        ln2_w, ln2_b = p.f32(pre + "feedforward_layernorm.weight"), p.f32(pre + "feedforward_layernorm.bias")
+        if recompute:
+            ops.layernorm_apply(x, st1[0], st1[1], p.f32(pre + "attention_layernorm.weight"), p.f32(pre + "attention_layernorm.bias"), act("ln1"))
+        elif not ln_done:
+            ops.layernorm_fwd(x, p.f32(pre + "attention_layernorm.weight"), p.f32(pre + "attention_layernorm.bias"),
+                              act("ln1"), st1[0], st1[1], c.eps_v)
+        ln2_done = False
+        if not recompute or self.vit_checkpoint == "full":
+            ops.gemm_nt(act("ln1"), p.w16(pre + "attention.input_proj.weight"), act("qkv"),
+                        bias=p.f32(pre + "attention.input_proj.bias"))
+            ops.attn_fwd(act("qkv"), act("att"), ws[f"lse{l}"], None, B, Nt, H)
+            if dp_l is None:
+                ops.gemm_nt(act("att"), p.w16(pre + "attention.output_proj.weight"), act("xmid"),
+                            bias=p.f32(pre + "attention.output_proj.bias"), residual=x)
+            else:
+                # stochastic depth (DESIGN 3j): the GEMM leaves the branch in dp_a; the per-sample scale, the residual add and the LayerNorm
+                # that follows it are one launch
+                ops.gemm_nt(act("att"), p.w16(pre + "attention.output_proj.weight"), ws["dp_a"], bias=p.f32(pre + "attention.output_proj.bias"))
+                ops.scale_add_layernorm_fwd(ws["dp_a"], x, dp_l[0], Nt, ln2_w, ln2_b, act("xmid"), act("ln2"), st2[0], st2[1], c.eps_v)
+                ln2_done = True
+        if not ln2_done:
+            if recompute:
+                ops.layernorm_apply(act("xmid"), st2[0], st2[1], ln2_w, ln2_b, act("ln2"))
+            else:
+                ops.layernorm_fwd(act("xmid"), ln2_w, ln2_b, act("ln2"), st2[0], st2[1], c.eps_v)
+        ops.gemm_nt(act("ln2"), p.w16(pre + "feedforward.model.0.weight"), act("h"),
+                    bias=p.f32(pre + "feedforward.model.0.bias"), aux=act("z"), epi=ops.EPI_GELU_DAUX)    # aux <- GELU'(z): the backward epilogue is one multiply
+        if recompute:
+            return False
+        if dp_l is None:
+            ops.gemm_nt(act("h"), p.w16(pre + "feedforward.model.2.weight"), xo,
+                        bias=p.f32(pre + "feedforward.model.2.bias"), residual=act("xmid"))
+            return False
+        # the feed-forward site writes the NEXT LayerNorm with it: ln1 of layer l + 1, or the final one
+        ops.gemm_nt(act("h"), p.w16(pre + "feedforward.model.2.weight"), ws["dp_a"], bias=p.f32(pre + "feedforward.model.2.bias"))
+        nxt = f"vit.layer.{l + 1}.attention_layernorm." if l + 1 < L else "vit.final_layer_norm."
+        y, st = (self._act(l + 1, "ln1"), ws[f"st1_{l + 1}"]) if l + 1 < L else (ws["lnf"], ws["stf"])
+        ops.scale_add_layernorm_fwd(ws["dp_a"], act("xmid"), dp_l[1], Nt, p.f32(nxt + "weight"), p.f32(nxt + "bias"), xo, y,
+                                    st[0], st[1], c.eps_v)
+        return True
 
     def _vit_drop_layers(self):
         """Per layer: None (today's launches) or the layer's [2, B] scales - the layers with p_l > 0 while self.vit_drop_scales is set."""
@@ -1240,8 +1314,17 @@ class Engine:
         stage_of = {l: s for s, l in enumerate(c.stage_layers())} if stage_grads else {}
         dp = self._vit_drop_layers()
         w_dz = w_dx2 = w_dqkv = None                       # last wgrad that READ the scratch buffer
+        w_set = [None, None]                               # cfg.vit_checkpoint: last wgrad that read a buffer of the shared set
         for l in range(L - 1, -1, -1):
             pre = f"vit.layer.{l}."
+            act = lambda name: self._act(l, name)
+            if self._ck_shared:
+                # recompute what the mode did not keep into the shared set of this parity.  Layer l + 2 used the set: its weight-gradient
+                # GEMMs may still be reading h, ln2, att, ln1 on the second stream, which runs in order - the last one's event covers all four
+                wait(w_set[l & 1])
+                if dp[l] is not None and self.vit_checkpoint == "full":
+                    wait(w_dx2)                            # the out-proj branch passes through dp_a again: layer l + 1's out-proj wgrad read it
+                self._vit_layer_forward(l, dp[l], recompute=True)
             if (l + 1) in stage_of:
                 ops.call("stage_grad_add", ws["dF"][stage_of[l + 1]], ws["slot_of"], dx, B, k, P, Nt, Dv)
             st1, st2 = ws[f"st1_{l}"], ws[f"st2_{l}"]
@@ -1252,13 +1335,13 @@ class Engine:
             if dp[l] is not None:
                 g2 = ws["dp_b"]
                 ops.call("drop_path", dx, None, dp[l][1], g2, B, Nt * Dv)
-            w_dx = wgrad(g2, ws[f"h{l}"], p.grad(pre + "feedforward.model.2.weight"), db=p.grad(pre + "feedforward.model.2.bias"))
+            w_dx = wgrad(g2, act("h"), p.grad(pre + "feedforward.model.2.weight"), db=p.grad(pre + "feedforward.model.2.bias"))
             wait(w_dz)
-            ops.gemm_nt(g2, p.w16t(pre + "feedforward.model.2.weight"), ws["dz"], aux=ws[f"z{l}"], epi=ops.EPI_MUL_AUX)
-            w_dz = wgrad(ws["dz"], ws[f"ln2_{l}"], p.grad(pre + "feedforward.model.0.weight"), db=p.grad(pre + "feedforward.model.0.bias"))
+            ops.gemm_nt(g2, p.w16t(pre + "feedforward.model.2.weight"), ws["dz"], aux=act("z"), epi=ops.EPI_MUL_AUX)
+            w_dz = wgrad(ws["dz"], act("ln2"), p.grad(pre + "feedforward.model.0.weight"), db=p.grad(pre + "feedforward.model.0.bias"))
             ops.gemm_nt(ws["dz"], p.w16t(pre + "feedforward.model.0.weight"), ws["dln"])
             wait(w_dx2)
-            ops.layernorm_bwd(ws["dln"], ws[f"xmid{l}"], st2[0], st2[1], p.f32(pre + "feedforward_layernorm.weight"), dx2,
+            ops.layernorm_bwd(ws["dln"], act("xmid"), st2[0], st2[1], p.f32(pre + "feedforward_layernorm.weight"), dx2,
                               p.grad(pre + "feedforward_layernorm.weight"), p.grad(pre + "feedforward_layernorm.bias"), add=dx, det=self._det)
             # attention: xmid = att Wo^T + bo + x
             # dp_a was last read by layer l + 1's out-proj wgrad: wait(w_dx2) above covers it
@@ -1266,11 +1349,12 @@ class Engine:
             if dp[l] is not None:
                 g1 = ws["dp_a"]
                 ops.call("drop_path", dx2, None, dp[l][0], g1, B, Nt * Dv)
-            w_dx2 = wgrad(g1, ws[f"att{l}"], p.grad(pre + "attention.output_proj.weight"), db=p.grad(pre + "attention.output_proj.bias"))
+            w_dx2 = wgrad(g1, act("att"), p.grad(pre + "attention.output_proj.weight"), db=p.grad(pre + "attention.output_proj.bias"))
             ops.gemm_nt(g1, p.w16t(pre + "attention.output_proj.weight"), ws["datt"])
             wait(w_dqkv)
-            ops.attn_bwd(ws[f"qkv{l}"], ws[f"att{l}"], ws["datt"], ws[f"lse{l}"], None, ws["dqkv"], ws["delta"], B, Nt, H)
-            w_dqkv = wgrad(ws["dqkv"], ws[f"ln1_{l}"], p.grad(pre + "attention.input_proj.weight"), db=p.grad(pre + "attention.input_proj.bias"))
+            ops.attn_bwd(act("qkv"), act("att"), ws["datt"], ws[f"lse{l}"], None, ws["dqkv"], ws["delta"], B, Nt, H)
+            w_dqkv = wgrad(ws["dqkv"], act("ln1"), p.grad(pre + "attention.input_proj.weight"), db=p.grad(pre + "attention.input_proj.bias"))
+            w_set[l & 1] = w_dqkv
             ops.gemm_nt(ws["dqkv"], p.w16t(pre + "attention.input_proj.weight"), ws["dln"])
             wait(w_dx)                                       # the FC2 wgrad read dx (or dp_b): done before LayerNorm-backward rewrites dx
                                                              # (and before the next layer rewrites dp_b)

@@ -327,6 +327,25 @@ def layernorm_fwd(x, gamma, beta, y, mean, rstd, eps):
     return y
 
 
+def layernorm_apply(x, mean, rstd, gamma, beta, y):
+    """y = bf16((x - mean) * rstd * gamma + beta) from saved statistics: the y of the LayerNorm forward launch that wrote mean / rstd,
+    bit for bit (medmoe_layernorm_apply; activation recomputation)."""
+    for t, nm in ((x, "x"), (y, "y")):
+        _need(t, torch.bfloat16, nm)
+    for t, nm in ((mean, "mean"), (rstd, "rstd"), (gamma, "gamma"), (beta, "beta")):
+        _need(t, torch.float32, nm)
+    rows, D = x.numel() // x.shape[-1], x.shape[-1]
+    if not x.is_contiguous() or not y.is_contiguous() or y.numel() != x.numel():
+        raise ValueError("layernorm_apply: x / y must be contiguous and equally sized")
+    if D % 8 or D > 2048:
+        raise ValueError(f"layernorm_apply: D must be a multiple of 8 and <= 2048, got {D}")
+    if gamma.numel() != D or beta.numel() != D or mean.numel() != rows or rstd.numel() != rows \
+            or not all(t.is_contiguous() for t in (mean, rstd, gamma, beta)):
+        raise ValueError("layernorm_apply: gamma / beta must hold D contiguous values, mean / rstd one per row")
+    call("layernorm_apply", x, mean, rstd, gamma, beta, y, rows, D)
+    return y
+
+
 def layernorm_bwd(dy, x, mean, rstd, gamma, dx, dgamma=None, dbeta=None, add=None, det: Optional[DetScratch] = None, rows_dev=None):
     """det (deterministic mode): dgamma / dbeta leave as per-workgroup partial rows summed in workgroup order (medmoe_layernorm_bwd_det).
     rows_dev (int32 device tensor of one element): medmoe_layernorm_bwd_rows - the first min(rows, *rows_dev) rows only."""
@@ -652,7 +671,7 @@ _SIGS = {
     "quant_rows_mx": "pipppii", "quant_weights_mx": "pppppiii", "gemm_mx_grouped": "ppppppippppppiiillli",
     "lerp_tokens_fwd": "ppiiii", "lerp_tokens_bwd": "pppiiii", "lerp_tokens_bwd2": "ppppiiii",
     "text_pack": "pppppii", "segment_map": "pippppiiii", "text_aggregate_bwd": "ppppiii", "text_embed_ln_bwd": "pppppppppppiiiif", "text_embed_ln_packed": "ppppppppiiiifpp", "text_aggregate_packed": "ppppipppppiii",
-    "layernorm_fwd_rows": "ppppppiifip", "attn_fwd_varlen": "ppppiiii",
+    "layernorm_fwd_rows": "ppppppiifip", "attn_fwd_varlen": "ppppiiii", "layernorm_apply": "ppppppii",
     "win_attn_fwd": "ppppiiiiii", "win_attn_bwd": "ppppppiiiiii", "patch_merge": "ppiiiii", "drop_path": "ppppil",
     "dropout_mask": "pliillll", "dropout_apply": "ppliillllf", "dropout_add_layernorm_fwd": "ppppppppiifllllf",
     "attn_drop_fwd": "ppppiiiillllf", "attn_drop_bwd": "pppppppiiiillllf",
@@ -768,6 +787,7 @@ _COSTS = {
     "layernorm_bwd_rows": lambda a: ("layernorm_bwd_kernel (rows)", (8.0 if a[5] is not None else 6.0) * (ROWS_HINT or a[9]) * a[10], "byte"),
     "attn_bwd_varlen": lambda a: ("attn_bwd_varlen (attn_bwd_dq_kernel + attn_bwd_dkv_kernel)", None, None),
     "layernorm_fwd_rows": lambda a: ("layernorm_fwd_kernel", 4.0 * (ROWS_HINT or a[6]) * a[7], "byte"),
+    "layernorm_apply": lambda a: ("layernorm_apply_kernel", 4.0 * a[6] * a[7], "byte"),                         # x read, y written
 }
 
 

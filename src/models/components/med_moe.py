@@ -78,6 +78,18 @@ def _vit_drop_path(c: MedMoEConfig, vision: Any) -> MedMoEConfig:
     placeholder there."""
     if _get(vision, "arch", "vit_b16") != "swin_t" or _get(vision, "config_name"):
         c.vit_drop_path = float(_get(vision, "drop_path_rate", 0.0))
+    return _vit_checkpoint(c, vision)
+
+
+def _vit_checkpoint(c: MedMoEConfig, vision: Any) -> MedMoEConfig:
+    """model.model.vision.grad_checkpointing: activation recomputation of the ViT tower (open_clip's --grad-checkpointing).
+    false / absent: none, nothing changes; true: full; "selective" / "full" / "none" by name."""
+    key = _get(vision, "grad_checkpointing", False)
+    mode = "none" if key is None or key is False else "full" if key is True else str(key)
+    if mode != "none" and _get(vision, "arch", "vit_b16") == "swin_t" and not _get(vision, "config_name"):
+        raise NotImplementedError(f"vit_checkpoint={mode!r} (model.model.vision.grad_checkpointing) with vision.arch=swin_t: the recomputation "
+                                  "is built for the engine's ViT tower; the Swin tower runs behind torch autograd and is not covered")
+    c.vit_checkpoint = mode
     return c
 
 
