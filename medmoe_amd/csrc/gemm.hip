@@ -54,8 +54,9 @@ extern int g_attn_resident;      // attention.hip
 extern int g_sa_rows;            // moe.hip
 extern int g_attn_rt13;          // attention.hip
 // Which kernel the most recent medmoe_gemm_nt / _rows / _tiles256 call of this process launched: 0 gemm_nt_kernel (128x128), 1 gemm_nt256_kernel,
-// 2 gemm_nt512_kernel, 3 gemm_nt512_kernel GROUPED, 4 gemm_nt4w_kernel, 5 gemm_nt4w_kernel GROUPED.  Measurement aid only (bench.py labels its
-// per-launch HIP-event timings with it); nothing in the product path reads it.
+// 2 gemm_nt512_kernel, 3 gemm_nt512_kernel GROUPED, 4 gemm_nt4w_kernel, 5 gemm_nt4w_kernel GROUPED, 6 gemm_nt_direct_kernel.  Measurement and
+// test aid only (bench.py labels its per-launch HIP-event timings with it, tests/test_gemm_nt_exact_gpu.py asserts the kernel each of its
+// cases was written for); nothing in the product path reads it.
 static int g_last_nt_kernel = -1;
 extern "C" int medmoe_last_gemm_nt_kernel() { return g_last_nt_kernel; }
 extern int g_ln_one_row;

@@ -190,7 +190,10 @@ def stream_fork(src: int, dst: int):
 
 def set_option(key: int, value: int):
     """medmoe_set_option: kernel-selection switches (1 nt256, 2 nt512, 3 tn512, 4 grouped-wgrad rows, 5 max NT grid,
-    6 scores512, 7 gemm_nt4w, 8 gemm_tn4w, 9 plain-wgrad rows per range) - for tests and measurements; the defaults are the fastest measured."""
+    6 scores512, 7 gemm_nt4w, 8 gemm_tn4w, 9 plain-wgrad rows per range, 10 grouped-wgrad rows per range on gemm_tn4w, 11 resident attention,
+    12 score GEMM without its epilogue (measurement only), 13 scale_attn_bwd rows per wave, 15 attention threads per workgroup at 13 key tiles,
+    16 LayerNorm one row per wave, 17 gemm_nt_direct for K % 64 == 32) - for tests and measurements; the defaults are the fastest measured.
+    The NT GEMM switches: 1, 2, 7 and 17 take 0 / 1 (default 1), 5 takes the largest grid of the 256x256 kernels, 1 .. 256 (default 256)."""
     _chk(load_library().medmoe_set_option(_c.c_int(key), _c.c_int(value)), "set_option")
 
 
