@@ -199,8 +199,21 @@ int medmoe_preprocess(const void* const* src_ptrs, const int* src_hw, void* dst,
 /* the reference's own filter: Pillow BICUBIC resize on uint8 (HF image processor of swin-tiny, swin.py:131), horizontal then vertical
    pass in 22-bit fixed point, then x rescale, (x - mean) / std -> bf16 [B,3,Ho,Wo].  meta[b][9] = {Hs, Ws, ksize_h, ksize_v, offsets of the
    horizontal bounds / weights and vertical bounds / weights in coef, first row of image b in tmp}; tmp: uint8 [total_src_rows][Wo][3];
-   u8_out (may be NULL): the resized uint8 image [B][Ho][Wo][3] before normalisation */
+   u8_out (may be NULL): the resized uint8 image [B][Ho][Wo][3] before normalisation; dst may be NULL when u8_out is not (the resize only) */
 int medmoe_preprocess_bicubic(const void* const* src_ptrs, const long long* meta, const int* coef, void* tmp, void* dst, void* u8_out, int B, int Ho, int Wo, long long total_src_rows, float rescale, const float* mean3, const float* std3, hipStream_t stream);
+
+/* train-time augmentation behind the resize above (the reference's `transformations` block, src/utils/utils.py:16-68): per-sample
+   parameters drawn on the device from the Philox stream of the dropout kernels (site 0x20000000; sample sample0 + b owns the groups
+   4 (sample0 + b) + {0 crop x0, y0, flip, order | 1 angle, tx, ty, scale | 2 brightness, contrast}), then crop -> flip -> nearest-neighbour
+   affine about the crop's centre -> brightness / contrast in pixel space -> (x - mean) / std -> bf16 [B][3][C][C].
+   params[b][16] = {m00 m01 m02 m10 m11 m12, brightness, contrast, order bit, flip bit, angle (degrees), tx, ty, scale, x0, y0}: output pixel
+   (x, y) reads crop pixel (rint(m00 x + m01 y + m02), rint(m10 x + m11 y + m12)), mirrored in x when the flip bit is set, at offset
+   (x0, y0) of the source; outside the crop the pixel is normalised zero.  S: the resized size, C <= S the crop's; train = 0 writes the
+   centre crop and identity everything else; flip_thresh = floor(p 2^32); angle ~ U(d0, d1) degrees, tx = rint(U(-tr_x C, tr_x C)), ty
+   likewise, scale ~ U(s0, s1), brightness ~ U(b0, b1), contrast ~ U(c0, c1).  apply takes any params buffer (the crop box is clamped into
+   the source); mean3 / std3 are HOST arrays; dst must be 16-byte aligned.  Both are pure functions of their inputs (no atomics). */
+int medmoe_augment_params(float* params, int B, long long sample0, long long seed, long long step, int S, int C, int train, unsigned flip_thresh, float d0, float d1, float tr_x, float tr_y, float s0, float s1, float b0, float b1, float c0, float c1, hipStream_t stream);
+int medmoe_augment_apply(const void* src_u8, const float* params, void* dst, int B, int Hs, int Ws, int C, float rescale, const float* mean3, const float* std3, hipStream_t stream);
 
 /* padded geometry (HWp, Tp, Gm row width) the local-loss kernels were instantiated for */
 int medmoe_local_geometry(int HW, int T, int* HWp, int* Tp, int* GW);

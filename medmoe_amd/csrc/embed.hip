@@ -704,7 +704,7 @@ __global__ __launch_bounds__(256) void bicubic_v_kernel(const unsigned char* __r
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       if (u8_out) u8_out[(((long long)b * Ho + yy) * Wo + xx) * 3 + c] = (unsigned char)v[c];
-      dst[(((long long)b * 3 + c) * Ho + yy) * Wo + xx] = f2bf(((float)v[c] * rescale - mean[c]) / sd[c]);      // HF: rescale, then (x - mean) / std
+      if (dst) dst[(((long long)b * 3 + c) * Ho + yy) * Wo + xx] = f2bf(((float)v[c] * rescale - mean[c]) / sd[c]);      // HF: rescale, then (x - mean) / std
     }
   }
 }
@@ -712,7 +712,7 @@ __global__ __launch_bounds__(256) void bicubic_v_kernel(const unsigned char* __r
 extern "C" int medmoe_preprocess_bicubic(const void* const* src_ptrs, const long long* meta, const int* coef, void* tmp, void* dst,
                                          void* u8_out, int B, int Ho, int Wo, long long total_src_rows, float rescale,
                                          const float* mean3, const float* std3, hipStream_t stream) {
-  if (!src_ptrs || !meta || !coef || !tmp || !dst || !mean3 || !std3) return MM_ERR_ARG;
+  if (!src_ptrs || !meta || !coef || !tmp || (!dst && !u8_out) || !mean3 || !std3) return MM_ERR_ARG;      // dst NULL: the uint8 image only
   if (B <= 0 || Ho <= 0 || Wo <= 0 || total_src_rows <= 0) return MM_ERR_SHAPE;
   for (int c = 0; c < 3; ++c) if (!(std3[c] > 0.f)) return MM_ERR_ARG;
   const long long n1 = total_src_rows * Wo, n2 = (long long)B * Ho * Wo;

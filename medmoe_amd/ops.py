@@ -485,6 +485,7 @@ def dropout_add_layernorm_fwd(z, residual, gamma, beta, x1, y, mean, rstd, eps, 
 # stochastic depth of the image tower: site DROPOUT_SITE_VIT_DROP_PATH + 2 * layer + {0 attention branch, 1 feed-forward branch},
 # one draw per sample - the keep bit of global sample g is element (0, g) of a one-row mask array
 DROPOUT_SITE_VIT_DROP_PATH = 0x40000000
+DROPOUT_SITE_AUGMENT = 0x20000000      # image augmentation: sample g owns the groups 4 g + {0, 1, 2} of this site
 DROP_PATH_MAX_SITES = 128
 
 
@@ -651,7 +652,7 @@ def lora_merge(W, A, Bw, targets, s):
 
 
 # ---------------------------------------------------------------------------------------------
-# generic caller for the remaining entry points: sig chars  p=pointer(tensor|None) i=int l=int64 f=float d=double
+# generic caller for the remaining entry points: sig chars  p=pointer(tensor|None) i=int l=int64 u=unsigned f=float d=double
 # ---------------------------------------------------------------------------------------------
 _SIGS = {
     "patchify": "ppiiiiii", "patchify_ld": "ppiiiiiii", "init_tokens": "pppiii", "pos_cls_grad": "pppiii",
@@ -679,6 +680,8 @@ _SIGS = {
     "dropout_mask": "pliillll", "dropout_apply": "ppliillllf", "dropout_add_layernorm_fwd": "ppppppppiifllllf",
     "attn_drop_fwd": "ppppiiiillllf", "attn_drop_bwd": "pppppppiiiillllf",
     "drop_path_scales": "ppiillll", "scale_add_layernorm_fwd": "pppippppppiif",
+    # image augmentation (csrc/augment.hip); the wrappers live in medmoe_amd/data.py.  mean3 / std3 of augment_apply are host arrays
+    "augment_params": "pillliiiuffffffffff", "augment_apply": "pppiiiifpp",
     "gemm_tn_cols_det": "pipipiiiiilllilpl", "gemm_tn_gram_det": "piplipiiiill", "scale_attn_bwd_det": "ppppppppppiipppppiiipipl",
     "router_bwd_det": "pppppppfpppiiiip", "ce_strided_det": "ppiilliffipp", "soft_xent_strided_det": "pppiillffffipp", "hardneg_strided_det": "ppiillffipp",
     "cos_scale_bwd_det": "ppppppiif",
@@ -694,7 +697,7 @@ _SIGS = {
 }
 
 
-_CTYPES = {"p": _vp, "i": _c.c_int, "l": _c.c_longlong, "d": _c.c_double, "f": _c.c_float}
+_CTYPES = {"p": _vp, "i": _c.c_int, "l": _c.c_longlong, "u": _c.c_uint, "d": _c.c_double, "f": _c.c_float}
 _FN = {}
 
 
@@ -723,7 +726,7 @@ def call(name: str, *args):
                 if not a.is_cuda:
                     _require_gpu(a, "medmoe_" + name)
                 cargs.append(a.data_ptr())
-        elif ch == "i" or ch == "l":
+        elif ch == "i" or ch == "l" or ch == "u":
             cargs.append(int(a))
         else:
             cargs.append(float(a))

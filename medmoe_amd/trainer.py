@@ -103,11 +103,15 @@ class Trainer:
         return None
 
     # ------------------------------------------------------------------------------------------------
-    def _to_device(self, datamodule, module, batch):
+    def _to_device(self, datamodule, module, batch, train: bool):
+        """`train`: the datamodule's `transformations` block augments training batches; validation and test get its centre crop."""
         if hasattr(datamodule, "to_device_batch") and isinstance(batch.get("image"), list):
             dev = next(module.parameters()).device
             size = getattr(getattr(module, "model", None), "cfg", None)
-            return datamodule.to_device_batch(batch, dev, size.img_size if size is not None else 224)
+            size = size.img_size if size is not None else 224
+            if hasattr(datamodule, "device_batch"):
+                return datamodule.device_batch(batch, dev, size, train)
+            return datamodule.to_device_batch(batch, dev, size)
         return batch
 
     def _allreduce_grads(self, params):
@@ -181,7 +185,7 @@ class Trainer:
             for i, batch in enumerate(loader):
                 if self.limit_train_batches is not None and i >= self.limit_train_batches:
                     break
-                dbatch = self._to_device(datamodule, model, batch)
+                dbatch = self._to_device(datamodule, model, batch, True)
                 last_of_epoch = n_batches is not None and i + 1 == n_batches
                 if fused:
                     # micro-batches of an accumulation window: zero the gradient on the first, step on the last (Lightning steps on
@@ -224,7 +228,7 @@ class Trainer:
         for i, batch in enumerate(datamodule.val_dataloader()):
             if self.limit_val_batches is not None and i >= self.limit_val_batches:
                 break
-            b = self._to_device(datamodule, model, batch)
+            b = self._to_device(datamodule, model, batch, False)
             out = step_fn(b, i) if callable(step_fn) else model.model_step(b)
             tot += float(out["loss"]); n += 1
         val = tot / n if n else math.nan

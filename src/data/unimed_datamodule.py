@@ -2,7 +2,9 @@
 methods.  Lightning and webdataset are optional in this image: with `webdataset` importable and shard paths given, the
 loaders read `jpg`/`txt`/`cls` tuples as the reference does (:44-46); otherwise they fall back to the seeded
 SyntheticUnimed set.  `to_device_batch` turns a collated batch into what the MI355X model takes: images preprocessed on the
-GPU (medmoe_amd.data), captions as id / mask tensors."""
+GPU (medmoe_amd.data), captions as id / mask tensors.  `device_batch` is the same with the `transformations` block applied: the
+reference builds its torchvision pipeline from that block (src/utils/utils.py:16-68); here it becomes an AugmentConfig and the
+augmentation runs on the GPU behind the resize (medmoe_amd.data.preprocess_augmented)."""
 from typing import Any, Dict, Optional
 
 import torch
@@ -27,6 +29,12 @@ class UnimedDataModule(_Base):
                  synthetic_size: int = 4096, max_len: int = 77, synthetic_vocab: int = 28996, synthetic_classes: int = 5) -> None:
         super().__init__()
         self.data_dir, self.transformations = data_dir, transformations
+        # the block is read (and refused, naming its key) here, not at the first batch; augment_step counts the TRAINING batches handed
+        # to device_batch and is the `step` of the augmentation's random stream, carried by state_dict()
+        self.augment, self.augment_step = None, 0
+        if transformations is not None:
+            from medmoe_amd.data import AugmentConfig
+            self.augment = AugmentConfig.from_hydra(transformations)
         self.batch_size, self.num_workers, self.pin_memory = batch_size, num_workers, pin_memory
         self.batch_size_per_device = batch_size
         self.collate_fn = collate_fn
@@ -76,7 +84,38 @@ class UnimedDataModule(_Base):
         from medmoe_amd.data import preprocess_images
         imgs = [torch.as_tensor(im).to(device, non_blocking=True).contiguous() for im in batch["image"]]
         image = preprocess_images(imgs, size=size)
+        return UnimedDataModule._with_captions(image, batch, device)
+
+    @staticmethod
+    def _with_captions(image, batch: Dict[str, Any], device) -> Dict[str, Any]:
         ids = torch.stack([torch.as_tensor(c) for c in batch["caption"]]).to(device)
         mask = (ids != 0).long()
         return {"image": image, "ids": ids, "attn_mask": mask, "token_type": torch.zeros_like(ids), "label": batch["label"].to(device),
                 "caption": {"ids": ids, "attn_mask": mask}}
+
+    def device_batch(self, batch: Dict[str, Any], device, size: int = 224, train: bool = True) -> Dict[str, Any]:
+        """to_device_batch with the `transformations` block applied.  No block: to_device_batch itself (the same launches, the same bits).
+        Otherwise the images are resized to `imsize`, augmented (train) or centre-cropped (validation, test) and normalised on the GPU;
+        the parameters of a sample are a function of (transformations.seed, augment_step, global sample index), and augment_step moves
+        once per TRAINING batch, so the micro-batches of an accumulation window draw different parameters and a restored run repeats."""
+        if self.augment is None:
+            return self.to_device_batch(batch, device, size)
+        cfg = self.augment
+        if cfg.out_size != size:
+            key = "data.transformations.random_crop.crop_size" if cfg.crop_size is not None else "data.transformations.imsize"
+            raise ValueError(f"{key} = {cfg.out_size} is the size of the augmented images, but the model's image size is {size}: "
+                             "the two must be equal")
+        from medmoe_amd.data import preprocess_augmented
+        imgs = [torch.as_tensor(im).to(device, non_blocking=True).contiguous() for im in batch["image"]]
+        trainer = getattr(self, "trainer", None)
+        rank = getattr(trainer, "global_rank", 0) if trainer is not None else 0
+        image = preprocess_augmented(imgs, cfg, self.augment_step, sample0=rank * self.batch_size_per_device, train=train)
+        if train:
+            self.augment_step += 1
+        return self._with_captions(image, batch, device)
+
+    def state_dict(self) -> Dict[str, Any]:
+        return {"augment_step": self.augment_step}
+
+    def load_state_dict(self, state_dict: Dict[str, Any]) -> None:
+        self.augment_step = int(state_dict.get("augment_step", 0))
