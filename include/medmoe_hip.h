@@ -435,6 +435,11 @@ int medmoe_lora_bwd_dx(const void* dqkv, int ldq, const void* Bt, const void* At
    (scratch_floats >= medmoe_lora_wgrad_scratch(M, D, n)), added up in a fixed order by a second kernel - no atomics */
 int medmoe_lora_bwd_wgrad(const void* dqkv, int ldq, const void* X, const void* U, const void* dU, float* gA, float* gB, float* scratch, long long scratch_floats, int M, int D, int n, int c0, int c1, int c2, float s, long long seed, long long step, long long site, long long thresh, float scale, hipStream_t stream);
 long long medmoe_lora_wgrad_scratch(int M, int D, int n);
+/* the same sums at the image tower's row counts: a workgroup accumulates over `run` (>= 1) consecutive 256-row chunks before it
+   stores one partial, ceil(chunks / run) partials are added in run order - no atomics, two launches are bit-identical, run = 1 gives the bits
+   of medmoe_lora_bwd_wgrad.  scratch_floats >= medmoe_lora_wgrad_runs_scratch(M, D, n, run) */
+int medmoe_lora_bwd_wgrad_runs(const void* dqkv, int ldq, const void* X, const void* U, const void* dU, float* gA, float* gB, float* scratch, long long scratch_floats, int M, int D, int n, int c0, int c1, int c2, int run, float s, long long seed, long long step, long long site, long long thresh, float scale, hipStream_t stream);
+long long medmoe_lora_wgrad_runs_scratch(int M, int D, int n, int run);
 /* W (bf16 [>= c_t + D rows][ldw], a copy of the fused projection's weight): rows c_t .. c_t + D - 1 = bf16(W + s B_t A_t) */
 int medmoe_lora_merge(void* W, int ldw, const void* A, const void* Bw, int D, int n, int c0, int c1, int c2, float s, hipStream_t stream);
 

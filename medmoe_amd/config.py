@@ -43,6 +43,18 @@ class MedMoEConfig:
     text_lora_alpha: float = 16.0
     text_lora_dropout: float = 0.0
     text_lora_targets: Tuple[str, ...] = ("query", "value")
+    # frozen image tower and LoRA adapters on it (reference configs/model/med-moe.yaml:18-30 vision.freeze_cnn / lora / lora_r / lora_alpha /
+    # lora_dropout, vision_encoder.py:20-36).  freeze_vit: the backbone - embeddings, blocks and the final LayerNorm - keeps no
+    # gradient, Adam state, average or bf16 gradient copy and no per-step launch touches it; the router and the experts train.  vit_lora:
+    # rank-r adapters on the chosen slices of every block's fused q / k / v projection train as well; it implies a frozen base, as peft's
+    # get_peft_model does (`vit_frozen`).  vit_lora_dropout acts on the side path's input (the block's first LayerNorm output), one mask per
+    # layer shared by its targets (site DROPOUT_SITE_VIT_LORA + layer of csrc/philox.h).  Fused step only
+    freeze_vit: bool = False
+    vit_lora: bool = False
+    vit_lora_r: int = 8
+    vit_lora_alpha: float = 16.0
+    vit_lora_dropout: float = 0.0
+    vit_lora_targets: Tuple[str, ...] = ("query", "value")
     # stochastic depth of the image tower (reference TransformerEncoder(drop_path_rate=), transformer.py:45-68, 188-192): in train mode
     # sample b skips the attention / the feed-forward branch of layer l with probability p_l = linspace(0, vit_drop_path, n_layer_v)[l], survivors
     # are scaled by 1 / (1 - p_l); the two branches draw independently.  The keep bits are a function of (dropout_seed, step, site, global sample)
@@ -108,6 +120,11 @@ class MedMoEConfig:
     # at the t-th update.  Engine.ema_weights() / eval_step(ema=True) evaluate on it, checkpoints and exports carry it
     ema_decay: float = 0.0
     ema_warmup: bool = False
+
+    @property
+    def vit_frozen(self) -> bool:
+        """The engine's notion of a frozen image backbone: asked for, or implied by adapters on it."""
+        return bool(self.freeze_vit or self.vit_lora)
 
     @property
     def n_patch(self) -> int:
@@ -189,6 +206,16 @@ class MedMoEConfig:
                 raise NotImplementedError("deterministic with text_lora (text.lora: true): the trainable text path (the local loss' word gradients, "
                                           "the text backward) has no deterministic form yet - a named follow-up (DESIGN 3e); the adapters' own "
                                           "weight gradients are summed in a fixed order already")
+        if not 0.0 <= float(self.vit_lora_dropout) < 1.0:
+            raise ValueError(f"vit_lora_dropout must be in [0, 1), got {self.vit_lora_dropout}")
+        if self.vit_lora:
+            if not 1 <= int(self.vit_lora_r) <= 16:
+                raise ValueError(f"vit_lora_r must be in 1..16 (the side path runs on the 16-wide MFMA), got {self.vit_lora_r}")
+            tg = (self.vit_lora_targets,) if isinstance(self.vit_lora_targets, str) else tuple(self.vit_lora_targets)
+            if not tg or len(set(tg)) != len(tg) or any(t not in ("query", "key", "value") for t in tg):
+                raise ValueError(f"vit_lora_targets must be a non-empty list of distinct names out of query / key / value, got {tg!r}")
+            if not float(self.vit_lora_alpha) > 0.0:
+                raise ValueError(f"vit_lora_alpha must be > 0, got {self.vit_lora_alpha}")
         if self.expert_fp8 and self.expert_mx:
             raise ValueError("expert_fp8 and expert_mx are two formats of the same weights: set one")
         if self.expert_mx and (self.d_v % 32 or self.d_out % 64):

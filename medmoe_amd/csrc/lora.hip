@@ -267,6 +267,89 @@ __global__ __launch_bounds__(256) void lora_bwd_wgrad_kernel(const bf16_t* __res
     }
 }
 
+// The same sums at the image tower's row counts (M = B * n_tok: 200 k rows, 788 chunks): a workgroup walks `run` CONSECUTIVE
+// chunks with the accumulators kept in its registers and stores ONE partial, part[blockIdx.x][t][which][rank][d] - 1 / run of the scratch
+// traffic and of the second kernel's walk.  Rows are still summed in row order inside a run and the runs in run order by the same second
+// kernel: no atomics, two launches give the same bits, and run = 1 gives those of lora_bwd_wgrad_kernel (the same steps in the same order).
+template <int NT, bool DROP>
+__global__ __launch_bounds__(256) void lora_bwd_wgrad_runs_kernel(const bf16_t* __restrict__ dqkv, int ldq, const bf16_t* __restrict__ X,
+                                                                  const bf16_t* __restrict__ U, const bf16_t* __restrict__ dU,
+                                                                  float* __restrict__ part, int M, int D, int run, LoraCols cols, float s,
+                                                                  DropRng rng) {
+  constexpr int PP = NT * LR + 2;
+  __shared__ __attribute__((aligned(16))) bf16_t Qs[NT + 1][32][WG_PITCH];
+  __shared__ __attribute__((aligned(16))) bf16_t Ps[2][32][PP];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int r = lane & 15, g = lane >> 4;
+  const int cb = blockIdx.y * WG_COLS;
+  const long long mbeg = (long long)blockIdx.x * run * WG_ROWS;          // the host checked run >= 1 and sized the grid: mbeg < M
+  const long long mend = mbeg + (long long)run * WG_ROWS < M ? mbeg + (long long)run * WG_ROWS : M;
+  const int gpr = D >> 2;
+  f32x4_t accB[NT][2], accA[NT][2];
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) accB[t][j] = accA[t][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+  for (long long m0 = mbeg; m0 < mend; m0 += 32) {                        // WG_ROWS is a multiple of 32: a step never straddles two chunks
+    __syncthreads();
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int lr = (tid >> 4) + 16 * h, c8 = (tid & 15) * 8;
+      const long long m = m0 + lr;
+      const bool ok = m < mend && cb + c8 < D;
+#pragma unroll
+      for (int q = 0; q <= NT; ++q) {
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (ok) {
+          if (q < NT) v = *(const uint4*)(dqkv + m * ldq + cols.c[q] + cb + c8);
+          else {
+            v = *(const uint4*)(X + m * D + cb + c8);
+            if constexpr (DROP) v = keep8(v, rng, m, gpr, cb + c8);
+          }
+        }
+        uint32_t* dst = (uint32_t*)&Qs[q][lr][c8];
+        dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; dst[3] = v.w;
+      }
+    }
+    for (int i = tid; i < 2 * 32 * NT * 4; i += 256) {
+      const int which = i / (32 * NT * 4), j = i - which * (32 * NT * 4);
+      const int lr = j / (NT * 4), c4 = (j - lr * (NT * 4)) * 4;
+      const long long m = m0 + lr;
+      uint2 v = make_uint2(0, 0);
+      if (m < mend) v = *(const uint2*)((which ? dU : U) + m * (NT * LR) + c4);
+      uint32_t* dst = (uint32_t*)&Ps[which][lr][c4];
+      dst[0] = v.x; dst[1] = v.y;
+    }
+    __syncthreads();
+    uint4 xf[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) xf[j] = lds_col8(&Qs[NT][8 * g][wid * 32 + j * 16 + r], WG_PITCH);
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      const uint4 uf = lds_col8(&Ps[0][8 * g][t * LR + r], PP), df = lds_col8(&Ps[1][8 * g][t * LR + r], PP);
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        accB[t][j] = mfma32(uf, lds_col8(&Qs[t][8 * g][wid * 32 + j * 16 + r], WG_PITCH), accB[t][j]);
+        accA[t][j] = mfma32(df, xf[j], accA[t][j]);
+      }
+    }
+  }
+  const float sa = DROP ? rng.scale : 1.f;
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int d = cb + wid * 32 + j * 16 + r;
+      if (d >= D) continue;
+      float* pb = part + (((long long)blockIdx.x * NT + t) * 2) * LR * D + d;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        pb[(long long)(4 * g + e) * D] = s * accB[t][j][e];
+        pb[(long long)(LR + 4 * g + e) * D] = sa * accA[t][j][e];
+      }
+    }
+}
+
 // gA[t*16 + rank][d] += sum over chunks (chunk order) of part[chunk][t][1][rank][d];  gB[t*D + d][rank] += ... of part[chunk][t][0][rank][d]
 __global__ __launch_bounds__(256) void lora_wgrad_reduce_kernel(const float* __restrict__ part, int nchunk, int NT, int D, float* __restrict__ gA,
                                                                 float* __restrict__ gB) {
@@ -409,6 +492,35 @@ extern "C" int medmoe_lora_bwd_wgrad_rows(const void* dqkv, int ldq, const void*
   if (!rows_dev) return MM_ERR_ARG;
   return lora_bwd_wgrad_impl(dqkv, ldq, X, U, dU, gA, gB, scratch, scratch_floats, M, D, n, c0, c1, c2, s, seed, step, site, thresh, scale, rows_dev,
                              stream);
+}
+
+// the image tower's form: one partial per `run` consecutive 256-row chunks.  scratch: medmoe_lora_wgrad_runs_scratch floats
+extern "C" long long medmoe_lora_wgrad_runs_scratch(int M, int D, int n, int run) {
+  if (M <= 0 || D <= 0 || n < 1 || n > 3 || run < 1) return 0;
+  const long long nchunk = ((long long)M + WG_ROWS - 1) / WG_ROWS;
+  return ((nchunk + run - 1) / run) * n * 2 * LR * D;
+}
+
+extern "C" int medmoe_lora_bwd_wgrad_runs(const void* dqkv, int ldq, const void* X, const void* U, const void* dU, float* gA, float* gB,
+                                          float* scratch, long long scratch_floats, int M, int D, int n, int c0, int c1, int c2, int run,
+                                          float s, long long seed, long long step, long long site, long long thresh, float scale,
+                                          hipStream_t stream) {
+  if (!dqkv || !X || !U || !dU || !gA || !gB || !scratch) return MM_ERR_ARG;
+  if (run < 1) return MM_ERR_SHAPE;
+  LoraCols cols;
+  if (int rc = lora_check(ldq, M, D, n, c0, c1, c2, &cols)) return rc;
+  if (scratch_floats < medmoe_lora_wgrad_runs_scratch(M, D, n, run)) return MM_ERR_SHAPE;
+  const DropRng rng = make_drop_rng(seed, step, site, thresh, scale);
+  const long long nchunk = ((long long)M + WG_ROWS - 1) / WG_ROWS;
+  const int nrun = (int)((nchunk + run - 1) / run);
+  const dim3 grid((unsigned)nrun, (unsigned)((D + WG_COLS - 1) / WG_COLS));
+  LORA_DISPATCH(lora_bwd_wgrad_runs_kernel, grid, (const bf16_t*)dqkv, ldq, (const bf16_t*)X, (const bf16_t*)U, (const bf16_t*)dU, scratch, M, D,
+                run, cols, s, rng);
+  if (int rc = mm_check_launch()) return rc;
+  const long long total = (long long)n * 2 * LR * D;
+  hipLaunchKernelGGL(lora_wgrad_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, (const float*)scratch, nrun, n, D, gA,
+                     gB);
+  return mm_check_launch();
 }
 
 extern "C" int medmoe_lora_merge(void* W, int ldw, const void* A, const void* Bw, int D, int n, int c0, int c1, int c2, float s,

@@ -13,6 +13,7 @@
 //              branch}; ONE draw per sample: the keep bit of global sample g is element (row 0, column g) of a [1][cols_padded] array
 //   image augmentation (augment.hip): site = DROPOUT_SITE_AUGMENT; global sample g owns the groups 4 g + {0 crop / flip / order,
 //              1 affine, 2 colour jitter}, whose words are turned into integers and uniform floats there
+//   LoRA adapters on the image tower: site = DROPOUT_SITE_VIT_LORA + layer, over the [B * n_tok][d_v] array of the layer's ln1
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -20,6 +21,7 @@
 #define DROPOUT_SITE_EMBED 0xffffffffu
 #define DROPOUT_SITE_VIT_DROP_PATH 0x40000000u
 #define DROPOUT_SITE_AUGMENT 0x20000000u
+#define DROPOUT_SITE_VIT_LORA 0x50000000u
 
 struct DropRng {
   uint32_t k0, k1;      // the two halves of the seed

@@ -237,6 +237,19 @@ class Engine:
         self.set_deterministic(cfg.deterministic or os.environ.get("MEDMOE_DETERMINISTIC", "0") == "1")
         torch.cuda.set_device(self.device)
         self.params = ParamStore(cfg, self.device, seed)
+        # frozen image backbone (cfg.freeze_vit, or implied by cfg.vit_lora): ParamStore keeps gradient / Adam / average buffers
+        # for the router and the experts only, _vit_backward runs no tower weight gradient.  vit_lora: rank-r adapters on slices of every
+        # block's fused q / k / v projection train in an arena of their own - the text adapters' class and launches.  Their dropout
+        # (cfg.vit_lora_dropout) acts in the passes of train_step only: _vit_lora_drop_step is the step whose masks a pass applies, None
+        # everywhere else (eval_step, a bare forward_image and the exports apply the adapters without dropout)
+        self.vit_frozen = cfg.vit_frozen
+        self.vlora = None
+        self._vit_lora_drop_step: Optional[int] = None
+        if cfg.vit_lora:
+            if cfg.vit_lora_dropout > 0.0:
+                self._refuse_with_graph("vit_lora_dropout", "model.model.vision.lora_dropout")
+            from .text_lora import LoraStore
+            self.vlora = LoraStore.for_vit(cfg, self.device, seed)
         self.vocab = vocab or VocabTables.synthetic(cfg.vocab, self.device)
         self.B = 0
         self.ws: Dict[str, torch.Tensor] = {}
@@ -273,7 +286,7 @@ class Engine:
             if cfg.text_lora_dropout > 0.0:
                 self._refuse_with_graph("text_lora_dropout", "model.model.text.lora_dropout")
             from .text_lora import LoraStore
-            self.lora = LoraStore(cfg, self.device, seed)
+            self.lora = LoraStore.for_text(cfg, self.device, seed)
             self.refresh_text_base()
         elif self.train_text:
             from .text_params import TextStore
@@ -311,9 +324,11 @@ class Engine:
         # region columns stored per (word, image) in the transposed pair matrices (MEDMOE_PAIR_PITCH, for A/B runs; default HWp)
         self.HWq = int(os.environ.get("MEDMOE_PAIR_PITCH", self.HWp))
         # gradient buckets in flat-buffer order: [embeddings | layer 0 | ... | layer L-1 | final LN + router + experts]
+        # (a frozen backbone: ONE bucket, the router and the experts - indices of the gradient buffer, which then holds that tail only)
         off = self.params.offsets
         self.bucket_bounds = [0] + [off[f"vit.layer.{l}.attention_layernorm.weight"] for l in range(cfg.n_layer_v)] \
             + [off["vit.final_layer_norm.weight"], self.params.numel]
+        self.bucket_bounds = self.params.grad_bounds(self.bucket_bounds)
         if any(b % 8 for b in self.bucket_bounds):                  # FlatArena.pack moves 16 bytes per lane from a bucket's first element on
             raise ValueError(f"gradient bucket offsets {self.bucket_bounds} must be multiples of 8 elements (a bucket starts inside an arena "
                              "group, whose members are stored without padding?)")
@@ -341,7 +356,40 @@ class Engine:
         out = {"vit": self.params}
         if self.text_arena() is not None:
             out["text"] = self.text_arena()
+        if self.vlora is not None:
+            out["vit_lora"] = self.vlora
         return out
+
+    def merged_image_params(self) -> Dict[str, torch.Tensor]:
+        """The image tower + MoE under their reference-style names (ParamStore.export_named: fp32 CPU tensors) with the adapters merged
+        into the fused projections: W_t <- bf16(W_t + s B_t A_t) (medmoe_lora_merge on a copy of the bf16 working weight).  For export, and
+        for evaluation on a plain engine (`params.load_named`)."""
+        if self.vlora is None:
+            raise RuntimeError("merged_image_params: this engine has no adapters on the image tower (cfg.vit_lora)")
+        lo, out = self.vlora, self.params.export_named()
+        for l in range(self.cfg.n_layer_v):
+            name = f"vit.layer.{l}.attention.input_proj.weight"
+            w = ops.lora_merge(self.params.w16(name).clone(), lo.A16(l), lo.B16(l), lo.targets, lo.scale)
+            out[name] = w.float().cpu()
+        return out
+
+    def _vit_lora_rng(self, l: int):
+        """The generator of layer l's adapter dropout under the masks of the current training pass; None: the pass drops nothing."""
+        if self._vit_lora_drop_step is None:
+            return None
+        return ops.dropout_rng(self.cfg.dropout_seed, self._vit_lora_drop_step, ops.DROPOUT_SITE_VIT_LORA + l, self.cfg.vit_lora_dropout)
+
+    # The adapter weight-gradient launch keeps accumulating over `run` 256-row chunks per workgroup (medmoe_lora_bwd_wgrad_runs).  Measured
+    # on one MI355X at D = 768, two targets (tools/bench_vit_lora.py --sweep, profiles/r19_notes.md): M = 201 728 (cfg2, batch 1024) run 1 /
+    # 2 / 4 / 8 / 16 = 542 / 380 / 258 / 327 / 558 us, M = 25 216 (batch 128) 62 / 73 / 117 / 217 / 424 us - a workgroup's time grows with
+    # its run, so a longer run pays only while the grid still holds about four workgroups per CU: the largest such run, else 1
+    @staticmethod
+    def vit_lora_wgrad_run(M: int, D: int) -> int:
+        groups = ((M + 255) // 256, (D + 127) // 128)
+        for run in (16, 8, 4, 2):
+            if ((groups[0] + run - 1) // run) * groups[1] >= 4 * 256:
+                return run
+        return 1
 
     def text_arena(self):
         """The arena the text side trains: the whole tower's (freeze_text = False), the LoRA adapters' (text_lora), or None (frozen)."""
@@ -492,6 +540,12 @@ class Engine:
         # backward scratch
         buf("dxa", (M, Dv)); buf("dxb", (M, Dv)); buf("dln", (M, Dv)); buf("dqkv", (M, 3 * Dv)); buf("datt", (M, Dv))
         buf("dz", (M, c.ff_v)); buf("delta", (B * H * Nt,), F32)
+        if self.vlora is not None:    # the adapters' U = dropout(ln1) A^T per layer (bf16, 16 per target: the backward reads it), one d U, the wgrad partials
+            nt = len(self.vlora.targets)
+            for l in range(L):
+                buf(f"v_lu{l}", (M, nt * ops.LORA_RANK_PAD))
+            self._vlora_run = self.vit_lora_wgrad_run(M, Dv)
+            buf("v_ldu", (M, nt * ops.LORA_RANK_PAD)); buf("v_lsc", (ops.lora_wgrad_runs_scratch(M, Dv, nt, self._vlora_run),), F32)
         if c.vit_drop_path > 0.0:
             # the scales of a step; dp_a: a branch's GEMM output before its scale + residual + LayerNorm launch (forward), the scaled out-proj
             # gradient (backward); dp_b: the scaled FC2 gradient.  Two gradient copies: the side stream's FC2 wgrad may still read one while
@@ -664,6 +718,9 @@ class Engine:
         if not recompute or self.vit_checkpoint == "full":
             ops.gemm_nt(act("ln1"), p.w16(pre + "attention.input_proj.weight"), act("qkv"),
                         bias=p.f32(pre + "attention.input_proj.bias"))
+            if self.vlora is not None:   # qkv[:, target columns] += s (dropout(ln1) A^T) B^T, U kept for the backward: one launch.  A "full"
+                lo = self.vlora          # recomputation runs it again under the same mask: the same bits
+                ops.lora_fwd(act("ln1"), lo.A16(l), lo.B16(l), ws[f"v_lu{l}"], act("qkv"), lo.targets, lo.scale, self._vit_lora_rng(l))
             ops.attn_fwd(act("qkv"), act("att"), ws[f"lse{l}"], None, B, Nt, H)
             if dp_l is None:
                 ops.gemm_nt(act("att"), p.w16(pre + "attention.output_proj.weight"), act("xmid"),
@@ -1186,9 +1243,18 @@ class Engine:
         B, P, Nt, Dv = self.B, c.n_patch, c.n_tok_v, c.d_v
         self._wgrad_begin()
         w_moe = self._moe_backward(labels, loss_scale, dprobs_ext)
+        if self.vit_frozen and self.vlora is None:
+            # freeze_vit without adapters: the router's and the experts' gradients are complete here, and nothing in or under the tower
+            # has a gradient anyone reads - the tower's backward is not run at all
+            self._wait(w_moe)
+            if bucket_ready is not None:
+                bucket_ready(0)
+            return
         # ---- mean-pool backward: the router-input gradient onto every patch token of the final LayerNorm's output ----
         ops.call("broadcast_tokens", ws["drouter_in"], ws["dln"], B, Nt, Dv, 1, P, 1.0 / P)
         w_last = self._vit_backward(w_moe, bucket_ready)
+        if self.vit_frozen:              # no patch-embedding, class-token or position-embedding backward; _vit_backward joined the second stream
+            return
         # ---- embeddings backward ----
         dx = ws["dxa"]
         ops.call("pos_cls_grad", dx, p.grad("vit.pos_embed"), p.grad("vit.cls_token"), B, Nt, Dv)
@@ -1299,16 +1365,30 @@ class Engine:
     def _vit_backward(self, w_moe=None, bucket_ready=None, stage_grads: bool = True):
         """Final LayerNorm + the pre-norm blocks backward: ws["dln"] (gradient w.r.t. the final LayerNorm's output) -> ws["dxa"]
         (gradient w.r.t. ws["x0"]) and every block weight gradient; `stage_grads`: add the experts' stage-feature gradients ws["dF"]
-        at the tapped layers.  Returns the event of the last wgrad on the second stream.  Call _wgrad_begin() first."""
+        at the tapped layers.  Returns the event of the last wgrad on the second stream.  Call _wgrad_begin() first.
+        Frozen backbone with adapters: the same chain of dgrad GEMMs, LayerNorm and attention backwards WITHOUT any tower
+        parameter gradient - the gradient targets are None, which skips the weight-gradient GEMMs and the LayerNorm gamma / beta sums.
+        Per layer, after the attention backward has written d qkv: medmoe_lora_bwd_dx (d U, and the adapters' term of d ln1 added into
+        the base dgrad GEMM's output) and medmoe_lora_bwd_wgrad_runs (the adapters' gradients, += into their arena).  At layer 0 nothing
+        below trains: the dgrad GEMM, the d ln1 term and the first LayerNorm's backward are skipped, and ws["dxa"] is not written.  The one
+        bucket of the image arena (router + experts) is reported once the experts' weight gradients are final."""
         c, p, ws = self.cfg, self.params, self.ws
         B = self.B
         k, Dv, P, Nt, H = c.top_k, c.d_v, c.n_patch, c.n_tok_v, c.n_head_v
-        wgrad, wait = self._wgrad, self._wait
+        wait = self._wait
+        fz, lo = self.vit_frozen, self.vlora
+        grad = (lambda name: None) if fz else p.grad
+        wgrad = (lambda *a, **kw: None) if fz else self._wgrad     # no gradient target: no launch
         L = c.n_layer_v
         dx, dx2 = ws["dxa"], ws["dxb"]
         ops.layernorm_bwd(ws["dln"], ws[f"x{L}"], ws["stf"][0], ws["stf"][1], p.f32("vit.final_layer_norm.weight"), dx,
-                          p.grad("vit.final_layer_norm.weight"), p.grad("vit.final_layer_norm.bias"), det=self._det)
-        if bucket_ready is not None:
+                          grad("vit.final_layer_norm.weight"), grad("vit.final_layer_norm.bias"), det=self._det)
+        if fz:
+            wait(w_moe)                  # nothing else runs on the second stream: this is the join
+            if bucket_ready is not None:
+                bucket_ready(0)          # router + experts: the image arena's only bucket
+            bucket_ready = None
+        elif bucket_ready is not None:
             wait(w_moe)                  # the experts' weight gradients ran on the second stream
             bucket_ready(L + 1)          # final LN + router + experts: complete
         stage_of = {l: s for s, l in enumerate(c.stage_layers())} if stage_grads else {}
@@ -1335,31 +1415,40 @@ class Engine:
             if dp[l] is not None:
                 g2 = ws["dp_b"]
                 ops.call("drop_path", dx, None, dp[l][1], g2, B, Nt * Dv)
-            w_dx = wgrad(g2, act("h"), p.grad(pre + "feedforward.model.2.weight"), db=p.grad(pre + "feedforward.model.2.bias"))
+            w_dx = wgrad(g2, act("h"), grad(pre + "feedforward.model.2.weight"), db=grad(pre + "feedforward.model.2.bias"))
             wait(w_dz)
             ops.gemm_nt(g2, p.w16t(pre + "feedforward.model.2.weight"), ws["dz"], aux=act("z"), epi=ops.EPI_MUL_AUX)
-            w_dz = wgrad(ws["dz"], act("ln2"), p.grad(pre + "feedforward.model.0.weight"), db=p.grad(pre + "feedforward.model.0.bias"))
+            w_dz = wgrad(ws["dz"], act("ln2"), grad(pre + "feedforward.model.0.weight"), db=grad(pre + "feedforward.model.0.bias"))
             ops.gemm_nt(ws["dz"], p.w16t(pre + "feedforward.model.0.weight"), ws["dln"])
             wait(w_dx2)
             ops.layernorm_bwd(ws["dln"], act("xmid"), st2[0], st2[1], p.f32(pre + "feedforward_layernorm.weight"), dx2,
-                              p.grad(pre + "feedforward_layernorm.weight"), p.grad(pre + "feedforward_layernorm.bias"), add=dx, det=self._det)
+                              grad(pre + "feedforward_layernorm.weight"), grad(pre + "feedforward_layernorm.bias"), add=dx, det=self._det)
             # attention: xmid = att Wo^T + bo + x
             # dp_a was last read by layer l + 1's out-proj wgrad: wait(w_dx2) above covers it
             g1 = dx2
             if dp[l] is not None:
                 g1 = ws["dp_a"]
                 ops.call("drop_path", dx2, None, dp[l][0], g1, B, Nt * Dv)
-            w_dx2 = wgrad(g1, act("att"), p.grad(pre + "attention.output_proj.weight"), db=p.grad(pre + "attention.output_proj.bias"))
+            w_dx2 = wgrad(g1, act("att"), grad(pre + "attention.output_proj.weight"), db=grad(pre + "attention.output_proj.bias"))
             ops.gemm_nt(g1, p.w16t(pre + "attention.output_proj.weight"), ws["datt"])
             wait(w_dqkv)
             ops.attn_bwd(act("qkv"), act("att"), ws["datt"], ws[f"lse{l}"], None, ws["dqkv"], ws["delta"], B, Nt, H)
-            w_dqkv = wgrad(ws["dqkv"], act("ln1"), p.grad(pre + "attention.input_proj.weight"), db=p.grad(pre + "attention.input_proj.bias"))
+            w_dqkv = wgrad(ws["dqkv"], act("ln1"), grad(pre + "attention.input_proj.weight"), db=grad(pre + "attention.input_proj.bias"))
             w_set[l & 1] = w_dqkv
-            ops.gemm_nt(ws["dqkv"], p.w16t(pre + "attention.input_proj.weight"), ws["dln"])
+            below = not fz or l > 0                          # something that trains reads this layer's input
+            if below:
+                ops.gemm_nt(ws["dqkv"], p.w16t(pre + "attention.input_proj.weight"), ws["dln"])
+            if lo is not None:
+                rng = self._vit_lora_rng(l)
+                ops.lora_bwd_dx(ws["dqkv"], lo.B16t(l), lo.A16t(l), ws["v_ldu"], ws["dln"] if below else None, lo.targets, lo.scale, rng)
+                ops.lora_bwd_wgrad_runs(ws["dqkv"], act("ln1"), ws[f"v_lu{l}"], ws["v_ldu"], lo.gA(l), lo.gB(l), ws["v_lsc"], lo.targets, lo.scale,
+                                        self._vlora_run, rng)
+            if not below:
+                break
             wait(w_dx)                                       # the FC2 wgrad read dx (or dp_b): done before LayerNorm-backward rewrites dx
                                                              # (and before the next layer rewrites dp_b)
             ops.layernorm_bwd(ws["dln"], ws[f"x{l}"], st1[0], st1[1], p.f32(pre + "attention_layernorm.weight"), dx,
-                              p.grad(pre + "attention_layernorm.weight"), p.grad(pre + "attention_layernorm.bias"), add=dx2, det=self._det)
+                              grad(pre + "attention_layernorm.weight"), grad(pre + "attention_layernorm.bias"), add=dx2, det=self._det)
             if bucket_ready is not None:
                 wait(w_dqkv)                                 # the side stream runs in order: its last wgrad of the layer covers all four
                 bucket_ready(l + 1)      # layer l: complete
@@ -1387,11 +1476,14 @@ class Engine:
             self.params.zero_grad()
             if self.train_text:
                 self.text_arena().zero_grad()
-        self._forward_both(batch, training=True)
+            if self.vlora is not None:
+                self.vlora.zero_grad()
         try:
+            self._forward_both(batch, training=True)
             return self._train_step_rest(batch, optimizer, loss_scale)
         finally:
             self.vit_drop_scales = None                             # whatever runs next (evaluation, a bare forward_image) drops nothing
+            self._vit_lora_drop_step = None
 
     def _forward_image_train(self, images: torch.Tensor):
         """forward_image of a training step: with cfg.vit_drop_path > 0 under the stochastic-depth scales of self.dropout_step, drawn here by
@@ -1402,6 +1494,8 @@ class Engine:
             probs = [pl for pl in c.vit_drop_path_rates() for _ in range(2)]
             ops.drop_path_scales(self.ws["vit_dp"], probs, self.B, self.rank * self.B, c.dropout_seed, self.dropout_step)
             self.vit_drop_scales = self.ws["vit_dp"]
+        if self.vlora is not None and c.vit_lora_dropout > 0.0:     # the adapters' masks of this step, for the forward and the backward
+            self._vit_lora_drop_step = self.dropout_step
         self.forward_image(images)
 
     def _train_step_rest(self, batch: Dict[str, torch.Tensor], optimizer: bool, loss_scale: float):
@@ -1426,6 +1520,9 @@ class Engine:
             if self.dist and optimizer:                           # the text tower's gradient: one more all-reduce (not overlapped)
                 from . import dist as D_
                 D_.allreduce_mean_(self.text_arena().g32, comm=self.grad_comm(self.text_arena()))
+        if self.vlora is not None and self.dist and optimizer:    # the image adapters' gradient: one more all-reduce, as the text arena's
+            from . import dist as D_
+            D_.allreduce_mean_(self.vlora.g32, comm=self.grad_comm(self.vlora))
         self.dropout_step += 1                                      # the next call draws new masks (evaluation never advances it)
         if optimizer:
             self.optimizer_step()
@@ -1449,17 +1546,17 @@ class Engine:
         if self._ema_active:
             raise RuntimeError("optimizer_step inside ema_weights(): the working copies hold the averaged weights - evaluate only")
         lr = c.lr if lr is None else lr
-        text_part = text.sumsq() if text is not None else None
+        side = [a for a in (text, self.vlora) if a is not None]     # the arenas next to the image one: ONE clip norm over all of them
+        parts = [a.sumsq() for a in side]
         total = image.sumsq()
-        if text is not None:
-            total.add_(text_part)
+        for part in parts:
+            total.add_(part)
         kw = dict(betas=tuple(c.adam_betas), eps=c.adam_eps, decoupled=c.optimizer == "adamw")
         if c.ema_decay > 0.0:                                       # the same launches in their _ema form: every arena, the same decay arguments
-            ema_.prepare([image] if text is None else [image, text])
+            ema_.prepare([image] + side)
             kw.update(ema_.step_kwargs(c))
-        image.adam_step(total, lr, c.weight_decay, c.clip, **kw)
-        if text is not None:
-            text.adam_step(total, lr, c.weight_decay, c.clip, **kw)
+        for a in [image] + side:
+            a.adam_step(total, lr, c.weight_decay, c.clip, **kw)
 
     # ------------------------------------------------------------------------------------------
     # evaluation (medmoe_module.py:114-134 validation_step / test_step: model_step without a backward)
@@ -1546,6 +1643,8 @@ class Engine:
         def fwd():
             if zero_grad:
                 self.params.zero_grad()
+                if self.vlora is not None:
+                    self.vlora.zero_grad()
             self._forward_both(b)
 
         if st["warm"] < 2:

@@ -39,12 +39,17 @@ def _pad(n: int) -> int:
 
 class FlatArena:
     def __init__(self, device, entries: Sequence[Tuple[str, Tuple[int, ...]]], groups: Sequence[Tuple[str, List[str]]] = (),
-                 gemm: Sequence[Tuple[str, bool]] = ()):
+                 gemm: Sequence[Tuple[str, bool]] = (), train_from: str = None):
         """entries: (name, shape) in storage order.  groups: (alias, member names) - the members are stored first, back to back in that order
         (no padding between them, the group padded as a whole), and `alias` names their concatenation along dim 0; every other entry is
         padded to 8 elements.  gemm: (name or alias, stacked) of the GEMM weights, in the order of their rows in the transpose table: one
         row per 2-D matrix - a stacked [E, r, c] weight gives E rows, any other one row (out, in) ([out, in] or [out, in, 1]; the two forms
-        cannot be told apart from the shape).  Adam's state is allocated on first need (`adam_state`)."""
+        cannot be told apart from the shape).  Adam's state is allocated on first need (`adam_state`).
+        train_from (an entry name; None: the whole arena trains, today's layout and launches bit for bit): everything stored BEFORE that
+        entry is frozen.  `self.train_from` is its offset (a multiple of 8); the master and the working copies still cover the
+        whole arena, but g32, m, v, e32 and g16 are TAIL buffers - they hold [train_from, numel) only, `view` finds an entry in either kind
+        of buffer, and asking for a frozen entry's gradient, moment or average raises.  No per-step launch touches the frozen range: not
+        zero_grad, sumsq, pack, the Adam launch, nor the transposes that follow it."""
         self.device = dev = torch.device(device)
         self.shapes: Dict[str, Tuple[int, ...]] = {n: tuple(s) for n, s in entries}
         member_of = {m for _, ms in groups for m in ms}
@@ -63,12 +68,17 @@ class FlatArena:
             self.shapes[a] = (sum(self.shapes[m][0] for m in ms),) + self.shapes[ms[0]][1:]
             self.offsets[a] = self.offsets[ms[0]]
         self.numel = off
+        self.train_from = 0 if train_from is None else self.offsets[train_from]
+        if self.train_from % _ALIGN or any(o < self.train_from < o + _numel(self.shapes[n]) for n, o in self.offsets.items()):
+            raise ValueError(f"FlatArena: train_from={train_from!r} (offset {self.train_from}) must start an entry at a multiple of {_ALIGN}")
+        self.n_train = off - self.train_from                        # elements of a tail buffer
         self.groups: Dict[str, List[str]] = {a: list(ms) for a, ms in groups}
         self.runs = None                                            # parameter groups: [(end, lr_mult, wd_mult)] in storage order, None = none set
         self._run_table = self._one_run = None                      # the device form of `runs` / of the one-run table ((numel, 1, 1))
         self._views: Dict[tuple, tuple] = {}
         z = lambda dt: torch.zeros(off, device=dev, dtype=dt)
-        self.p32, self.g32, self.p16, self.p16t = z(torch.float32), z(torch.float32), z(torch.bfloat16), z(torch.bfloat16)
+        self.p32, self.p16, self.p16t = z(torch.float32), z(torch.bfloat16), z(torch.bfloat16)
+        self.g32 = torch.zeros(self.n_train, device=dev, dtype=torch.float32)
         rows = []
         self._mat: Dict[str, Tuple[int, ...]] = {}                  # GEMM weight -> its matrix form, (r, c) or (E, r, c)
         for n, stacked in gemm:
@@ -78,6 +88,12 @@ class FlatArena:
             rows += [[o + e * r * c, o + e * r * c, r, c] for e in range(_numel(form[:-2]))]
         self.tr_table = torch.tensor(rows, device=dev, dtype=torch.int64) if rows else None
         self.tr_max_tiles = max(((r[2] + 63) // 64) * ((r[3] + 63) // 64) for r in rows) if rows else 0
+        # what an optimiser step re-derives: the trainable matrices only (the whole table when nothing is frozen)
+        self._tr_step, self._tr_step_tiles = self.tr_table, self.tr_max_tiles
+        if self.train_from:
+            rows = [r for r in rows if r[0] >= self.train_from]
+            self._tr_step = torch.tensor(rows, device=dev, dtype=torch.int64) if rows else None
+            self._tr_step_tiles = max(((r[2] + 63) // 64) * ((r[3] + 63) // 64) for r in rows) if rows else 0
         self.m = self.v = self.normsq = self.norm_scratch = None
         self.step_count = 0
         # bf16 gradient exchange: `g16` (bf16, this layout, allocated on first need) receives pack()'s bf16(g32 * scale) and is
@@ -96,7 +112,14 @@ class FlatArena:
         """`name`'s elements of a flat buffer of this layout, in its own shape or any other of no more elements."""
         shape = self.shapes[name] if shape is None else shape
         o = self.offsets[name]
+        if self.train_from and flat.numel() == self.n_train:        # a tail buffer: g32, m, v, e32, g16
+            o -= self.train_from
+            if o < 0:
+                raise KeyError(f"{name} is frozen (stored before offset {self.train_from}): it has no gradient, Adam state or average")
         return flat[o: o + _numel(shape)].view(shape)
+
+    def is_frozen(self, name) -> bool:
+        return self.offsets[name] < self.train_from
 
     def _cached(self, kind, flat, name, shape=None):
         key = (kind, name)
@@ -111,7 +134,7 @@ class FlatArena:
     def f32(self, name):
         """fp32 view of `name` as the passes read it: of the master - of the average while load_ema() holds (biases, LayerNorms, embeddings
         and the router are read in fp32, not from p16)."""
-        return self.ema(name) if self.ema_loaded else self._cached(0, self.p32, name)
+        return self.ema(name) if self.ema_loaded and not self.is_frozen(name) else self._cached(0, self.p32, name)
 
     def ema(self, name):
         """fp32 view of `name`'s average (enable_ema() first)."""
@@ -140,11 +163,12 @@ class FlatArena:
 
     sync_working_copies = refresh                                   # the stores' earlier name for it: the same method
 
-    def _derive(self, src=None):
+    def _derive(self, src=None, step: bool = False):
         """What follows p16 after every update: the transposed copies, then the store's own derived copies.  `src`: the fp32 buffer p16 was
-        just cast from (None: the master)."""
-        if self.tr_table is not None:
-            ops.call("transpose_many", self.p16, self.p16t, self.tr_table, self.tr_table.shape[0], self.tr_max_tiles)
+        just cast from (None: the master).  step: after an optimiser step or a switch to the average - only what trains changed (restore_master takes the full refresh())."""
+        table, tiles = (self._tr_step, self._tr_step_tiles) if step else (self.tr_table, self.tr_max_tiles)
+        if table is not None:
+            ops.call("transpose_many", self.p16, self.p16t, table, table.shape[0], tiles)
         if src is None:
             self.after_update()
         else:
@@ -161,8 +185,8 @@ class FlatArena:
         if self.ema_loaded:
             raise RuntimeError("FlatArena.enable_ema: the working copies hold the average (restore_master() first)")
         if self.e32 is None:
-            self.e32 = torch.zeros(self.numel, device=self.device, dtype=torch.float32)
-        self.e32.copy_(self.p32)
+            self.e32 = torch.zeros(self.n_train, device=self.device, dtype=torch.float32)
+        self.e32.copy_(self.p32[self.train_from:])
         self.ema_updates = 0
 
     def load_ema(self):
@@ -171,8 +195,8 @@ class FlatArena:
         restore_master() undoes it.  Views of f32() taken BEFORE the call stay views of the master: whoever keeps some asks again."""
         if self.e32 is None:
             raise RuntimeError("FlatArena.load_ema: this arena keeps no average (enable_ema())")
-        ops.call("cast_bf16", self.e32, self.p16, self.numel)
-        self._derive(self.e32)
+        ops.call("cast_bf16", self.e32, self.p16[self.train_from:], self.n_train)
+        self._derive(self.e32, step=True)
         self.ema_loaded = True
 
     def restore_master(self):
@@ -184,12 +208,13 @@ class FlatArena:
     @property
     def g16(self) -> torch.Tensor:
         if self._g16 is None:
-            self._g16 = torch.zeros(self.numel, device=self.device, dtype=torch.bfloat16)
+            self._g16 = torch.zeros(self.n_train, device=self.device, dtype=torch.bfloat16)
         return self._g16
 
     def pack(self, lo: int, hi: int, scale: float):
         """g16[lo:hi] = bf16(g32[lo:hi] * scale) on the current stream (medmoe_grad_pack_bf16; lo a multiple of 8, as every entry's offset
-        is).  g32 is left as it is: the rank-local fp32 sum that accumulation over micro-batches needs."""
+        is).  g32 is left as it is: the rank-local fp32 sum that accumulation over micro-batches needs.  lo / hi index the gradient buffer
+        (with a frozen head: the trainable tail, as `grad_bounds` maps arena offsets)."""
         ops.call("grad_pack_bf16", self.g32[lo:hi], self.g16[lo:hi], hi - lo, scale)
 
     def reduced_grad(self) -> torch.Tensor:
@@ -207,7 +232,7 @@ class FlatArena:
     def adam_state(self):
         """(m, v), allocated with the clip norm's buffers on first need: an arena that is never stepped (the autograd Swin path) holds none."""
         if self.m is None:
-            self.m, self.v = torch.zeros_like(self.p32), torch.zeros_like(self.p32)
+            self.m, self.v = torch.zeros_like(self.g32), torch.zeros_like(self.g32)
             self.normsq = torch.zeros(1, device=self.device, dtype=torch.float32)
             self.norm_scratch = torch.zeros(2049, device=self.device, dtype=torch.float32)   # per-block partials + arrival counter
         return self.m, self.v
@@ -216,14 +241,22 @@ class FlatArena:
         """Sum of squares of the gradient arena, summed in a fixed order (identical on every rank): this arena's share of the clip norm."""
         self.adam_state()
         if self.g16_reduced:                                        # the bf16-reduced gradient: the same sum in the same order, read as bf16
-            ops.call("sumsq_det_bf16", self.g16, self.numel, self.normsq, self.norm_scratch)
+            ops.call("sumsq_det_bf16", self.g16, self.n_train, self.normsq, self.norm_scratch)
         else:
-            ops.call("sumsq_det", self.g32, self.numel, self.normsq, self.norm_scratch)
+            ops.call("sumsq_det", self.g32, self.n_train, self.normsq, self.norm_scratch)
         return self.normsq
 
     # -- parameter groups: contiguous runs of the arena with their own learning-rate and weight-decay multipliers ---------------------------
+    def grad_bounds(self, bounds):
+        """Arena offsets -> indices of the gradient buffer: shifted by train_from, whatever lies in the frozen head dropped (the first
+        bound that survives is 0)."""
+        tf = self.train_from
+        out = [b - tf for b in bounds if b > tf]
+        return ([0] + out) if tf else list(bounds)
+
     def _upload_runs(self, runs):
-        dev = self.device
+        dev, tf = self.device, self.train_from
+        runs = [(r[0] - tf, r[1], r[2]) for r in runs if r[0] > tf]  # the Adam launch sees the trainable tail only
         return (torch.tensor([r[0] for r in runs], device=dev, dtype=torch.int64), torch.tensor([r[1] for r in runs], device=dev, dtype=torch.float32),
                 torch.tensor([r[2] for r in runs], device=dev, dtype=torch.float32))
 
@@ -276,19 +309,21 @@ class FlatArena:
         g, sfx = (self.g16, "_g16") if self.g16_reduced else (self.g32, "")
         if ema_args:
             sfx = "_ema" + sfx
+        tf = self.train_from
+        p32, p16 = (self.p32[tf:], self.p16[tf:]) if tf else (self.p32, self.p16)
         if self.runs is None and not decoupled and (b1, b2) == (0.9, 0.999) and float(eps) == 1e-8:
-            ops.call("adam_step" + sfx, self.p32, g, m, v, self.p16, self.numel, lr, 0.9, 0.999, 1e-8, weight_decay, self.step_count,
+            ops.call("adam_step" + sfx, p32, g, m, v, p16, self.n_train, lr, 0.9, 0.999, 1e-8, weight_decay, self.step_count,
                      normsq_total, clip, grad_scale, *ema_args)
         else:
             if self.runs is None and self._one_run is None:
                 self._one_run = self._upload_runs([(self.numel, 1.0, 1.0)])
             ends, lrm, wdm = self._run_table if self.runs is not None else self._one_run
-            ops.call("adam_groups_step" + sfx, self.p32, g, m, v, self.p16, self.numel, ends, lrm, wdm, ends.numel(), lr, b1, b2, eps,
+            ops.call("adam_groups_step" + sfx, p32, g, m, v, p16, self.n_train, ends, lrm, wdm, ends.numel(), lr, b1, b2, eps,
                      weight_decay, 1 if decoupled else 0, self.step_count, normsq_total, clip, grad_scale, *ema_args)
         if ema_args:
             self.ema_updates += 1
         self.g16_reduced = False
-        self._derive()
+        self._derive(step=True)
 
 
 class FlatStore(FlatArena):

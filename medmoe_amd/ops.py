@@ -564,6 +564,7 @@ def attn_drop_bwd(qkv, out, dout, lse, key_mask, dqkv, delta, B, N, H, rng, head
 LORA_RANK_PAD = 16                   # adapters are stored at rank 16: pad rows of A / pad columns of B are zero and stay zero
 LORA_TARGETS = ("query", "key", "value")
 DROPOUT_SITE_LORA = 3                # + 4 * layer: the fourth site of a layer, one mask shared by the layer's targets
+DROPOUT_SITE_VIT_LORA = 0x50000000   # + layer: the image tower's adapters, clear of every other site of csrc/philox.h
 _NO_DROP = (0, 0, 0, 0, 1.0)
 
 
@@ -641,6 +642,27 @@ def lora_bwd_wgrad(dqkv, x, U, dU, gA, gB, scratch, targets, s, rng=None, rows_d
         call("lora_bwd_wgrad_rows", *a, rows_dev)
 
 
+def lora_wgrad_runs_scratch(M: int, D: int, n: int, run: int) -> int:
+    return _scratch_query("lora_wgrad_runs_scratch", M, D, n, run)
+
+
+def lora_bwd_wgrad_runs(dqkv, x, U, dU, gA, gB, scratch, targets, s, run, rng=None):
+    """lora_bwd_wgrad at the image tower's row counts: a workgroup keeps accumulating over `run` consecutive 256-row chunks
+    before it stores one partial; the partials are summed in run order.  run = 1: the bits of lora_bwd_wgrad."""
+    M, D, n = x.shape[0], x.shape[1], len(targets)
+    _lora_check("lora_bwd_wgrad_runs", M, D, n, U, dqkv=dqkv, x=x, U=U, dU=dU)
+    for t, nm in ((gA, "gA"), (gB, "gB"), (scratch, "scratch")):
+        _need(t, torch.float32, nm)
+    if int(run) != run or run < 1:
+        raise ValueError(f"lora_bwd_wgrad_runs: run must be an integer >= 1, got {run!r}")
+    if gA.numel() != n * LORA_RANK_PAD * D or gB.numel() != gA.numel() or dU.numel() != U.numel() or dqkv.shape[0] != M or dqkv.shape[-1] != 3 * D \
+            or not gA.is_contiguous() or not gB.is_contiguous() or scratch.numel() < lora_wgrad_runs_scratch(M, D, n, int(run)):
+        raise ValueError("lora_bwd_wgrad_runs: gA [n*16, D], gB [n*D, 16] contiguous, dqkv [M, 3D], scratch of lora_wgrad_runs_scratch(M, D, n, run) "
+                         "floats")
+    call("lora_bwd_wgrad_runs", dqkv, dqkv.stride(-2), x, U, dU, gA, gB, scratch, scratch.numel(), M, D, n, *lora_cols(targets, D), int(run), s,
+         *(rng or _NO_DROP))
+
+
 def lora_merge(W, A, Bw, targets, s):
     """W [3D, D] bf16 (a COPY of the fused projection's weight): rows of target t = bf16(W + s B_t A_t)."""
     D, n = W.shape[1], len(targets)
@@ -686,7 +708,8 @@ _SIGS = {
     "router_bwd_det": "pppppppfpppiiiip", "ce_strided_det": "ppiilliffipp", "soft_xent_strided_det": "pppiillffffipp", "hardneg_strided_det": "ppiillffipp",
     "cos_scale_bwd_det": "ppppppiif",
     "sumsq": "plp", "sumsq_det": "plpp", "adam_step": "pppppldddddipff", "adam_groups_step": "ppppplpppidddddiipff", "cast_bf16": "ppl", "transpose_many": "pppii",
-    "lora_fwd": "pppppiiiiiiifllllf", "lora_bwd_dx": "pippppiiiiiifllllf", "lora_bwd_wgrad": "pippppppliiiiiifllllf", "lora_merge": "pippiiiiif",
+    "lora_fwd": "pppppiiiiiiifllllf", "lora_bwd_dx": "pippppiiiiiifllllf", "lora_bwd_wgrad": "pippppppliiiiiifllllf",
+    "lora_bwd_wgrad_runs": "pippppppliiiiiiifllllf", "lora_merge": "pippiiiiif",
     "attn_bwd_varlen": "pppppppiiii", "layernorm_bwd_rows": "pppppppppiip", "text_aggregate_bwd_packed": "ppppppiii",
     "text_embed_ln_bwd_packed": "pppppppppppiiiifpp",
     "lora_fwd_rows": "pppppiiiiiiifllllfp", "lora_bwd_dx_rows": "pippppiiiiiifllllfp", "lora_bwd_wgrad_rows": "pippppppliiiiiifllllfp",
@@ -787,6 +810,7 @@ _COSTS = {
     "lora_fwd": lambda a: ("lora_fwd_kernel", 2.0 * a[6] * (a[7] + 2 * a[8] * a[7] + a[8] * 16), "byte"),
     "lora_bwd_dx": lambda a: ("lora_bwd_dx_kernel", 2.0 * a[6] * (a[8] * a[7] + a[8] * 16 + (2 * a[7] if a[5] is not None else 0)), "byte"),
     "lora_bwd_wgrad": lambda a: ("lora_bwd_wgrad_kernel + lora_wgrad_reduce_kernel", 2.0 * a[9] * (a[11] * a[10] + a[10] + 2 * a[11] * 16), "byte"),
+    "lora_bwd_wgrad_runs": lambda a: ("lora_bwd_wgrad_runs_kernel + lora_wgrad_reduce_kernel", 2.0 * a[9] * (a[11] * a[10] + a[10] + 2 * a[11] * 16), "byte"),
     "lora_fwd_rows": lambda a: ("lora_fwd_kernel (rows)", 2.0 * (ROWS_HINT or a[6]) * (a[7] + 2 * a[8] * a[7] + a[8] * 16), "byte"),
     "lora_bwd_dx_rows": lambda a: ("lora_bwd_dx_kernel (rows)", 2.0 * (ROWS_HINT or a[6]) * (a[8] * a[7] + a[8] * 16 + (2 * a[7] if a[5] is not None else 0)), "byte"),
     "lora_bwd_wgrad_rows": lambda a: ("lora_bwd_wgrad_kernel + lora_wgrad_reduce_kernel (rows)", 2.0 * (ROWS_HINT or a[9]) * (a[11] * a[10] + a[10] + 2 * a[11] * 16), "byte"),

@@ -12,7 +12,8 @@
                   the running ordinal of `encoder.layers.{s}.blocks.{b}.` (Swin; a stage's patch merging has the depth of the stage's last
                   block, as SimMIM assigns it).
 
-Store kinds: "vit" (ParamStore: image tower + MoE), "text" (TextStore), "swin_tower" and "swin_moe" (the two FlatStores of the Swin-T model)."""
+Store kinds: "vit" (ParamStore: image tower + MoE), "text" (TextStore, or the text tower's LoraStore), "vit_lora" (the image tower's LoraStore:
+layer l's adapters get the multipliers of layer l's weights, and the no_decay rules see them as the 2-D weights they are), "swin_tower" and "swin_moe" (the two FlatStores of the Swin-T model)."""
 import re
 from dataclasses import dataclass
 from fnmatch import fnmatchcase
@@ -64,7 +65,7 @@ def depth_of(kind: str, names: Sequence[str]) -> Tuple[Dict[str, int], int]:
         for n in names:
             mt = _VIT_BLOCK.match(n)
             out[n] = int(mt.group(1)) + 1 if mt else (0 if n in ("vit.patch_embed.weight", "vit.patch_embed.bias", "vit.cls_token", "vit.pos_embed") else L + 1)
-    elif kind == "text":
+    elif kind in ("text", "vit_lora"):     # vit_lora: the image tower's adapters (`layer.{l}.`): layer l's adapters have layer l's depth
         L = 1 + max(int(mt.group(1)) for mt in map(_TEXT_BLOCK.match, names) if mt)
         for n in names:
             mt = _TEXT_BLOCK.match(n)

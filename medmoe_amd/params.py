@@ -56,7 +56,10 @@ class ParamStore(FlatArena):
 
         self.kinds = {n: k for n, _, k in self.specs}
         # transpose table: one entry per 2-D matrix (per expert for stacked weights)
-        super().__init__(device, [(n, s) for n, s, _ in self.specs], gemm=[(n, len(s) == 3) for n, s, k in self.specs if k == "wt"])
+        # cfg.freeze_vit / cfg.vit_lora: the backbone - everything stored before the router, the final LayerNorm included, as
+        # under peft - is frozen: no gradient, Adam state, average or bf16 gradient copy over it, and no per-step launch touches it
+        super().__init__(device, [(n, s) for n, s, _ in self.specs], gemm=[(n, len(s) == 3) for n, s, k in self.specs if k == "wt"],
+                         train_from="moe.router.0.weight" if cfg.vit_frozen else None)
         self.adam_state()
         dev = self.device
         # fp8 expert weights (BASELINE configs[4]): e4m3 copies [E,N,K] + transposes [E,K,N] + per-output-channel scales [E,N] of
@@ -188,7 +191,10 @@ class ParamStore(FlatArena):
         flat = self.p32 if flat is None else flat
         c = self.cfg
         out = {}
+        tail = self.train_from and flat.numel() == self.n_train      # a gradient / moment / average buffer of a frozen backbone: the tail's names
         for name in self.shapes:
+            if tail and self.is_frozen(name):
+                continue
             v = self.view(flat, name)
             if name.startswith("moe.proj."):
                 s = int(name.split(".")[2]); leaf = name.split(".")[3]

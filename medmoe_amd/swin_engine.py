@@ -39,6 +39,9 @@ class SwinEngine:
         if getattr(engine, "deterministic", False):
             raise NotImplementedError("deterministic with the Swin-T encoder (vision.arch = swin_t, SwinEngine): the relative-position bias "
                                       "tables' gradients are summed by index_add_ - a named follow-up (DESIGN 3e)")
+        if engine.cfg.vit_frozen:
+            raise NotImplementedError("freeze_vit / vit_lora (vision.freeze_cnn / vision.lora_vit) with the Swin-T encoder (vision.arch = swin_t, "
+                                      "SwinEngine): the frozen backbone and its adapters are built for the engine's ViT tower (DESIGN 3n)")
         self.eng, self.enc, self.cfg = engine, encoder, engine.cfg
         self.device = encoder.dev
         self.train_text = engine.train_text

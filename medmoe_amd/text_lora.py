@@ -1,4 +1,4 @@
-"""LoRA adapters of the text tower (cfg.text_lora; reference configs/model/med-moe.yaml:27-30 names the keys, vision_encoder.py:30-36 sketches
+"""LoRA adapters of a tower's attention projections: the text tower's (cfg.text_lora; reference configs/model/med-moe.yaml:27-30 names the keys, vision_encoder.py:30-36 sketches
 peft's LoraConfig(target_modules=["query", "value"])).  The base tower stays the frozen bf16 dict of `ParamStore.text`; what trains
 is this arena: per layer and target t in (query, key, value) peft's `lora_A` [r, D] and `lora_B` [D, r], the update of the target's slice of
 the fused q / k / v projection being s * B A with s = lora_alpha / r.
@@ -8,7 +8,11 @@ MFMA and the bf16 working copies are its operands as they are.  The pad rows of 
 zero gradient (d U's pad columns are dqkv times B's zero columns, U's pad columns are x times A's zero rows), so Adam and AdamW leave them at
 zero.  A layer's A matrices lie back to back (`layer.{l}.lora_A` = A_cat [n_t * 16, D], one MFMA operand for all targets), so do its B matrices
 (`layer.{l}.lora_B` = [n_t * D, 16]); both are GEMM weights of the arena, so `w16t` holds them transposed - the backward's operands.
-Checkpoints and `export_named` carry the true [r, D] / [D, r] shapes."""
+Checkpoints and `export_named` carry the true [r, D] / [D, r] shapes.
+
+The image tower's adapters (cfg.vit_lora) are the SAME class: `LoraStore.for_vit` builds it from the vit_lora_* keys with D = d_v,
+L = n_layer_v, the export prefix `vit.` and an init stream of its own.  What differs between the towers is data: the prefix, r, alpha, D, L,
+the targets and the stream."""
 import math
 from typing import Dict, List, Tuple
 
@@ -22,11 +26,14 @@ RP = ops.LORA_RANK_PAD
 
 
 class LoraStore(FlatArena):
-    def __init__(self, cfg: MedMoEConfig, device, seed: int = 0):
-        self.cfg = cfg
-        self.r, self.D, self.L = int(cfg.text_lora_r), cfg.d_t, cfg.n_layer_t
-        self.scale = float(cfg.text_lora_alpha) / self.r
-        self.targets: Tuple[str, ...] = tuple(t for t in ops.LORA_TARGETS if t in tuple(cfg.text_lora_targets))     # column order of the fused row
+    def __init__(self, device, prefix: str, r: int, alpha: float, D: int, L: int, targets, init_seed: int):
+        """prefix: what the adapters' names carry outside the arena (`text.` / `vit.`: load_named, export_named); init_seed: the stream A is
+        drawn from."""
+        self.prefix = prefix
+        self.r, self.D, self.L = int(r), int(D), int(L)
+        self.scale = float(alpha) / self.r
+        targets = (targets,) if isinstance(targets, str) else tuple(targets)
+        self.targets: Tuple[str, ...] = tuple(t for t in ops.LORA_TARGETS if t in targets)     # column order of the fused row
         D = self.D
         entries: List[Tuple[str, Tuple[int, ...]]] = []
         groups, gemm = [], []
@@ -39,13 +46,23 @@ class LoraStore(FlatArena):
         super().__init__(device, entries, groups, gemm)
         self.adam_state()
         # peft's init: A Kaiming-uniform with a = sqrt(5) (bound 1 / sqrt(fan_in)), B zero - the adapted tower starts as the base tower
-        g = torch.Generator(device="cpu").manual_seed(int(seed) + 2)
+        g = torch.Generator(device="cpu").manual_seed(int(init_seed))
         bound = 1.0 / math.sqrt(D)
         for l in range(self.L):
             for t in self.targets:
                 a = (torch.rand(self.r, D, generator=g) * 2.0 - 1.0) * bound
                 self.f32(self.name(l, t, "A"))[:self.r].copy_(a.to(self.device))
         self.refresh()
+
+    @classmethod
+    def for_text(cls, cfg: MedMoEConfig, device, seed: int = 0) -> "LoraStore":
+        """cfg.text_lora: the text tower's adapters (stream seed + 2: ParamStore draws the towers from seed and seed + 1)."""
+        return cls(device, "text.", cfg.text_lora_r, cfg.text_lora_alpha, cfg.d_t, cfg.n_layer_t, cfg.text_lora_targets, int(seed) + 2)
+
+    @classmethod
+    def for_vit(cls, cfg: MedMoEConfig, device, seed: int = 0) -> "LoraStore":
+        """cfg.vit_lora: the image tower's adapters (stream seed + 3)."""
+        return cls(device, "vit.", cfg.vit_lora_r, cfg.vit_lora_alpha, cfg.d_v, cfg.n_layer_v, cfg.vit_lora_targets, int(seed) + 3)
 
     @staticmethod
     def name(l: int, t: str, which: str) -> str:
@@ -68,12 +85,12 @@ class LoraStore(FlatArena):
     def gB(self, l): return self.grad(f"layer.{l}.lora_B")
 
     def load_named(self, named: Dict[str, torch.Tensor]):
-        """`text.layer.{l}.attention.{t}.lora_A[.weight]` / `.lora_B[.weight]` entries (true shapes) into the master buffer; entries that are
-        not adapters are left to the caller.  The pad rows / columns stay zero."""
+        """`<prefix>layer.{l}.attention.{t}.lora_A[.weight]` / `.lora_B[.weight]` entries (true shapes) into the master buffer; entries that
+        are not adapters are left to the caller.  The pad rows / columns stay zero."""
         for k, v in named.items():
-            if not k.startswith("text.") or ".lora_" not in k:
+            if not k.startswith(self.prefix) or ".lora_" not in k:
                 continue
-            kk = k[len("text."):]
+            kk = k[len(self.prefix):]
             kk = kk[:-len(".weight")] if kk.endswith(".weight") else kk
             if kk not in self.shapes or kk in self.groups:
                 raise KeyError(f"unknown adapter parameter {k} (targets {self.targets}, {self.L} layers)")
@@ -85,7 +102,7 @@ class LoraStore(FlatArena):
 
     def export_named(self, flat=None) -> Dict[str, torch.Tensor]:
         flat = self.p32 if flat is None else flat
-        return {"text." + n: self.true_view(flat, n).detach().float().cpu().contiguous() for n in self.true_names()}
+        return {self.prefix + n: self.true_view(flat, n).detach().float().cpu().contiguous() for n in self.true_names()}
 
     def pad_is_zero(self, flat=None) -> bool:
         flat = self.p32 if flat is None else flat

@@ -90,6 +90,26 @@ def _vit_checkpoint(c: MedMoEConfig, vision: Any) -> MedMoEConfig:
         raise NotImplementedError(f"vit_checkpoint={mode!r} (model.model.vision.grad_checkpointing) with vision.arch=swin_t: the recomputation "
                                   "is built for the engine's ViT tower; the Swin tower runs behind torch autograd and is not covered")
     c.vit_checkpoint = mode
+    return _vit_lora(c, vision)
+
+
+def _vit_lora(c: MedMoEConfig, vision: Any) -> MedMoEConfig:
+    """model.model.vision.freeze_cnn (the reference's key, med-moe.yaml:50): the ViT backbone is frozen.  model.model.vision.lora_vit: LoRA
+    adapters on the ViT tower's attention projections, parameters from the reference's own lora_r / lora_alpha / lora_dropout (yaml default
+    0.1: counts only with lora_vit) plus lora_targets.  `vision.lora` itself stays rejected (_FIXED): it names peft on the
+    reference's Swin tower.  Absent keys change nothing.  With arch: swin_t both are refused: the Swin tower runs behind torch autograd."""
+    freeze, lora = bool(_get(vision, "freeze_cnn", False)), bool(_get(vision, "lora_vit", False))
+    if (freeze or lora) and _get(vision, "arch", "vit_b16") == "swin_t" and not _get(vision, "config_name"):
+        raise NotImplementedError(f"model.model.vision.{'lora_vit' if lora else 'freeze_cnn'}=true with vision.arch=swin_t: the frozen backbone "
+                                  "and its adapters are built for the engine's ViT tower (DESIGN 3n); adapters on the Swin tower are out of scope")
+    c.freeze_vit, c.vit_lora = freeze, lora
+    if lora:
+        c.vit_lora_r = int(_get(vision, "lora_r", c.vit_lora_r))
+        c.vit_lora_alpha = float(_get(vision, "lora_alpha", c.vit_lora_alpha))
+        c.vit_lora_dropout = float(_get(vision, "lora_dropout", 0.0))
+        tg = _get(vision, "lora_targets", None)
+        if tg is not None:
+            c.vit_lora_targets = (tg,) if isinstance(tg, str) else tuple(str(t) for t in tg)
     return c
 
 
@@ -187,6 +207,10 @@ class MedMoE(nn.Module):
             lo = module.engine.lora
             for n in lo.true_names():
                 state_dict[prefix + "text_encoder." + n + ".weight"] = lo.true_view(lo.p32, n)
+        if module.engine.vlora is not None:                          # vision.lora_vit: true - the same convention under the image encoder's prefix
+            lo = module.engine.vlora
+            for n in lo.true_names():
+                state_dict[prefix + "image_encoder." + lo.prefix + n + ".weight"] = lo.true_view(lo.p32, n)
         return state_dict
 
     def ema_state_dict(self) -> Dict[str, torch.Tensor]:
@@ -211,6 +235,9 @@ class MedMoE(nn.Module):
         if eng.lora is not None:
             for n in eng.lora.true_names():
                 out["text_encoder." + n + ".weight"] = eng.lora.true_view(eng.lora.e32, n).detach().clone()
+        if eng.vlora is not None:
+            for n in eng.vlora.true_names():
+                out["image_encoder." + eng.vlora.prefix + n + ".weight"] = eng.vlora.true_view(eng.vlora.e32, n).detach().clone()
         return out
 
     def _from_reference_keys(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
@@ -225,6 +252,10 @@ class MedMoE(nn.Module):
         if named or text:
             if p.p32.data_ptr() != self.weights.data_ptr():
                 self.refresh_working_copies()                        # re-attach the engine to the parameter's storage first
+            if named and self.engine.vlora is not None:           # vision.lora_vit: true - the adapters into their arena, the rest into the tower
+                lora = {k: named.pop(k) for k in [k for k in named if ".lora_" in k]}
+                if lora:
+                    self.engine.vlora.load_named(lora)
             if named:
                 want = set(p.named_views())
                 got = set(named)
@@ -282,6 +313,10 @@ class MedMoE(nn.Module):
             raise NotImplementedError("vit_drop_path > 0 (model.model.vision.drop_path_rate) trains through the fused step (model.fused_step=true "
                                       "-> Engine.train_step draws the stochastic-depth masks and scales the branch gradients); the torch-autograd "
                                       "mirror runs the tower without drops, which is right for evaluation only")
+        if self.cfg.vit_frozen and torch.is_grad_enabled():
+            raise NotImplementedError("vision.freeze_cnn / vision.lora_vit: true train through the fused step (model.fused_step: true -> "
+                                      "Engine.train_step skips the frozen backbone's gradients and has the adapters' backward); the "
+                                      "torch-autograd mirror hands the whole flat parameter a gradient, which a frozen backbone does not keep")
         self.refresh_working_copies()
         img_g, img_l, probs = _ImageTowerFn.apply(self.weights, images.contiguous(), self.engine)
         B, P, D = img_l.shape

@@ -280,6 +280,8 @@ class MedMoEPretrainingLightningModule(_Base):
         out = {"image": m.engine.params}
         if m.engine.text_arena() is not None:
             out["text"] = m.engine.text_arena()
+        if m.engine.vlora is not None:                               # vision.lora_vit: true - the image adapters' Adam state and average travel too
+            out["vit_lora"] = m.engine.vlora
         return out
 
     def on_save_checkpoint(self, checkpoint: Dict[str, Any]) -> None:
@@ -301,7 +303,7 @@ class MedMoEPretrainingLightningModule(_Base):
         averaged = {name: st for name, st in self._fused_stores().items() if getattr(st, "e32", None) is not None}
         if averaged:
             checkpoint["fused_ema"] = {name: {"updates": int(st.ema_updates), "numel": int(st.e32.numel()),
-                                              "ema": (st.e32 if st.ema_updates else st.p32).detach().cpu().clone()} for name, st in averaged.items()}
+                                              "ema": (st.e32 if st.ema_updates else st.p32[st.train_from:]).detach().cpu().clone()} for name, st in averaged.items()}
         # the text tower's dropout masks are a function of (seed, step, site, element): the step counter resumes where it stopped
         checkpoint["text_dropout_step"] = int(self.model.engine.dropout_step)
 
