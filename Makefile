@@ -30,7 +30,15 @@ check-exchange: tools/pair3_exchange_check.cpp
 	$(CXX) -std=c++17 -O1 -g -fsanitize=thread -pthread $< -o build/pair3_exchange_check
 	build/pair3_exchange_check
 
+# host-only check of the top-K list insert / merge (topk_list.h, shared with retrieval.hip) against std::stable_sort, under the sanitizers
+check-topk: tools/topk_list_check.cpp $(CSRC)/topk_list.h
+	@mkdir -p build
+	$(CXX) -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I$(CSRC) $< -o build/topk_list_check
+	build/topk_list_check
+
+build/retrieval.o: $(CSRC)/topk_list.h
+
 clean:
 	rm -rf build $(LIB)
 
-.PHONY: all clean check-plan check-exchange
+.PHONY: all clean check-plan check-exchange check-topk

@@ -462,6 +462,29 @@ int medmoe_lora_fwd_rows(const void* X, const void* A, const void* Bw, void* U, 
 int medmoe_lora_bwd_dx_rows(const void* dqkv, int ldq, const void* Bt, const void* At, void* dU, void* dy, int M, int D, int n, int c0, int c1, int c2, float s, long long seed, long long step, long long site, long long thresh, float scale, const int* rows_dev, hipStream_t stream);
 int medmoe_lora_bwd_wgrad_rows(const void* dqkv, int ldq, const void* X, const void* U, const void* dU, float* gA, float* gB, float* scratch, long long scratch_floats, int M, int D, int n, int c0, int c1, int c2, float s, long long seed, long long step, long long site, long long thresh, float scale, const int* rows_dev, hipStream_t stream);
 
+/* Retrieval and zero-shot evaluation (csrc/retrieval.hip).
+   y[r] = x[r] / max(|x[r]|_2, eps) over the rows of fp32 [rows][D]; y may be x; a zero row stays zero.  The norm is rounded to fp32 once
+   (its sum of squares runs in double) and the quotient once. */
+int medmoe_l2_normalize(const float* x, float* y, int rows, int D, float eps, hipStream_t stream);
+/* For every row of q (fp32 [Nq][D]) the K best rows of keys (fp32 [Nk][D]) under the total order (score descending, key index ascending);
+   the score is the fp32 dot product, nothing is normalised here.  top_val fp32 [Nq][K], top_idx int32 [Nq][K]; positions past min(K, Nk) hold
+   -inf / -1.  Scores are single v_mfma_f32_16x16x4_f32 chains over D in ascending order (the bits of an fmaf chain), so a score depends on its
+   (query, key) pair alone; the [Nq][Nk] matrix is never stored.  The keys are split into S contiguous chunks (grid = query tiles x S); with
+   S > 1 the partial lists go to `scratch` (scratch_elems >= medmoe_sim_topk_scratch(Nq, Nk, D, K)) and a second launch merges them.  The
+   result does not depend on S, bit for bit; no atomics, two launches give the same bits.  A NaN score is never listed.
+   1 <= K <= 16, D % 64 == 0; anything else returns -2 before a launch. */
+int medmoe_sim_topk(const float* q, const float* keys, int Nq, int Nk, int D, int K, float* top_val, int* top_idx, float* scratch, long long scratch_elems, hipStream_t stream);
+/* scratch elements (4 bytes each) of medmoe_sim_topk at the current split setting, 0 when no scratch is needed; medmoe_sim_rank needs no
+   more than medmoe_sim_topk_scratch(Nq, Nk, D, 1) */
+long long medmoe_sim_topk_scratch(int Nq, int Nk, int D, int K);
+/* tests: key splits S of medmoe_sim_topk / medmoe_sim_rank (0 = automatic, at most 64) */
+int medmoe_sim_topk_splits(int n);
+/* rank[i] (int32) = the number of keys ordered before keys[target[i]] for query i under the order of medmoe_sim_topk:
+   #{j : s_ij > s_it} + #{j < t : s_ij == s_it}.  The same main loop as medmoe_sim_topk with a counting epilogue; the target's score is the
+   diagonal of a gathered tile run through that loop, so an exact duplicate of the target row compares equal.  Per-split counts are summed as
+   integers.  A target outside [0, Nk) is scored as a zero row (no fault, the count is meaningless).  D % 64 == 0, else -2 before a launch. */
+int medmoe_sim_rank(const float* q, const float* keys, const int* target, int Nq, int Nk, int D, int* rank, float* scratch, long long scratch_elems, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

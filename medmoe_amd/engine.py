@@ -1581,6 +1581,38 @@ class Engine:
         ops.call("router_eval", self.ws["probs"], batch["label"].to(I32).contiguous(), self.ws["loss_parts"], B, c.n_expert)
         return self._step_result(None)
 
+    # -- embeddings without a loss (retrieval and zero-shot evaluation) ---------------------------------------------------------
+    def embed(self, batch: Dict[str, torch.Tensor], ema: bool = False):
+        """(img_g, txt_g): the global image and sentence embeddings of a batch, fp32 [B, d_out] VIEWS of ws["img_g"] / ws["txt_g"], valid until
+        the next engine call.  The forward launches of `eval_step` and nothing after them: no loss, and no parameter, gradient, Adam or EMA
+        buffer is written.  ema=True: on the averaged weights (inside ema_weights()), as eval_step(ema=True)."""
+        if ema and not self._ema_active:
+            with self.ema_weights():
+                return self.embed(batch)
+        self._alloc(batch["image"].shape[0])
+        self.prefetch_cap_lens(batch["ids"])
+        self._forward_both(batch)
+        return self.ws["img_g"], self.ws["txt_g"]
+
+    def embed_image(self, images: torch.Tensor, ema: bool = False):
+        """The image half of `embed` alone: fp32 [B, d_out] view of ws["img_g"], valid until the next engine call."""
+        if ema and not self._ema_active:
+            with self.ema_weights():
+                return self.embed_image(images)
+        self.forward_image(images)
+        return self.ws["img_g"]
+
+    def embed_text(self, ids: torch.Tensor, attn_mask: torch.Tensor, token_type: Optional[torch.Tensor] = None, ema: bool = False):
+        """The text half of `embed` alone - needs no image pass before it (a set of class prompts has none): fp32 [B, d_out] view of
+        ws["txt_g"], valid until the next engine call."""
+        if ema and not self._ema_active:
+            with self.ema_weights():
+                return self.embed_text(ids, attn_mask, token_type)
+        self._alloc(ids.shape[0])
+        self.prefetch_cap_lens(ids)
+        self.forward_text(ids, attn_mask, token_type)
+        return self.ws["txt_g"]
+
     def _local_loss_eval(self):
         """GLoRIA local loss value (losses.py:961-1026) of ws["img_l"] against ws["words"] into loss_parts[3]; ws["gsim"] is the heads' scratch.
         The transposed object lends medmoe_local_sim_fwd its Gram matrices, tile tables and word norms - its pair matrices are not touched

@@ -717,6 +717,8 @@ _SIGS = {
     # the four optimiser steps with the weight EMA: their sibling's arguments + (ema, one_minus_decay)
     "adam_step_ema": "pppppldddddipffpf", "adam_groups_step_ema": "ppppplpppidddddiipffpf",
     "adam_step_ema_g16": "pppppldddddipffpf", "adam_groups_step_ema_g16": "ppppplpppidddddiipffpf",
+    # retrieval and zero-shot evaluation (csrc/retrieval.hip)
+    "l2_normalize": "ppiif", "sim_topk": "ppiiiipppl", "sim_rank": "pppiiippl",
 }
 
 
@@ -818,6 +820,9 @@ _COSTS = {
     "attn_bwd_varlen": lambda a: ("attn_bwd_varlen (attn_bwd_dq_kernel + attn_bwd_dkv_kernel)", None, None),
     "layernorm_fwd_rows": lambda a: ("layernorm_fwd_kernel", 4.0 * (ROWS_HINT or a[6]) * a[7], "byte"),
     "layernorm_apply": lambda a: ("layernorm_apply_kernel", 4.0 * a[6] * a[7], "byte"),                         # x read, y written
+    "l2_normalize": lambda a: ("l2_normalize_kernel", 12.0 * a[2] * a[3], "byte"),                              # x read twice, y written
+    "sim_topk": lambda a: ("sim_stream_kernel<D / 64, TOPK> (+ topk_merge_kernel)", 2.0 * a[2] * a[3] * a[4], "flop"),
+    "sim_rank": lambda a: ("sim_stream_kernel<D / 64, RANK> (+ rank_sum_kernel)", 2.0 * a[3] * a[4] * a[5], "flop"),
 }
 
 
@@ -858,3 +863,75 @@ def local_geometry(HW: int, T: int):
     rc = lib.medmoe_local_geometry(_c.c_int(HW), _c.c_int(T), _c.byref(a), _c.byref(b), _c.byref(c))
     _chk(rc, "local_geometry")
     return a.value, b.value, c.value
+
+
+# ---------------------------------------------------------------------------------------------
+# retrieval and zero-shot evaluation (csrc/retrieval.hip)
+# ---------------------------------------------------------------------------------------------
+SIM_TOPK_MAX = 16
+L2_EPS = 1e-8                        # the clamp of medmoe_cos_scale
+
+
+def sim_topk_splits(n: int):
+    """Tests: force the number of key splits of sim_topk / sim_rank (0 = automatic).  The results do not depend on it."""
+    _chk(load_library().medmoe_sim_topk_splits(_c.c_int(n)), "sim_topk_splits")
+
+
+def l2_normalize(x, out=None, eps: float = L2_EPS):
+    """out = x / max(|x|_2, eps) per row of a contiguous fp32 [rows, D] tensor; out may be x (in place), default a new tensor."""
+    _need(x, torch.float32, "x")
+    if x.dim() != 2 or not x.is_contiguous():
+        raise ValueError("l2_normalize: x must be a contiguous [rows, D] tensor")
+    if out is None:
+        out = torch.empty_like(x)
+    _need(out, torch.float32, "out")
+    if out.shape != x.shape or not out.is_contiguous() or out.device != x.device:
+        raise ValueError("l2_normalize: out must be contiguous, shaped like x and on its device")
+    call("l2_normalize", x, out, x.shape[0], x.shape[1], eps)
+    return out
+
+
+def _sim_check(name, q, keys):
+    _need(q, torch.float32, "q"); _need(keys, torch.float32, "keys")
+    if q.dim() != 2 or keys.dim() != 2 or not q.is_contiguous() or not keys.is_contiguous():
+        raise ValueError(f"{name}: q and keys must be contiguous [rows, D] tensors")
+    if q.shape[1] != keys.shape[1]:
+        raise ValueError(f"{name}: q has D = {q.shape[1]}, keys D = {keys.shape[1]}")
+    if q.shape[1] % 64 or q.shape[1] == 0:
+        raise ValueError(f"{name}: D must be a multiple of 64, got {q.shape[1]}")
+    if q.shape[0] == 0 or keys.shape[0] == 0:
+        raise ValueError(f"{name}: q and keys must each hold at least one row")
+    if q.device != keys.device:
+        raise ValueError(f"{name}: q and keys must be on one device")
+    return q.shape[0], keys.shape[0], q.shape[1]
+
+
+def _sim_scratch(Nq, Nk, D, K, device):
+    need = _scratch_query("sim_topk_scratch", Nq, Nk, D, K)
+    return (torch.empty(need, device=device, dtype=torch.float32), need) if need else (None, 0)
+
+
+def sim_topk(q, keys, K: int):
+    """(val fp32 [Nq, K], idx int32 [Nq, K]): the K best rows of `keys` for every row of `q` by fp32 dot product, ordered (score descending,
+    key index ascending); positions past min(K, Nk) hold -inf / -1.  The [Nq, Nk] matrix is never stored.  1 <= K <= 16, D % 64 == 0."""
+    if int(K) != K or not 1 <= K <= SIM_TOPK_MAX:
+        raise ValueError(f"sim_topk: K must be an integer in 1 .. {SIM_TOPK_MAX}, got {K!r}")
+    Nq, Nk, D = _sim_check("sim_topk", q, keys)
+    val = torch.empty(Nq, int(K), device=q.device, dtype=torch.float32)
+    idx = torch.empty(Nq, int(K), device=q.device, dtype=torch.int32)
+    sc, n = _sim_scratch(Nq, Nk, D, int(K), q.device)
+    call("sim_topk", q, keys, Nq, Nk, D, int(K), val, idx, sc, n)
+    return val, idx
+
+
+def sim_rank(q, keys, target):
+    """rank int32 [Nq]: the number of rows of `keys` ordered before keys[target[i]] for query i under sim_topk's order (0 = the target is the
+    best key).  target: int32 [Nq] with values in [0, Nk) - the caller's contract, a value outside it is scored as a zero row."""
+    Nq, Nk, D = _sim_check("sim_rank", q, keys)
+    _need(target, torch.int32, "target")
+    if target.dim() != 1 or target.numel() != Nq or not target.is_contiguous() or target.device != q.device:
+        raise ValueError("sim_rank: target must be a contiguous int32 [Nq] tensor on q's device")
+    rank = torch.empty(Nq, device=q.device, dtype=torch.int32)
+    sc, n = _sim_scratch(Nq, Nk, D, 1, q.device)
+    call("sim_rank", q, keys, target, Nq, Nk, D, rank, sc, n)
+    return rank

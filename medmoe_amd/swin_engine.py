@@ -210,6 +210,17 @@ class SwinEngine:
         ema_.prepare(stores.values())
         return {kind: {n: st.view(st.e32, n).detach().cpu().clone() for n in st.offsets if n not in st.groups} for kind, st in stores.items()}
 
+    def embed(self, batch: Dict[str, torch.Tensor], ema: bool = False):
+        raise NotImplementedError("SwinEngine.embed / embed_image / embed_text: retrieval and zero-shot evaluation run on the ViT Engine "
+                                  "(DESIGN 3o); the Swin-T model evaluates through the module's model_step - embeddings from this engine "
+                                  "are a named follow-up")
+
+    def embed_image(self, images: torch.Tensor, ema: bool = False):
+        self.embed(None)
+
+    def embed_text(self, ids: torch.Tensor, attn_mask: torch.Tensor, token_type=None, ema: bool = False):
+        self.embed(None)
+
     def eval_step(self, batch: Dict[str, torch.Tensor]):
         """Forward + losses without gradients reaching the parameters (validation): the same launch sequence minus the encoder backward."""
         was = self.training

@@ -220,10 +220,17 @@ class Trainer:
     @torch.no_grad()
     def validate(self, model, datamodule, step: str = "validation_step"):
         """Mean `loss` over the validation batches -> val/loss.  A module that defines `validation_step` / `test_step` (the reference's
-        hooks, medmoe_module.py:114-134) is evaluated through them; any other through `model_step`."""
+        hooks, medmoe_module.py:114-134) is evaluated through them; any other through `model_step`.
+        A module that defines `on_validation_epoch_start` / `on_validation_epoch_end` (`on_test_epoch_*` under `test`) has them called
+        around the loop; a dict the end hook returns (the retrieval metrics of `model.retrieval`) is merged into
+        callback_metrics under val/... or test/....  val/loss is computed as before."""
         self._hand_over(model)
         model.eval()
         step_fn = getattr(model, step, None)
+        stage, prefix = ("test", "test/") if step == "test_step" else ("validation", "val/")
+        start_hook, end_hook = getattr(model, f"on_{stage}_epoch_start", None), getattr(model, f"on_{stage}_epoch_end", None)
+        if callable(start_hook):
+            start_hook()
         tot, n = 0.0, 0
         for i, batch in enumerate(datamodule.val_dataloader()):
             if self.limit_val_batches is not None and i >= self.limit_val_batches:
@@ -237,6 +244,9 @@ class Trainer:
             torch.distributed.all_reduce(t)
             val = float(t) / self.world_size
         self.callback_metrics["val/loss"] = val
+        extra = end_hook() if callable(end_hook) else None
+        if isinstance(extra, dict):
+            self.callback_metrics.update({prefix + k: v for k, v in extra.items()})
         return dict(self.callback_metrics)
 
     def test(self, model, datamodule=None, ckpt_path: Optional[str] = None):

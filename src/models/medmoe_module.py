@@ -23,7 +23,7 @@ def _get(cfg: Any, key: str, default=None):
 class MedMoEPretrainingLightningModule(_Base):
     def __init__(self, model: nn.Module, loss: Any, optimizer: Any = None, scheduler: Any = None,
                  compile: bool = False, num_classes: int = 5, fused_step: bool = False, optimizer_groups: Any = None,
-                 grad_comm_dtype: str = "fp32", ema: Any = None):
+                 grad_comm_dtype: str = "fp32", ema: Any = None, retrieval: Any = None):
         """`fused_step` (MI355X build, `model.fused_step` in the config tree): training steps run `Engine.train_step` - the hand-scheduled
         forward / losses / backward with the embedding all-gather, the reduce-scatter of the gathered-key gradients, the per-layer
         gradient all-reduce overlapped with backward and the fused clip + Adam - instead of torch autograd + a torch optimizer.
@@ -37,7 +37,14 @@ class MedMoEPretrainingLightningModule(_Base):
         `ema` (`+model.ema.decay=0.9999 +model.ema.warmup=true +model.ema.validate=true`, fused step only): an exponential moving average
         of every trained weight, kept in fp32 next to the master and updated inside the fused Adam launch (MedMoEConfig.ema_decay /
         ema_warmup); `validate`: validation_step / test_step evaluate on the average.  It travels with the checkpoint
-        (`fused_ema`) and `ema_state_dict()` exports it under the reference's key names."""
+        (`fused_ema`) and `ema_state_dict()` exports it under the reference's key names.
+        `retrieval` (`+model.retrieval.ks=[1,5,10]`, fused step with the ViT towers only): validation / test epochs also report
+        image <-> text retrieval over the whole evaluation set - val/i2t_R@k, val/t2i_R@k, mean and median ranks.  validation_step returns
+        the same loss dict from the same Engine.eval_step call and adds the batch's global embeddings (already in the workspace: no second
+        forward) to a medmoe_amd.retrieval.EmbeddingBank; `on_validation_epoch_start` resets the bank, `on_validation_epoch_end` scores it.
+        `zero_shot` = path of a .pt holding prompt_ids / prompt_mask [C, Pn, T] and class_names: zero-shot accuracy (`zero_shot_ks`,
+        default [1, 5]) of the images against the prompt-ensembled class embeddings, the true class read from batch[`label_key`]
+        (default "label").  With model.ema.validate everything runs on the averaged weights."""
         super().__init__()
         self.model = model
         self.loss_cfg = loss
@@ -73,9 +80,30 @@ class MedMoEPretrainingLightningModule(_Base):
                                       "flat stores and updated inside the fused Adam launch; the autograd path steps a torch optimizer")
         if self._ema_validate and not self._ema_decay > 0.0:
             raise ValueError("model.ema.validate=true needs model.ema.decay > 0: there is no average to validate on")
+        self._retrieval, self._bank, self._zs, self._class_emb = self._retrieval_block(retrieval), None, None, None
         if self.fused_step:
             self.automatic_optimization = False                                  # Lightning: manual optimisation (the engine steps itself)
             self._configure_engine()
+
+    def _retrieval_block(self, retrieval: Any):
+        """The validated `model.retrieval` block (None when absent)."""
+        if retrieval is None:
+            return None
+        r = dict(retrieval)
+        unknown = set(r) - {"ks", "zero_shot", "zero_shot_ks", "label_key"}
+        if unknown:
+            raise KeyError(f"model.retrieval: unknown keys {sorted(unknown)} (ks, zero_shot, zero_shot_ks, label_key)")
+        if not self.fused_step:
+            raise NotImplementedError("model.retrieval needs fused_step=true (model.fused_step=true): the embeddings are read from the HIP "
+                                      "engine's workspace after Engine.eval_step; the autograd path keeps none")
+        if getattr(self.model, "swin", None) is not None:
+            raise NotImplementedError("model.retrieval with vision.arch = swin_t: that model validates through model_step, not Engine.eval_step - "
+                                      "retrieval metrics for the Swin engine are a named follow-up (DESIGN 3o)")
+        ks = tuple(int(k) for k in r.get("ks", (1, 5, 10)))
+        zks = tuple(int(k) for k in r.get("zero_shot_ks", (1, 5)))
+        if not ks or min(ks) < 1 or min(zks or (1,)) < 1:
+            raise ValueError(f"model.retrieval: ks / zero_shot_ks must hold integers >= 1, got {ks} / {zks}")
+        return {"ks": ks, "zero_shot": r.get("zero_shot"), "zero_shot_ks": zks, "label_key": str(r.get("label_key", "label"))}
 
     def forward(self, batch):
         return self.model(batch)
@@ -261,11 +289,65 @@ class MedMoEPretrainingLightningModule(_Base):
     def validation_step(self, batch, batch_idx: int = 0):                                # :114-125
         """The loss dict of a validation batch (`val/loss` is its "loss"): Engine.eval_step in fused mode, `model_step` otherwise."""
         if self.fused_step:
-            return self.fused_eval_step(batch)
+            out = self.fused_eval_step(batch)
+            if self._retrieval is not None:
+                self._bank_add(batch)
+            return out
         return self.model_step(batch)
 
     def test_step(self, batch, batch_idx: int = 0):                                      # :127-134
         return self.validation_step(batch, batch_idx)
+
+    # ---- retrieval / zero-shot metrics of an evaluation epoch (model.retrieval, DESIGN 3o) ----------------------------------------------
+    def _bank_add(self, batch: Dict[str, Any]):
+        """The global embeddings Engine.eval_step has just left in the workspace (on the averaged weights under model.ema.validate) go
+        into the bank, normalised, with the batch's labels."""
+        from medmoe_amd.retrieval import EmbeddingBank
+        eng = self.model.engine
+        if self._bank is None:
+            self._bank = EmbeddingBank(eng.cfg.d_out, eng.device)
+        lab = batch.get(self._retrieval["label_key"]) if isinstance(batch, dict) else None
+        self._bank.add(eng.ws["img_g"], eng.ws["txt_g"], lab if torch.is_tensor(lab) else None)
+
+    def on_validation_epoch_start(self):
+        """Empty the bank; with model.retrieval.zero_shot, embed the class prompts under the weights this epoch validates on."""
+        if self._retrieval is None:
+            return
+        if self._bank is not None:
+            self._bank.reset()
+        path = self._retrieval["zero_shot"]
+        if path:
+            from medmoe_amd.retrieval import class_embeddings
+            if self._zs is None:
+                self._zs = torch.load(str(path), map_location="cpu", weights_only=True)
+                missing = {"prompt_ids", "prompt_mask", "class_names"} - set(self._zs)
+                if missing:
+                    raise KeyError(f"model.retrieval.zero_shot: {path} lacks {sorted(missing)}")
+            eng = self._fused_engine()
+            self._class_emb = class_embeddings(eng, self._zs["prompt_ids"].to(eng.device), self._zs["prompt_mask"].to(eng.device),
+                                               ema=self._ema_validate)
+
+    def on_validation_epoch_end(self):
+        """The epoch's retrieval (and zero-shot) metrics as plain floats; the trainer files them under val/... or test/...."""
+        if self._retrieval is None or self._bank is None:
+            return None
+        from medmoe_amd.retrieval import retrieval_metrics, zero_shot_metrics
+        out = {k: float(v) for k, v in retrieval_metrics(self._bank, self._retrieval["ks"]).items()}
+        if self._class_emb is not None:
+            zs = zero_shot_metrics(self._bank, self._class_emb, ks=self._retrieval["zero_shot_ks"])
+            names = list(self._zs["class_names"])
+            for k, v in zs.items():
+                if torch.is_tensor(v):
+                    out.update({f"{k}/{names[c]}": float(x) for c, x in enumerate(v.tolist())})
+                else:
+                    out[k] = float(v)
+        return out
+
+    def on_test_epoch_start(self):
+        return self.on_validation_epoch_start()
+
+    def on_test_epoch_end(self):
+        return self.on_validation_epoch_end()
 
     # ---- fused mode: the optimiser state lives in the engine's flat stores, not in a torch optimizer -----------------------------------
     def _fused_stores(self) -> Dict[str, Any]:
