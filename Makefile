@@ -9,7 +9,7 @@ FLAGS := --offload-arch=$(ARCH) -O3 -fPIC -std=c++17 -Iinclude -I$(CSRC) -Wno-un
 
 all: $(LIB)
 
-build/%.o: $(CSRC)/%.hip $(CSRC)/common.h $(CSRC)/philox.h $(CSRC)/det_plan.h
+build/%.o: $(CSRC)/%.hip $(wildcard $(CSRC)/*.h)
 	@mkdir -p build
 	$(HIPCC) $(FLAGS) -c $< -o $@
 
@@ -35,8 +35,6 @@ check-topk: tools/topk_list_check.cpp $(CSRC)/topk_list.h
 	@mkdir -p build
 	$(CXX) -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I$(CSRC) $< -o build/topk_list_check
 	build/topk_list_check
-
-build/retrieval.o: $(CSRC)/topk_list.h
 
 clean:
 	rm -rf build $(LIB)

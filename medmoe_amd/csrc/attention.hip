@@ -11,6 +11,7 @@
 // (S^T = K Q^T) so the accumulator registers are already the B operand of the P.V product
 // (sum over the accumulator's row index needs no lane movement; cdna guide section 3).
 #include "common.h"
+#include "options.h"
 
 #define HD 64
 

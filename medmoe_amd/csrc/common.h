@@ -125,13 +125,16 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
   return base + s;
 }
 
-// gemm.hip: the ping-pong score kernel of one caption length class (false: shape not taken, use the loss.hip kernel)
+// functions and variables that only connect the library's translation units: not part of the ABI
+#define MM_HIDDEN __attribute__((visibility("hidden")))
+
+// gemm_scores.hip: the ping-pong score kernel of one caption length class (false: shape not taken, use the loss.hip kernel)
 bool mm_launch_scores512(const void* ctx, const void* words, const int* cap_lens, void* a1, float* lse, int B, int Bc, int HW, int T,
                          int D, const int* cap_list, int n_cap, int ntt, long long col_base, long long ldp, hipStream_t stream);
 
-// launches that took an order-dependent form (medmoe_nondet_launches, defined in gemm.hip): host-side, one add per such launch.  One
+// launches that took an order-dependent form (medmoe_nondet_launches, defined in options.hip): host-side, one add per such launch.  One
 // counter for all the library's translation units (a file-level static could not be shared), hidden: not part of the ABI.
-extern __attribute__((visibility("hidden"))) long long g_mm_nondet;
+MM_HIDDEN extern long long g_mm_nondet;
 
 // dst[c] += rec[first*stride + c] + rec[(first+1)*stride + c] + ... (count records) for the float4 column group `c4` of this thread, summed in
 // a FIXED order whatever finished first: row ty of the 16-row block takes records ty, ty + 16, ..., the 16 rows meet in LDS in row order.

@@ -1,8 +1,9 @@
 // Modality-specialised MoE glue kernels (reference swin.py:11-117): token mean-pool, the
 // router (fixed fp32 operation order => bit-exact top-k indices against the oracle), dispatch
 // tables for the grouped expert GEMMs, the fused scale-attention + combine, and their backward.
-// The expert projections themselves are grouped bf16 MFMA GEMMs (gemm.hip).
+// The expert projections themselves are grouped bf16 MFMA GEMMs (gemm_nt*.hip; wgrads: gemm.hip).
 #include "common.h"
+#include "options.h"
 
 // ---------------------------------------------------------------------------------------------
 // out[b,c] = (1/cnt) * sum_{t=t0}^{t0+cnt-1} x[b,t,c]   (t ascending, fp32; swin.py:137 / :112)

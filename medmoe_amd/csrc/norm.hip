@@ -2,6 +2,7 @@
 // reference normalizations.py:8-19).  One wave per row, 16-byte bf16 loads, values kept
 // in registers between the mean and the variance pass.
 #include "common.h"
+#include "options.h"
 
 #define LN_MAX_CHUNKS 4   // D <= 64 lanes * 8 * 4 = 2048
 int g_ln_one_row = 0;     // medmoe_set_option(16, 1): one row per wave whatever the width (A/B runs)

@@ -2,7 +2,7 @@
 // as local_pair2_kernel in loss.hip, which stays for geometries with more than 224 regions).
 //
 // Input: fp16 LOG2-probabilities lp2 = (S - lse) / ln 2 of the word softmax (a1 = exp2(lp2), S = lp2 ln 2 + lse) from
-// medmoe_local_scores_t (gemm.hip) + the fp32 row log-sum-exps.
+// medmoe_local_scores_t (gemm_scores.hip) + the fp32 row log-sum-exps.
 // Layout: element (row, image b, region hw) of a pair matrix at row*ld + b*bstride + hw, row = row_base + j*TP + t for word t of the
 // class's j-th caption, hw < pw (ld = B*pw, bstride = pw: [word rows][image region columns]; ld = pw, bstride = rows*pw: image-major;
 // pw = 224 for 196 regions makes every 64-byte wave segment 64-byte aligned: with 208 every second row started mid-burst and the tile

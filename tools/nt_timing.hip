@@ -2,7 +2,10 @@
 //   tools/nt_timing.hip -o tools/nt_timing.bin ; ./tools/nt_timing.bin [M N K]
 // Prints, per wave and averaged over blocks, the shader clocks spent in the counted vmcnt waits, at the segment
 // barriers, in the LOAD segments (LDS fragment reads + DMA issue), the MFMA segments and the epilogues.
-#include "../medmoe_amd/csrc/gemm.hip"
+// The NT GEMM files are compiled into this one translation unit (their option variables with them: set directly below).
+#include "../medmoe_amd/csrc/gemm_nt.hip"
+#include "../medmoe_amd/csrc/gemm_nt_ring.hip"
+#include "../medmoe_amd/csrc/gemm_nt4w.hip"
 #include <cstdio>
 #include <cstdlib>
 int main(int argc, char** argv) {
@@ -30,8 +33,8 @@ int main(int argc, char** argv) {
 #ifdef NT_EXPERIMENT
   if (getenv("NT_SKIP")) { int np = atoi(getenv("NT_SKIP")); hipMemcpyToSymbol(HIP_SYMBOL(g_nt_dbg_skip), &np, sizeof np); }
 #endif
-  if (getenv("NT_GRID")) medmoe_set_option(5, atoi(getenv("NT_GRID")));
-  if (getenv("NT_4W")) medmoe_set_option(7, atoi(getenv("NT_4W")));
+  if (getenv("NT_GRID")) g_nt_max_grid = atoi(getenv("NT_GRID"));
+  if (getenv("NT_4W")) g_use_nt4w = atoi(getenv("NT_4W"));
   for (int i = 0; i < 3; ++i) if (run()) { printf("launch failed\n"); return 1; }
   hipDeviceSynchronize();
   unsigned long long z[64] = {0};
