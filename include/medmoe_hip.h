@@ -485,6 +485,30 @@ int medmoe_sim_topk_splits(int n);
    integers.  A target outside [0, Nk) is scored as a zero row (no fault, the count is meaningless).  D % 64 == 0, else -2 before a launch. */
 int medmoe_sim_rank(const float* q, const float* keys, const int* target, int Nq, int Nk, int D, int* rank, float* scratch, long long scratch_elems, hipStream_t stream);
 
+/* Supervised classification (csrc/classify.hip).  A linear head on fp32 features: x [N][D], W [C][D], b [C], z = x W^T + b [N][C].
+   D % 64 == 0, 64 <= D <= 2048, 1 <= C <= 64, N >= 1 - anything else returns -2 before a launch; x, W, dx, the targets and the scratch must be 16-byte aligned.
+   medmoe_cls_head_logits writes z alone (evaluation). */
+int medmoe_cls_head_logits(const float* x, const float* W, const float* b, float* z, int N, int D, int C, hipStream_t stream);
+/* Forward + loss + backward of the head in one call.  task 0, multiclass: targets int32 [N] in [0, C), -1 = the row is not counted; V the
+   counted rows, q_n = (1 - label_smoothing) onehot(y_n) + label_smoothing / C, L = loss_scale / |V| sum_V -sum_c q_nc log softmax(z_n)_c,
+   dz_n = loss_scale / |V| (softmax(z_n) - q_n) on V and 0 elsewhere.  task 1, multilabel: targets int8 [N][C] in {0, 1, -1}, -1 = the
+   element is not counted; K the counted elements, pos_weight fp32 [C] or null (= 1), l = pw_c t softplus(-z) + (1 - t) softplus(z) with
+   softplus(z) = max(z, 0) + log1p(exp(-|z|)), L = loss_scale / |K| sum_K l, dz = loss_scale / |K| ((1 - t) sigmoid(z) - pw_c t sigmoid(-z))
+   on K and 0 elsewhere; label_smoothing is not used.
+   Written: z [N][C]; *loss; counts[0] = |V| or |K|, counted on the device; counts[1] = multiclass: the rows of V whose argmax z (ties: the
+   lowest class) is the target, multilabel: the elements of K with (z > 0) == (t == 1); dx = dz W [N][D] when dx is not null (written, not
+   accumulated).  Accumulated: dW [C][D] += dz^T x, db [C] += sum_n dz.  A count of 0 gives L = 0, dz = 0 and no NaN.
+   No fp32 atomics: the loss is summed from per-row terms in a fixed order (segments of 1024 rows, then the segments), dW / db from per-row-range records in range order (scratch_floats >=
+   medmoe_cls_head_scratch(N, D, C), which also holds dz) - two calls give the same bits.  x is read twice (rows, then dW). */
+int medmoe_cls_head_step(const float* x, const float* W, const float* b, const void* targets, const float* pos_weight, int task, float label_smoothing, float loss_scale, float* z, float* dx, float* dW, float* db, float* loss, int* counts, float* scratch, long long scratch_floats, int N, int D, int C, hipStream_t stream);
+/* scratch floats of medmoe_cls_head_step, 0 for a shape it refuses */
+long long medmoe_cls_head_scratch(int N, int D, int C);
+/* Pair counts of the Mann-Whitney AUROC per class: scores fp32 [N][C] (finite - not checked), targets int8 [N][C] in {0, 1, -1} (-1: the
+   element takes no part; multiclass callers pass one-hot rows), out int64 [C][4] = (n_pos, n_neg, n_less, n_equal) with
+   n_less = #{(i, j) : t_ic = 1, t_jc = 0, s_jc < s_ic} and n_equal the same pairs with s_jc == s_ic.  The negatives stream past tiles of
+   256 positives through LDS, nothing of size [N][N] is stored; the counts are 64-bit integer adds: exact and repeatable. */
+int medmoe_auroc_counts(const float* scores, const signed char* targets, long long* out, int N, int C, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

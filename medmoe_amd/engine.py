@@ -1613,6 +1613,86 @@ class Engine:
         self.forward_text(ids, attn_mask, token_type)
         return self.ws["txt_g"]
 
+    # -- supervised classification on the global image embedding -------------------------------------------------------------
+    def _classify_refuse(self, train_tower: bool):
+        if self.dist:
+            raise NotImplementedError("classify_step / classify_eval under data parallelism (self.dist: WORLD_SIZE > 1, trainer.devices > 1): the "
+                                      "head's gradient has no all-reduce yet - data-parallel classification is a named follow-up (DESIGN 3p)")
+        if train_tower and self.cfg.ema_decay > 0.0:
+            raise NotImplementedError("classify_step(train_tower=True) with cfg.ema_decay > 0 (model.ema.decay): the head keeps no average, so "
+                                      "the towers' averages would pair with an un-averaged head - EMA of the head is a named follow-up (DESIGN 3p)")
+
+    def classify_step(self, batch: Dict[str, torch.Tensor], head, train_tower: bool, optimizer: bool = True, zero_grad: bool = True,
+                      loss_scale: float = 1.0, head_lr: Optional[float] = None):
+        """One supervised step of `head` (medmoe_amd.classify.ClassifierHead) on ws["img_g"] of batch["image"] against batch["label"] (int
+        [B] class indices, or int [B, C] in {0, 1, -1} for a multilabel head; -1 = not counted).  No caption is read, the text tower is not run.
+        train_tower=False, the online linear probe: forward_image in its evaluation form (no drop path, no adapter dropout), the head's
+        fused forward / loss / backward launch, the head's Adam step - not one parameter, gradient, Adam or EMA buffer of the engine's own
+        stores is written, and dropout_step stays.
+        train_tower=True, fine-tuning: the training form of the image pass (drop path, adapter dropout and recomputation as in train_step),
+        the head launch writes d loss / d img_g into ws["d_img_g"], ws["d_img_l"] is zeroed and backward(None) runs unchanged - so a
+        freeze_vit engine fine-tunes MoE + head and a vit_lora engine adapters + MoE + head.  ONE clip norm over the image arena, the
+        adapters and the head, then Adam on each, the head at head_lr (default cfg.lr); dropout_step advances.
+        Gradient accumulation as in train_step: optimizer=False for all but the last micro-batch, zero_grad=False for all but the first,
+        loss_scale = 1 / number of micro-batches.  Always eager.  Returns device scalars: loss, n_valid, n_correct, acc."""
+        self._classify_refuse(train_tower)
+        if self._ema_active:
+            raise RuntimeError("classify_step inside ema_weights(): the working copies hold the averaged weights - evaluate only")
+        c, images = self.cfg, batch["image"]
+        self._alloc(images.shape[0])
+        ws = self.ws
+        lr = c.lr if head_lr is None else float(head_lr)
+        kw = dict(betas=tuple(c.adam_betas), eps=c.adam_eps, decoupled=c.optimizer == "adamw")
+        if not train_tower:
+            self.forward_image(images)
+            if zero_grad:
+                head.store.zero_grad()
+            out = head.step(ws["img_g"], batch["label"], loss_scale)
+            if optimizer:
+                head.adam_step(lr, c.weight_decay, c.clip, **kw)
+            return self._classify_result(out)
+        towers = [self.params] + ([self.vlora] if self.vlora is not None else [])
+        if zero_grad:
+            for a in towers:
+                a.zero_grad()
+            head.store.zero_grad()
+        try:
+            self._forward_image_train(images)
+            out = head.step(ws["img_g"], batch["label"], loss_scale, dfeat=ws["d_img_g"])
+            ws["d_img_l"].zero_()
+            self.backward(None, loss_scale)
+        finally:
+            self.vit_drop_scales = None
+            self._vit_lora_drop_step = None
+        self.dropout_step += 1
+        if optimizer:
+            parts = [a.sumsq() for a in towers[1:] + [head.store]]
+            total = self.params.sumsq()
+            for part in parts:
+                total.add_(part)
+            for a in towers:
+                a.adam_step(total, c.lr, c.weight_decay, c.clip, **kw)
+            head.adam_step(lr, c.weight_decay, c.clip, normsq_total=total, **kw)
+        return self._classify_result(out)
+
+    @staticmethod
+    def _classify_result(out):
+        loss, n_valid, n_correct = out
+        return {"loss": loss, "n_valid": n_valid, "n_correct": n_correct, "acc": n_correct.float() / n_valid.clamp(min=1).float()}
+
+    def classify_eval(self, batch: Dict[str, torch.Tensor], head, ema: bool = False):
+        """(logits, loss dict) of `head` on a batch, forward only: the evaluation form of the image pass, then the head launch with
+        loss_scale 1 into gradient buffers of its own that nobody reads (ClassifierHead.evaluate) - no parameter, gradient or optimiser
+        state of the engine or the head is written.  logits: fp32 [B, C] view of the head's workspace, valid until its next launch.
+        ema=True: the image pass runs on the averaged weights (inside ema_weights()); the head keeps no average."""
+        self._classify_refuse(False)
+        if ema and not self._ema_active:
+            with self.ema_weights():
+                return self.classify_eval(batch, head)
+        self.forward_image(batch["image"])
+        out = head.evaluate(self.ws["img_g"], batch["label"])
+        return head.last_logits, self._classify_result(out)
+
     def _local_loss_eval(self):
         """GLoRIA local loss value (losses.py:961-1026) of ws["img_l"] against ws["words"] into loss_parts[3]; ws["gsim"] is the heads' scratch.
         The transposed object lends medmoe_local_sim_fwd its Gram matrices, tile tables and word norms - its pair matrices are not touched

@@ -719,6 +719,8 @@ _SIGS = {
     "adam_step_ema_g16": "pppppldddddipffpf", "adam_groups_step_ema_g16": "ppppplpppidddddiipffpf",
     # retrieval and zero-shot evaluation (csrc/retrieval.hip)
     "l2_normalize": "ppiif", "sim_topk": "ppiiiipppl", "sim_rank": "pppiiippl",
+    # supervised classification (csrc/classify.hip)
+    "cls_head_logits": "ppppiii", "cls_head_step": "pppppiffpppppppliii", "auroc_counts": "pppii",
 }
 
 
@@ -823,6 +825,11 @@ _COSTS = {
     "l2_normalize": lambda a: ("l2_normalize_kernel", 12.0 * a[2] * a[3], "byte"),                              # x read twice, y written
     "sim_topk": lambda a: ("sim_stream_kernel<D / 64, TOPK> (+ topk_merge_kernel)", 2.0 * a[2] * a[3] * a[4], "flop"),
     "sim_rank": lambda a: ("sim_stream_kernel<D / 64, RANK> (+ rank_sum_kernel)", 2.0 * a[3] * a[4] * a[5], "flop"),
+    "cls_head_logits": lambda a: ("cls_row_kernel<J4, -, false>", 4.0 * a[4] * (a[5] + a[6]), "byte"),                 # x read, z written
+    # x read twice (rows, dW), dx written when asked for, z and dz written, dz read
+    "cls_head_step": lambda a: ("cls_row_kernel<J4, TASK, true> + cls_wgrad_kernel (+ count, sums)",
+                                4.0 * a[16] * ((3 if a[9] is not None else 2) * a[17] + 3 * a[18]), "byte"),
+    "auroc_counts": lambda a: ("auroc_kernel", 2.0 * a[3] * a[3] * a[4], "flop"),                                        # at most N^2 C pairs, two compares each
 }
 
 
@@ -935,3 +942,141 @@ def sim_rank(q, keys, target):
     sc, n = _sim_scratch(Nq, Nk, D, 1, q.device)
     call("sim_rank", q, keys, target, Nq, Nk, D, rank, sc, n)
     return rank
+
+
+# ---------------------------------------------------------------------------------------------
+# supervised classification (csrc/classify.hip)
+# ---------------------------------------------------------------------------------------------
+CLS_TASKS = {"multiclass": 0, "multilabel": 1}
+CLS_MAX_CLASSES = 64
+CLS_MAX_D = 2048
+
+
+def _cls_f32(name, arg, t, shape=None, align=False):
+    """A contiguous fp32 tensor (of `shape`, 16-byte aligned when asked): ValueError naming the argument otherwise."""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+        raise ValueError(f"{name}: {arg} must be an fp32 tensor, got {getattr(t, 'dtype', type(t))}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: {arg} must be contiguous")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: {arg} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+    if align and t.data_ptr() % 16:
+        raise ValueError(f"{name}: {arg} must start at a 16-byte boundary")
+
+
+def _cls_head_check(name, x, W, b):
+    for arg, t in (("x", x), ("W", W), ("b", b)):
+        _cls_f32(name, arg, t, align=arg != "b")
+    if x.dim() != 2 or W.dim() != 2 or b.dim() != 1:
+        raise ValueError(f"{name}: x must be [N, D], W [C, D] and b [C]")
+    N, D = x.shape
+    C = W.shape[0]
+    if D % 64 or not 64 <= D <= CLS_MAX_D:
+        raise ValueError(f"{name}: x has D = {D}; D must be a multiple of 64 in 64 .. {CLS_MAX_D}")
+    if not 1 <= C <= CLS_MAX_CLASSES:
+        raise ValueError(f"{name}: W has C = {C} rows; 1 <= C <= {CLS_MAX_CLASSES}")
+    if W.shape[1] != D:
+        raise ValueError(f"{name}: W has {W.shape[1]} columns, x has D = {D}")
+    if b.shape[0] != C:
+        raise ValueError(f"{name}: b holds {b.shape[0]} values, W has C = {C} rows")
+    if N < 1:
+        raise ValueError(f"{name}: x must hold at least one row")
+    return N, D, C
+
+
+def _cls_same_device(name, ref, **tensors):
+    for arg, t in tensors.items():
+        if t is not None:
+            _require_gpu(t, f"{name}: {arg}")
+            if t.device != ref.device:
+                raise ValueError(f"{name}: {arg} is on {t.device}, x on {ref.device}")
+
+
+def cls_head_scratch(N: int, D: int, C: int) -> int:
+    return _scratch_query("cls_head_scratch", N, D, C)
+
+
+def cls_head_logits(x, W, b, z=None):
+    """z [N, C] = x [N, D] @ W [C, D]^T + b [C], all fp32 (medmoe_cls_head_logits): the evaluation form of the head."""
+    N, D, C = _cls_head_check("cls_head_logits", x, W, b)
+    if z is None:
+        z = torch.empty((N, C), device=x.device, dtype=torch.float32)
+    _cls_f32("cls_head_logits", "z", z, (N, C))
+    _require_gpu(x, "cls_head_logits: x")
+    _cls_same_device("cls_head_logits", x, W=W, b=b, z=z)
+    call("cls_head_logits", x, W, b, z, N, D, C)
+    return z
+
+
+def cls_head_step(x, W, b, targets, dW, db, task: str = "multiclass", label_smoothing: float = 0.0, pos_weight=None, loss_scale: float = 1.0,
+                  z=None, dx=None, loss=None, counts=None, scratch=None):
+    """Forward, loss and backward of the linear head (medmoe_cls_head_step; the formulas are in include/medmoe_hip.h).
+    targets: int32 [N] (multiclass, -1 = not counted) or int8 [N, C] in {0, 1, -1} (multilabel).  dW [C, D] and db [C] are ACCUMULATED into;
+    dx [N, D], when given, is written.  Returns (z [N, C], loss fp32 [1], counts int32 [2] = (n_valid, n_correct)) - device tensors, nothing
+    is read back.  z / loss / counts / scratch may be handed in to reuse buffers (scratch: cls_head_scratch(N, D, C) floats)."""
+    name = "cls_head_step"
+    N, D, C = _cls_head_check(name, x, W, b)
+    if task not in CLS_TASKS:
+        raise ValueError(f"{name}: task must be one of {sorted(CLS_TASKS)}, got {task!r}")
+    want_dtype, want_shape = (torch.int32, (N,)) if task == "multiclass" else (torch.int8, (N, C))
+    if not isinstance(targets, torch.Tensor) or targets.dtype != want_dtype:
+        raise ValueError(f"{name}: targets must be {want_dtype} for task {task!r}, got {getattr(targets, 'dtype', type(targets))}")
+    if tuple(targets.shape) != want_shape or not targets.is_contiguous():
+        raise ValueError(f"{name}: targets must be contiguous with shape {want_shape}, got {tuple(targets.shape)}")
+    if targets.data_ptr() % 16:
+        raise ValueError(f"{name}: targets must start at a 16-byte boundary")
+    if not 0.0 <= float(label_smoothing) < 1.0:
+        raise ValueError(f"{name}: label_smoothing must be in [0, 1), got {label_smoothing}")
+    if task == "multilabel" and float(label_smoothing) != 0.0:
+        raise ValueError(f"{name}: label_smoothing is defined for the multiclass task only")
+    if pos_weight is not None:
+        if task != "multilabel":
+            raise ValueError(f"{name}: pos_weight is defined for the multilabel task only")
+        _cls_f32(name, "pos_weight", pos_weight, (C,))
+    _cls_f32(name, "dW", dW, (C, D))
+    _cls_f32(name, "db", db, (C,))
+    if dx is not None:
+        _cls_f32(name, "dx", dx, (N, D), align=True)
+    _require_gpu(x, f"{name}: x")
+    dev = x.device
+    if z is None:
+        z = torch.empty((N, C), device=dev, dtype=torch.float32)
+    if loss is None:
+        loss = torch.empty(1, device=dev, dtype=torch.float32)
+    if counts is None:
+        counts = torch.empty(2, device=dev, dtype=torch.int32)
+    need = cls_head_scratch(N, D, C)
+    if scratch is None:
+        scratch = torch.empty(need, device=dev, dtype=torch.float32)
+    _cls_f32(name, "z", z, (N, C))
+    _cls_f32(name, "loss", loss, (1,))
+    _cls_f32(name, "scratch", scratch, align=True)
+    if scratch.numel() < need:
+        raise ValueError(f"{name}: scratch holds {scratch.numel()} floats, cls_head_scratch({N}, {D}, {C}) = {need}")
+    if counts.dtype != torch.int32 or counts.numel() != 2 or not counts.is_contiguous():
+        raise ValueError(f"{name}: counts must be a contiguous int32 tensor of 2 elements")
+    _cls_same_device(name, x, W=W, b=b, targets=targets, pos_weight=pos_weight, dW=dW, db=db, dx=dx, z=z, loss=loss, counts=counts, scratch=scratch)
+    call(name, x, W, b, targets, pos_weight, CLS_TASKS[task], float(label_smoothing), float(loss_scale), z, dx, dW, db, loss, counts, scratch,
+         scratch.numel(), N, D, C)
+    return z, loss, counts
+
+
+def auroc_counts(scores, targets):
+    """int64 [C, 4] = (n_pos, n_neg, n_less, n_equal) per class (medmoe_auroc_counts): scores fp32 [N, C] (finite), targets int8 [N, C] in
+    {0, 1, -1}; n_less / n_equal count the (positive i, negative j) pairs with s_j < s_i / s_j == s_i.  Exact integers, no [N, N] matrix."""
+    name = "auroc_counts"
+    _cls_f32(name, "scores", scores)
+    if scores.dim() != 2 or scores.shape[0] < 1 or scores.shape[1] < 1:
+        raise ValueError(f"{name}: scores must be [N, C] with N >= 1 and C >= 1, got {tuple(scores.shape)}")
+    if not isinstance(targets, torch.Tensor) or targets.dtype != torch.int8:
+        raise ValueError(f"{name}: targets must be int8, got {getattr(targets, 'dtype', type(targets))}")
+    if tuple(targets.shape) != tuple(scores.shape) or not targets.is_contiguous():
+        raise ValueError(f"{name}: targets must be contiguous and shaped like scores {tuple(scores.shape)}, got {tuple(targets.shape)}")
+    N, C = scores.shape
+    if C > 65535:
+        raise ValueError(f"{name}: at most 65535 classes, got {C}")
+    _require_gpu(scores, f"{name}: scores")
+    _cls_same_device(name, scores, targets=targets)
+    out = torch.empty((C, 4), device=scores.device, dtype=torch.int64)
+    call(name, scores, targets, out, N, C)
+    return out

@@ -221,6 +221,13 @@ class SwinEngine:
     def embed_text(self, ids: torch.Tensor, attn_mask: torch.Tensor, token_type=None, ema: bool = False):
         self.embed(None)
 
+    def classify_step(self, *a, **kw):
+        raise NotImplementedError("SwinEngine.classify_step / classify_eval (vision.arch = swin_t): the classification head trains on the ViT "
+                                  "Engine's global embedding and backward (DESIGN 3p); the Swin tower is a named follow-up")
+
+    def classify_eval(self, *a, **kw):
+        self.classify_step()
+
     def eval_step(self, batch: Dict[str, torch.Tensor]):
         """Forward + losses without gradients reaching the parameters (validation): the same launch sequence minus the encoder backward."""
         was = self.training
