@@ -149,6 +149,13 @@ int medmoe_gemm_tn_gram(const void* A, int lda, const float* w, long long w_gstr
    global store, one owner per element, no atomics (two launches give the same bits).  There is no pair matrix, hence no column base.
    Geometries of medmoe_local_pair3_supported, D % 64 == 0; anything else returns -2 before a launch. */
 int medmoe_local_sim_fwd(const void* ctx, const void* words, const int* cap_lens, const void* gm, const float* wnorm, float* sim, int B, int Bc, int HW, int T, int D, float temp1, float temp2, float eps, const int* cap_list, int n_cap, int ntt, hipStream_t stream);
+/* the same similarity for a LIST of (image, caption) pairs grouped by image (candidate re-ranking), one launch per caption
+   length class ntt: units int32 [n_units][4] = (image b, first list entry, entry count, 0); one workgroup per unit stages image b's Gram
+   fragments once and walks its entries; entry e is the pair (b, pair_cap[e]) and its similarity goes to out[pair_slot[e]].  The device
+   code is medmoe_local_sim_fwd's: a pair's value equals that kernel's bit for bit.  One owner per written slot, no atomics; slots that
+   no entry names are not written.  The kernel trusts its tables - validate on the host.  n_units == 0 returns 0 without a launch;
+   geometries as medmoe_local_sim_fwd, anything else returns -2 before a launch. */
+int medmoe_local_sim_pairs(const void* ctx, const void* words, const int* cap_lens, const void* gm, const float* wnorm, float* out, const int* units, int n_units, const int* pair_cap, const int* pair_slot, int B, int Bc, int HW, int T, int D, float temp1, float temp2, float eps, int ntt, hipStream_t stream);
 /* tests: caption chunks per image of medmoe_local_sim_fwd (0 = automatic) */
 int medmoe_local_sim_chunks(int n);
 /* tests: caption chunks per image of medmoe_local_pair3 (0 = automatic) */

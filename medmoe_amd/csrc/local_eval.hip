@@ -18,10 +18,17 @@
 // Reductions over a caption's WORDS (the word softmax, sum_t exp(temp2 cos_t)) cross the 16 lanes of a DPP row and, for captions of
 // more than 16 words, the caption's waves through LDS.  The waves are in lock step here anyway (the ring), so that exchange uses the
 // workgroup barrier instead of pair3's epoch flags; its mailboxes alias the ring, which is idle between two captions' score loops.
+//
+// The same body serves two launches (template flag PAIRS).  All pairs (medmoe_local_sim_fwd): a workgroup is (image, chunk of the class's
+// caption list) and writes sim[b][i].  Listed pairs (medmoe_local_sim_pairs, candidate re-ranking - DESIGN 3q): a workgroup is one UNIT
+// (image b, a run of entries of a pair list); entry e names its caption pair_cap[e] and the element pair_slot[e] of `sim` that receives
+// the value.  Only where the caption index comes from and where the result goes differs: the arithmetic of a pair is the same
+// instructions in the same order, so a listed pair's value is the all-pairs value bit for bit.
 #include "common.h"
 
 struct LocalSimArgs {
   const bf16_t* ctx; const bf16_t* words; const bf16_t* gm; const float* wnorm; const int* cap_lens; const int* cap_list; float* sim;
+  const int* units; const int* pair_slot;      // PAIRS: [n_units][4] = (image, first entry, entries, 0); cap_list is then pair_cap
   int n_cap, B, Bc, T, D, caps_per_wg, n_chunk;
   float temp1, temp2, eps;
 };
@@ -51,7 +58,7 @@ __device__ __forceinline__ float ls_grp4_sum(float v) {      // over the four 16
 // waves: 168): no instantiation spills.  One workgroup is resident per CU either way (150 KB of LDS).
 __host__ __device__ constexpr int ls_waves(int ntt) { return ntt == 3 ? 12 : ntt == 5 ? 10 : 8; }
 
-template <int HW, int NTT>
+template <int HW, int NTT, bool PAIRS>
 __global__ __launch_bounds__(ls_waves(NTT) * 64) void local_sim_fwd_kernel(LocalSimArgs p) {
   constexpr int NW = ls_waves(NTT);
   constexpr int NS = (HW + 31) / 32, NRT = 2 * NS, GR = NS * 32, CPI = NW / NTT, TP = NTT * 16;
@@ -66,7 +73,15 @@ __global__ __launch_bounds__(ls_waves(NTT) * 64) void local_sim_fwd_kernel(Local
   __shared__ __attribute__((aligned(16))) char smem[OFF_SE + 64];
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int fr = lane & 15, g = lane >> 4;
-  const int b = blockIdx.x / p.n_chunk, chunk = blockIdx.x - b * p.n_chunk;
+  // the image and the run [j0, j_end) of the caption list this workgroup walks
+  int b, j0, j_end;
+  if (PAIRS) {
+    const int4 u = *(const int4*)(p.units + 4 * blockIdx.x);
+    b = u.x; j0 = u.y; j_end = u.y + u.z;
+  } else {
+    b = blockIdx.x / p.n_chunk;
+    j0 = (blockIdx.x - b * p.n_chunk) * p.caps_per_wg; j_end = min(p.n_cap, j0 + p.caps_per_wg);
+  }
   const int D = p.D, nk = D >> 6;
   // ---- the image's Gram matrix, rows permuted, as MFMA A-operand fragments [rt][s][lane] ----
   for (int f = wid; f < NRT * NS; f += NW) {
@@ -101,7 +116,6 @@ __global__ __launch_bounds__(ls_waves(NTT) * 64) void local_sim_fwd_kernel(Local
   };
   const float c1 = p.temp1 * 1.44269504088896f;
   constexpr float LOG2E = 1.44269504088896f;
-  const int j0 = chunk * p.caps_per_wg, j_end = min(p.n_cap, j0 + p.caps_per_wg);
   const char* gfrag = smem + lane * 16;
   // every wave takes every barrier: the loop count is the workgroup's, a wave without a unit (the tail of the
   // list) fills the ring and skips the arithmetic
@@ -259,8 +273,16 @@ __global__ __launch_bounds__(ls_waves(NTT) * 64) void local_sim_fwd_kernel(Local
         for (int q = 0; q < NTT; ++q) se += sebox[w0 + q];
       }
     }
-    if (active && tt == 0 && lane == 0) p.sim[(long long)b * p.Bc + i] = __logf(se);
+    if (active && tt == 0 && lane == 0) p.sim[PAIRS ? (long long)p.pair_slot[j] : (long long)b * p.Bc + i] = __logf(se);
   }
+}
+
+template <bool PAIRS>
+static void ls_launch(const LocalSimArgs& p, int HW, int ntt, dim3 grid, dim3 block, hipStream_t stream) {
+#define LS(HW_, T_) hipLaunchKernelGGL((local_sim_fwd_kernel<HW_, T_, PAIRS>), grid, block, 0, stream, p);
+  if (HW == 64) LS(64, 1)
+  else switch (ntt) { case 1: LS(196, 1) break; case 2: LS(196, 2) break; case 3: LS(196, 3) break; case 4: LS(196, 4) break; default: LS(196, 5) break; }
+#undef LS
 }
 
 // Tests: force the number of caption chunks per image (0 = automatic), as medmoe_local_pair3_chunks does for the training kernels.
@@ -283,7 +305,7 @@ extern "C" int medmoe_local_sim_fwd(const void* ctx, const void* words, const in
   if (!((HW == 64 && ntt == 1) || HW == 196) || D < 64 || (D % 64)) return MM_ERR_SHAPE;
   LocalSimArgs p;
   p.ctx = (const bf16_t*)ctx; p.words = (const bf16_t*)words; p.gm = (const bf16_t*)gm; p.wnorm = wnorm; p.cap_lens = cap_lens;
-  p.cap_list = cap_list; p.sim = sim; p.n_cap = n_cap; p.B = B; p.Bc = Bc; p.T = T; p.D = D; p.temp1 = temp1; p.temp2 = temp2; p.eps = eps;
+  p.cap_list = cap_list; p.sim = sim; p.units = nullptr; p.pair_slot = nullptr; p.n_cap = n_cap; p.B = B; p.Bc = Bc; p.T = T; p.D = D; p.temp1 = temp1; p.temp2 = temp2; p.eps = eps;
   // one workgroup per (image, caption chunk), one resident per CU (LDS): enough chunks that small batches still give every CU a few
   // workgroups (the heuristic of medmoe_local_pair3, not tuned here); chunks are a multiple of the captions per iteration
   const int nw = ls_waves(ntt), cpi = nw / ntt;
@@ -292,9 +314,27 @@ extern "C" int medmoe_local_sim_fwd(const void* ctx, const void* words, const in
   n_chunk = (n_cap + cpw - 1) / cpw;
   p.caps_per_wg = cpw; p.n_chunk = n_chunk;
   const dim3 grid(B * n_chunk), block(nw * 64);
-#define LS(HW_, T_) hipLaunchKernelGGL((local_sim_fwd_kernel<HW_, T_>), grid, block, 0, stream, p);
-  if (HW == 64) LS(64, 1)
-  else switch (ntt) { case 1: LS(196, 1) break; case 2: LS(196, 2) break; case 3: LS(196, 3) break; case 4: LS(196, 4) break; default: LS(196, 5) break; }
-#undef LS
+  ls_launch<false>(p, HW, ntt, grid, block, stream);
+  return mm_check_launch();
+}
+
+// Host entry of the listed pairs (candidate re-ranking): out[pair_slot[e]] = the similarity of (image units[u][0], caption pair_cap[e]) for
+// every entry e of every unit u = (image, first entry, entries, 0), one workgroup per unit, which stages the image's Gram fragments once
+// and walks its entries ls_waves(ntt) / ntt captions at a time.  ctx, words, cap_lens, gm, wnorm as medmoe_local_sim_fwd; all captions of a
+// launch are of length class ntt.  One owner per written slot (the caller's lists name a slot once), no atomics; slots no entry names
+// are not written.  The kernel trusts its tables: the caller validates every index on the host (medmoe_amd/ops.py local_sim_pairs).
+extern "C" int medmoe_local_sim_pairs(const void* ctx, const void* words, const int* cap_lens, const void* gm, const float* wnorm, float* out,
+                                      const int* units, int n_units, const int* pair_cap, const int* pair_slot, int B, int Bc, int HW, int T,
+                                      int D, float temp1, float temp2, float eps, int ntt, hipStream_t stream) {
+  if (n_units < 0) return MM_ERR_ARG;
+  if (B <= 0 || Bc <= 0 || T <= 0 || ntt < 1 || ntt > 5 || ntt * 16 > ((T + 15) / 16) * 16) return MM_ERR_SHAPE;
+  if (!((HW == 64 && ntt == 1) || HW == 196) || D < 64 || (D % 64)) return MM_ERR_SHAPE;
+  if (n_units == 0) return MM_OK;
+  if (!ctx || !words || !cap_lens || !gm || !wnorm || !out || !units || !pair_cap || !pair_slot) return MM_ERR_ARG;
+  LocalSimArgs p;
+  p.ctx = (const bf16_t*)ctx; p.words = (const bf16_t*)words; p.gm = (const bf16_t*)gm; p.wnorm = wnorm; p.cap_lens = cap_lens;
+  p.cap_list = pair_cap; p.sim = out; p.units = units; p.pair_slot = pair_slot; p.n_cap = 0; p.B = B; p.Bc = Bc; p.T = T; p.D = D;
+  p.caps_per_wg = 0; p.n_chunk = 1; p.temp1 = temp1; p.temp2 = temp2; p.eps = eps;
+  ls_launch<true>(p, HW, ntt, dim3(n_units), dim3(ls_waves(ntt) * 64), stream);
   return mm_check_launch();
 }

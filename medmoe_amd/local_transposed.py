@@ -60,16 +60,55 @@ def local_sim_forward(ctx: torch.Tensor, words: torch.Tensor, cap_lens: torch.Te
     caller's gm3 [B*GR, GR] (zero outside [P, P]), wn [Bc, T] and sim."""
     Bc, T, Do = words.shape
     B = ctx.shape[0] // P
-    _, Tp, _ = ops.local_geometry(P, T)
-    perm, col_of_cap, ntts, _, classes, _, Kp = ragged_layout(cap_lens_host, T, Tp)
-    meta = torch.from_numpy(np.concatenate((perm, col_of_cap, 16 * ntts)).astype(np.int32)).to(ctx.device, non_blocking=True)
-    d_perm, d_col, d_tp = meta[:Bc], meta[Bc:2 * Bc], meta[2 * Bc:]
-    ops.call("words_prep_ragged", words, wn, None, Bc, T, Tp, Do, d_col, d_tp, Kp)                         # word norms only
-    ops.gemm_nt(ctx, ctx, gm3, c_rowmap=gm3_crowmap, tiles=img_tiles, tile_count=img_tile_count, max_tiles=img_tiles.shape[0],
-                stride_b=P * Do, M=B * P, N=P)
+    d_perm, classes = local_word_norms(words, cap_lens_host, wn, P)
+    local_gram(ctx, gm3, P=P, gm3_crowmap=gm3_crowmap, img_tiles=img_tiles, img_tile_count=img_tile_count)
     for ntt, start, n_c, _ in classes:
         ops.call("local_sim_fwd", ctx, words, cap_lens, gm3, wn, sim, B, Bc, P, T, Do, temp1, temp2, 1e-8, d_perm[start:start + n_c], n_c, ntt)
     return sim
+
+
+def local_word_norms(words: torch.Tensor, cap_lens_host, wn: torch.Tensor, P: int):
+    """The word norms of local_sim_forward into wn fp32 [Bc, T].  Returns (d_perm, classes): the captions in class-major order on the device
+    and ragged_layout's class table [(ntt, first index into d_perm, count, first column)]."""
+    Bc, T, Do = words.shape
+    _, Tp, _ = ops.local_geometry(P, T)
+    perm, col_of_cap, ntts, _, classes, _, Kp = ragged_layout(cap_lens_host, T, Tp)
+    meta = torch.from_numpy(np.concatenate((perm, col_of_cap, 16 * ntts)).astype(np.int32)).to(words.device, non_blocking=True)
+    d_perm, d_col, d_tp = meta[:Bc], meta[Bc:2 * Bc], meta[2 * Bc:]
+    ops.call("words_prep_ragged", words, wn, None, Bc, T, Tp, Do, d_col, d_tp, Kp)                         # word norms only
+    return d_perm, classes
+
+
+def local_gram(ctx: torch.Tensor, gm3: torch.Tensor, *, P: int, gm3_crowmap: torch.Tensor, img_tiles: torch.Tensor,
+               img_tile_count: torch.Tensor) -> torch.Tensor:
+    """The Gram matrices ctx_b ctx_b^T of local_sim_forward into gm3 bf16 [B*GR, GR] (zero outside [P, P]: the GEMM only fills [P][P])."""
+    ops.gemm_nt(ctx, ctx, gm3, c_rowmap=gm3_crowmap, tiles=img_tiles, tile_count=img_tile_count, max_tiles=img_tiles.shape[0],
+                stride_b=P * ctx.shape[1], M=ctx.shape[0], N=P)
+    return gm3
+
+
+class LocalSimScratch:
+    """The workspace of local_sim_forward / ops.local_sim_pairs for up to `B` images of P regions outside an engine (evaluation over a bank,
+    medmoe_amd/retrieval.py): the Gram matrices with their row map and tile table.  gram_kw(n) = the keywords of local_gram /
+    local_sim_forward for the first n images."""
+
+    def __init__(self, B: int, P: int, device):
+        self.B, self.P, self.GR, dev = int(B), int(P), (P + 31) // 32 * 32, torch.device(device)
+        self.gm3 = torch.zeros(self.B * self.GR, self.GR, device=dev, dtype=BF)
+        arg = torch.arange(self.B * P, device=dev)
+        self.crowmap = (arg // P * self.GR + arg % P).to(I32)
+        tl = [[b, m, (b + 1) * P, 0] for b in range(self.B) for m in range(b * P, (b + 1) * P, 128)]
+        self.tiles = torch.tensor(tl, device=dev, dtype=I32)
+        self.tiles_per_image = len(tl) // self.B
+        self._count = {}
+
+    def gram_kw(self, n: int):
+        if not 1 <= n <= self.B:
+            raise ValueError(f"LocalSimScratch: {n} images, sized for 1 .. {self.B}")
+        nt = n * self.tiles_per_image
+        if n not in self._count:
+            self._count[n] = torch.tensor([nt], device=self.gm3.device, dtype=I32)
+        return dict(P=self.P, gm3_crowmap=self.crowmap[:n * self.P], img_tiles=self.tiles[:nt], img_tile_count=self._count[n])
 
 
 class TransposedLocalLoss:

@@ -689,7 +689,7 @@ _SIGS = {
     "local_pair": "pppppppppppppiiiiifffi", "local_scores": "pppppiiiii", "local_pair2": "ppppppppppiiiifff", "scale_blocks": "pppiiii",
     "words_prep_ragged": "pppiiiippl", "local_scores_ragged": "pppppiiiiipiill",
     "local_pair2_ragged": "pppppppppiiiifffpiill", "scale_blocks_ragged": "pppiiipl",
-    "local_pair3": "ppppppppppppliiiifffpiilllip", "local_pair3_wgrad": "ppppppppppppliiiifffpiilllipp", "local_scores_t": "pppppiiiiipiilll", "local_sim_fwd": "ppppppiiiiifffpii", "gemm_tn_cols": "pipipiiiiilllil", "gemm_tn_gram": "piplipiiiill",
+    "local_pair3": "ppppppppppppliiiifffpiilllip", "local_pair3_wgrad": "ppppppppppppliiiifffpiilllipp", "local_scores_t": "pppppiiiiipiilll", "local_sim_fwd": "ppppppiiiiifffpii", "local_sim_pairs": "pppppppippiiiiifffi", "gemm_tn_cols": "pipipiiiiilllil", "gemm_tn_gram": "piplipiiiill",
     "local_gen_fwd_a": "pppiiiiiifl", "local_gen_cos": "pppppppiiiiiffl", "local_gen_dwctx": "ppppppppiiiiiffl",
     "local_gen_dwords": "pppppppppiiiiiffl",
     "local_gen_bwd_s": "ppppiiiiiifl", "unpad_cast2": "pppiiii",
@@ -783,6 +783,10 @@ def _cost_local_sim(a):     # (ctx, words, caps, gm, wn, sim, B, Bc, P, T, Do, t
     return "local_sim_fwd_kernel<196, NTT> (scores + pair stage, forward only)", 2.0 * a[6] * a[8] * a[15] * 16 * a[16] * a[10], "flop"
 
 
+def _cost_local_pairs(a):   # (ctx, words, caps, gm, wn, out, units, n_units, pair_cap, pair_slot, B, Bc, P, T, Do, t1, t2, eps, ntt): work unknown here (the entry count is the tables')
+    return "local_sim_fwd_kernel<196, NTT, PAIRS> (listed pairs)", None, None
+
+
 def _cost_tn_cols(a):       # (g, ldg, x, ldx, dw, ldw, M, Nn, Kk, n_groups, ...)
     return "gemm_tn4w_kernel<false, COLG, false> (local-loss dC)", 2.0 * a[6] * a[7] * a[8] * max(1, a[9]), "flop"
 
@@ -792,7 +796,7 @@ def _cost_tn_gram(a):       # (AT, ld, d2, srows, 1, out, ldo, Kp, HWq, B, bs, o
 
 
 _COSTS = {
-    "local_scores_t": _cost_scores, "local_pair3": _cost_pair3, "local_pair3_wgrad": _cost_pair3, "local_sim_fwd": _cost_local_sim, "gemm_tn_cols": _cost_tn_cols, "gemm_tn_gram": _cost_tn_gram,
+    "local_scores_t": _cost_scores, "local_pair3": _cost_pair3, "local_pair3_wgrad": _cost_pair3, "local_sim_fwd": _cost_local_sim, "local_sim_pairs": _cost_local_pairs, "gemm_tn_cols": _cost_tn_cols, "gemm_tn_gram": _cost_tn_gram,
     "gemm_tn_cols_det": _cost_tn_cols, "gemm_tn_gram_det": _cost_tn_gram,
     "adam_step": lambda a: ("adam_kernel", 34.0 * a[5], "byte"),                                   # p, g, m, v read; p, m, v, bf16 copy written
     "adam_groups_step": lambda a: ("adam_groups_kernel", 34.0 * a[5], "byte"),                     # the same traffic: the run table stays on chip
@@ -870,6 +874,60 @@ def local_geometry(HW: int, T: int):
     rc = lib.medmoe_local_geometry(_c.c_int(HW), _c.c_int(T), _c.byref(a), _c.byref(b), _c.byref(c))
     _chk(rc, "local_geometry")
     return a.value, b.value, c.value
+
+
+def local_sim_pairs(ctx, words, cap_lens, gm, wnorm, out, units, pair_cap, pair_slot, *, P: int, ntt: int, temp1: float, temp2: float,
+                    cap_lens_host, eps: float = 1e-8):
+    """medmoe_local_sim_pairs (csrc/local_eval.hip): out.view(-1)[pair_slot[e]] = the local similarity (before temp3) of image
+    units[u][0] and caption pair_cap[e], for every entry e of every unit u = (image, first entry, entry count, 0).  ctx bf16 [B*P, D], words
+    bf16 [Bc, T, D], cap_lens int32 [Bc] and wnorm fp32 [Bc, T] on the device, gm bf16 [B*GR, GR] as for local_sim_fwd; all captions listed
+    are of length class ntt.  units / pair_cap / pair_slot and cap_lens_host are HOST tables (numpy or CPU tensors): the kernel trusts
+    them, so every index is checked here, before anything is uploaded or launched - an index of -1 (sim_topk's padding) never reaches
+    the device.  Slots no entry names keep their value.  Returns out."""
+    import numpy as np
+    name = "local_sim_pairs"
+    _need(ctx, torch.bfloat16, "ctx"); _need(words, torch.bfloat16, "words"); _need(gm, torch.bfloat16, "gm")
+    _need(cap_lens, torch.int32, "cap_lens"); _need(wnorm, torch.float32, "wnorm"); _need(out, torch.float32, "out")
+    if words.dim() != 3 or ctx.dim() != 2 or not (ctx.is_contiguous() and words.is_contiguous() and gm.is_contiguous() and out.is_contiguous()
+                                                   and wnorm.is_contiguous() and cap_lens.is_contiguous()):
+        raise ValueError(f"{name}: ctx [B*P, D], words [Bc, T, D], gm, wnorm, cap_lens and out must be contiguous")
+    Bc, T, D = words.shape
+    P, ntt = int(P), int(ntt)
+    if ctx.shape[1] != D or ctx.shape[0] % P or ctx.shape[0] == 0:
+        raise ValueError(f"{name}: ctx must be [B*{P}, {D}], got {tuple(ctx.shape)}")
+    B, GR = ctx.shape[0] // P, (P + 31) // 32 * 32
+    if D % 64 or D < 64 or not 1 <= ntt <= 5 or not local_pair3_supported(P, 16 * ntt) or 16 * ntt > (T + 15) // 16 * 16:
+        raise ValueError(f"{name}: {P} regions x length class {ntt} (T = {T}) at D = {D} has no kernel: 196 regions with classes 1..5 or 64 "
+                         "regions with class 1, D a multiple of 64 (local_pair3_supported)")
+    if gm.numel() != B * GR * GR or wnorm.numel() != Bc * T or cap_lens.numel() != Bc:
+        raise ValueError(f"{name}: gm must hold [{B}*{GR}, {GR}], wnorm [{Bc}, {T}] and cap_lens [{Bc}] elements")
+    tab = [np.ascontiguousarray(t.cpu().numpy() if torch.is_tensor(t) else t).astype(np.int64) for t in (units, pair_cap, pair_slot)]
+    units_h, cap_h, slot_h = tab[0].reshape(-1, 4), tab[1].reshape(-1), tab[2].reshape(-1)
+    lens_h = np.asarray(cap_lens_host.cpu().numpy() if torch.is_tensor(cap_lens_host) else cap_lens_host, dtype=np.int64).reshape(-1)
+    if lens_h.shape[0] != Bc:
+        raise ValueError(f"{name}: cap_lens_host holds {lens_h.shape[0]} lengths, words {Bc} captions")
+    if slot_h.shape[0] != cap_h.shape[0]:
+        raise ValueError(f"{name}: pair_cap holds {cap_h.shape[0]} entries, pair_slot {slot_h.shape[0]}")
+    n_units, n_e = units_h.shape[0], cap_h.shape[0]
+    if n_units == 0:
+        return out
+    if units_h[:, 0].min() < 0 or units_h[:, 0].max() >= B:
+        raise ValueError(f"{name}: a unit's image lies outside [0, {B})")
+    if units_h[:, 1].min() < 0 or units_h[:, 2].min() < 0 or (units_h[:, 1] + units_h[:, 2]).max() > n_e:
+        raise ValueError(f"{name}: a unit's entries lie outside the list of {n_e}")
+    if n_e and (cap_h.min() < 0 or cap_h.max() >= Bc):
+        raise ValueError(f"{name}: a pair_cap entry lies outside [0, {Bc}) (drop the -1 padding of sim_topk before building the list)")
+    if n_e and (slot_h.min() < 0 or slot_h.max() >= out.numel()):
+        raise ValueError(f"{name}: a pair_slot entry lies outside [0, {out.numel()})")
+    if np.unique(slot_h).shape[0] != n_e:
+        raise ValueError(f"{name}: pair_slot names a slot twice - every written slot has one owner")
+    cls = (np.clip(lens_h[cap_h], 1, T) + 15) // 16
+    if n_e and (cls != ntt).any():
+        raise ValueError(f"{name}: a listed caption is not of length class {ntt} (16 (ntt - 1) < length <= 16 ntt)")
+    meta = torch.from_numpy(np.concatenate((units_h.reshape(-1), cap_h, slot_h)).astype(np.int32)).to(ctx.device, non_blocking=True)
+    call(name, ctx, words, cap_lens, gm, wnorm, out, meta[:4 * n_units], n_units, meta[4 * n_units:4 * n_units + n_e], meta[4 * n_units + n_e:],
+         B, Bc, P, T, D, temp1, temp2, eps, ntt)
+    return out
 
 
 # ---------------------------------------------------------------------------------------------

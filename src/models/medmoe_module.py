@@ -44,7 +44,11 @@ class MedMoEPretrainingLightningModule(_Base):
         forward) to a medmoe_amd.retrieval.EmbeddingBank; `on_validation_epoch_start` resets the bank, `on_validation_epoch_end` scores it.
         `zero_shot` = path of a .pt holding prompt_ids / prompt_mask [C, Pn, T] and class_names: zero-shot accuracy (`zero_shot_ks`,
         default [1, 5]) of the images against the prompt-ensembled class embeddings, the true class read from batch[`label_key`]
-        (default "label").  With model.ema.validate everything runs on the averaged weights."""
+        (default "label").  With model.ema.validate everything runs on the averaged weights.
+        `local` (`+model.retrieval.local=true`, `local_k` 1..16, `local_agg` sum | mean): the epoch also keeps the batches' region
+        and word features (medmoe_amd.retrieval.LocalBank) and reports val/i2t_local_R@k, val/t2i_local_* - every query's local_k best keys
+        re-ranked with the weighted global + GLoRIA local similarity - and, with `zero_shot`, val/zs_local_acc@k.  Every key logged without
+        it keeps its value."""
         super().__init__()
         self.model = model
         self.loss_cfg = loss
@@ -81,6 +85,7 @@ class MedMoEPretrainingLightningModule(_Base):
         if self._ema_validate and not self._ema_decay > 0.0:
             raise ValueError("model.ema.validate=true needs model.ema.decay > 0: there is no average to validate on")
         self._retrieval, self._bank, self._zs, self._class_emb = self._retrieval_block(retrieval), None, None, None
+        self._lbank, self._class_words = None, None              # model.retrieval.local: the local features of the epoch, the prompts' words
         if self.fused_step:
             self.automatic_optimization = False                                  # Lightning: manual optimisation (the engine steps itself)
             self._configure_engine()
@@ -90,9 +95,9 @@ class MedMoEPretrainingLightningModule(_Base):
         if retrieval is None:
             return None
         r = dict(retrieval)
-        unknown = set(r) - {"ks", "zero_shot", "zero_shot_ks", "label_key"}
+        unknown = set(r) - {"ks", "zero_shot", "zero_shot_ks", "label_key", "local", "local_k", "local_agg"}
         if unknown:
-            raise KeyError(f"model.retrieval: unknown keys {sorted(unknown)} (ks, zero_shot, zero_shot_ks, label_key)")
+            raise KeyError(f"model.retrieval: unknown keys {sorted(unknown)} (ks, zero_shot, zero_shot_ks, label_key, local, local_k, local_agg)")
         if not self.fused_step:
             raise NotImplementedError("model.retrieval needs fused_step=true (model.fused_step=true): the embeddings are read from the HIP "
                                       "engine's workspace after Engine.eval_step; the autograd path keeps none")
@@ -103,7 +108,25 @@ class MedMoEPretrainingLightningModule(_Base):
         zks = tuple(int(k) for k in r.get("zero_shot_ks", (1, 5)))
         if not ks or min(ks) < 1 or min(zks or (1,)) < 1:
             raise ValueError(f"model.retrieval: ks / zero_shot_ks must hold integers >= 1, got {ks} / {zks}")
-        return {"ks": ks, "zero_shot": r.get("zero_shot"), "zero_shot_ks": zks, "label_key": str(r.get("label_key", "label"))}
+        blk = {"ks": ks, "zero_shot": r.get("zero_shot"), "zero_shot_ks": zks, "label_key": str(r.get("label_key", "label"))}
+        local_k, local_agg = r.get("local_k", 16), str(r.get("local_agg", "sum"))
+        if isinstance(local_k, bool) or int(local_k) != local_k or not 1 <= int(local_k) <= 16:
+            raise ValueError(f"model.retrieval.local_k must be an integer in 1 .. 16 (the depth of sim_topk), got {local_k!r}")
+        if local_agg not in ("sum", "mean"):
+            raise ValueError(f"model.retrieval.local_agg must be 'sum' or 'mean', got {local_agg!r}")
+        if bool(r.get("local", False)):
+            if max(ks) > int(local_k):
+                raise ValueError(f"model.retrieval: ks = {ks} with local=true needs local_k >= {max(ks)}, got {int(local_k)} (at most 16: a target "
+                                 "outside its candidate list keeps its global rank; deeper lists are a named follow-up, DESIGN 3q)")
+            cfg = getattr(getattr(self.model, "engine", None), "cfg", None)
+            if cfg is not None:
+                from medmoe_amd import ops
+                if not ops.local_pair3_supported(cfg.n_patch, cfg.max_len) or cfg.d_out % 64:
+                    raise NotImplementedError(f"model.retrieval.local with {cfg.n_patch} regions x {cfg.max_len} words at width {cfg.d_out}: the "
+                                              "listed-pair kernel covers 196 regions (up to 80 words) and 64 regions (up to 16); the 256 / 576 "
+                                              "regions of cfg4 / cfg3 are a named follow-up (DESIGN 3q)")
+            blk.update({"local": True, "local_k": int(local_k), "local_agg": local_agg})     # absent without local: the block of DESIGN 3o as it was
+        return blk
 
     def forward(self, batch):
         return self.model(batch)
@@ -308,6 +331,11 @@ class MedMoEPretrainingLightningModule(_Base):
             self._bank = EmbeddingBank(eng.cfg.d_out, eng.device)
         lab = batch.get(self._retrieval["label_key"]) if isinstance(batch, dict) else None
         self._bank.add(eng.ws["img_g"], eng.ws["txt_g"], lab if torch.is_tensor(lab) else None)
+        if self._retrieval.get("local"):
+            if self._lbank is None:
+                from medmoe_amd.retrieval import LocalBank
+                self._lbank = LocalBank.for_engine(eng)
+            self._lbank.add(eng)
 
     def on_validation_epoch_start(self):
         """Empty the bank; with model.retrieval.zero_shot, embed the class prompts under the weights this epoch validates on."""
@@ -315,6 +343,8 @@ class MedMoEPretrainingLightningModule(_Base):
             return
         if self._bank is not None:
             self._bank.reset()
+        if self._lbank is not None:
+            self._lbank.reset()
         path = self._retrieval["zero_shot"]
         if path:
             from medmoe_amd.retrieval import class_embeddings
@@ -326,15 +356,21 @@ class MedMoEPretrainingLightningModule(_Base):
             eng = self._fused_engine()
             self._class_emb = class_embeddings(eng, self._zs["prompt_ids"].to(eng.device), self._zs["prompt_mask"].to(eng.device),
                                                ema=self._ema_validate)
+            if self._retrieval.get("local"):
+                from medmoe_amd.retrieval import class_prompt_words
+                self._class_words = class_prompt_words(eng, self._zs["prompt_ids"].to(eng.device), self._zs["prompt_mask"].to(eng.device),
+                                                       ema=self._ema_validate)
 
     def on_validation_epoch_end(self):
         """The epoch's retrieval (and zero-shot) metrics as plain floats; the trainer files them under val/... or test/...."""
         if self._retrieval is None or self._bank is None:
             return None
         from medmoe_amd.retrieval import retrieval_metrics, zero_shot_metrics
-        out = {k: float(v) for k, v in retrieval_metrics(self._bank, self._retrieval["ks"]).items()}
+        loc = dict(local=self._lbank, local_k=self._retrieval["local_k"], local_agg=self._retrieval["local_agg"]) if self._lbank is not None else {}
+        out = {k: float(v) for k, v in retrieval_metrics(self._bank, self._retrieval["ks"], **loc).items()}
         if self._class_emb is not None:
-            zs = zero_shot_metrics(self._bank, self._class_emb, ks=self._retrieval["zero_shot_ks"])
+            zloc = dict(local=(self._lbank,) + tuple(self._class_words), local_agg=self._retrieval["local_agg"]) if self._class_words is not None else {}
+            zs = zero_shot_metrics(self._bank, self._class_emb, ks=self._retrieval["zero_shot_ks"], **zloc)
             names = list(self._zs["class_names"])
             for k, v in zs.items():
                 if torch.is_tensor(v):
