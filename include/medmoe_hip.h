@@ -516,6 +516,43 @@ long long medmoe_cls_head_scratch(int N, int D, int C);
    256 positives through LDS, nothing of size [N][N] is stored; the counts are 64-bit integer adds: exact and repeatable. */
 int medmoe_auroc_counts(const float* scores, const signed char* targets, long long* out, int N, int C, hipStream_t stream);
 
+/* Masked-language-model objective of the text tower (csrc/mlm.hip).
+   The step's mask, drawn on the chip.  ids int32 [B][T], attn uint8 [B][T]; a token is a candidate iff attn != 0 and its id is none of
+   cls_id / sep_id / pad_id.  Token t of global sample g = sample_offset + b owns the Philox group g * T + t of (seed, step, site
+   DROPOUT_SITE_MLM): word 0 selects it iff word0 < thresh (= floor(p * 2^32)); word 1 picks the action - below floor(0.8 * 2^32) the id
+   becomes mask_id, below floor(0.9 * 2^32) it becomes mulhi(word2, V), else it is kept.  A pure function of (seed, step, global sample,
+   position): no launch geometry, no padded / packed layout enters.
+   Written: ids_masked [B][T]; labels [B][T] = the original id where selected, -1 elsewhere; rows [B*T] = the selected tokens' row indices,
+   ascending - b * T + t, or tok_row[b * T + t] (medmoe_text_pack) when tok_row is not null; row_labels aligned with rows; count [1].  The
+   tails of rows / row_labels past the count are not written.  One workgroup, the list positions come from a scan: no atomics, nothing is
+   read back.  B * T < 2^31, V >= 2, 0 <= mask_id < V, sample_offset >= 0, 0 <= thresh < 2^32 - anything else returns -2 before a launch. */
+int medmoe_mlm_mask(const int* ids, const unsigned char* attn, const int* tok_row, int* ids_masked, int* labels, int* rows, int* row_labels, int* count, int B, int T, int V, int cls_id, int sep_id, int pad_id, int mask_id, long long sample_offset, long long seed, long long step, long long thresh, hipStream_t stream);
+/* bf16 rows of D elements (D % 8 == 0, 16-byte aligned), k < min(*count, M_bound); the listed rows are distinct, so the add has one writer:
+   gather       dst[k] = src[rows[k]]                    scatter_add  dst[rows[k]] = bf16(dst[rows[k]] + src[k])
+   mul          dst[k] = bf16(a[k] * b[k]), and dst[k] = 0 for count <= k < M_bound */
+int medmoe_rows_gather(const void* src, const int* rows, const int* count, void* dst, int M_bound, int D, hipStream_t stream);
+int medmoe_rows_scatter_add(const void* src, const int* rows, const int* count, void* dst, int M_bound, int D, hipStream_t stream);
+int medmoe_rows_mul(const void* a, const void* b, const int* count, void* dst, int M_bound, int D, hipStream_t stream);
+/* The tied decoder fused with its cross-entropy.  z bf16 [M_bound][D], the first n = min(*count, M_bound) rows live (count on the device); E
+   bf16 [V][D]; bias fp32 [V]; row_labels int32 [M_bound] in [0, V) on the live rows.  logits = z E^T + bias on the bf16 MFMA with fp32
+   accumulation; no [M][V] array is written anywhere: a workgroup reduces its 64 x 256 tile to one (max, sum exp) pair per row, a second
+   kernel merges a row's ceil(V / 256) pairs in tile order, a third sums the rows in a fixed order.
+   Written: lse [M_bound] and terms [M_bound] = lse - logit[target] (both 0 at and past n); loss [1] = loss_scale / n * sum of the live
+   terms, 0 when n = 0; counts[0] = n, counts[1] = the live rows whose target logit equals the row's maximum.  A row at or past n is never
+   read into a result (its z is replaced by zeros as it is staged).  No atomics: two calls give the same bits.
+   D % 64 == 0, 64 <= D <= 1024, V >= 2, M_bound >= 1 - anything else returns -2 before a launch; z and E 16-byte aligned;
+   scratch_floats >= medmoe_vocab_ce_scratch(M_bound, V, D) = (2 ceil(V / 256) + 2) M_bound. */
+int medmoe_vocab_ce_fwd(const void* z, const void* E, const float* bias, const int* row_labels, const int* count, float loss_scale, float* lse, float* terms, float* loss, int* counts, float* scratch, long long scratch_floats, int M_bound, int V, int D, hipStream_t stream);
+/* scratch floats of medmoe_vocab_ce_fwd, 0 for a shape it refuses */
+long long medmoe_vocab_ce_scratch(int M_bound, int V, int D);
+/* Its backward, P = (softmax(logits) - onehot(target)) loss_scale / n recomputed tile by tile from lse (fp32, rounded to bf16 for the second
+   product) and never stored: _dx owns 64 token rows per workgroup, streams the vocabulary and WRITES dz = P E (bf16 [M_bound][D], rows at
+   and past n untouched); _dw owns 64 vocabulary rows, streams the token rows and ACCUMULATES dE [V][D] += P^T z, dbias [V] += sum over rows
+   of P (fp32).  Every output element has one owner: no atomics, two calls give the same bits; n = 0 launches nothing that writes.  Shapes
+   and refusals as medmoe_vocab_ce_fwd. */
+int medmoe_vocab_ce_bwd_dx(const void* z, const void* E, const float* bias, const int* row_labels, const float* lse, const int* count, float loss_scale, void* dz, int M_bound, int V, int D, hipStream_t stream);
+int medmoe_vocab_ce_bwd_dw(const void* z, const void* E, const float* bias, const int* row_labels, const float* lse, const int* count, float loss_scale, float* dE, float* dbias, int M_bound, int V, int D, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -120,6 +120,14 @@ class MedMoEConfig:
     # at the t-th update.  Engine.ema_weights() / eval_step(ema=True) evaluate on it, checkpoints and exports carry it
     ema_decay: float = 0.0
     ema_warmup: bool = False
+    # masked-language-model objective of the TRAINABLE text tower (reference losses.py:150-245, FLAVA's MaskedPredictionLoss): a
+    # training step draws a BERT 80 / 10 / 10 mask over mlm_prob of the non-special tokens on the chip (stream: dropout_seed, the step), runs
+    # the tower ONCE on the masked ids - the contrastive losses read that pass too - and adds mlm_weight * cross-entropy of the masked
+    # positions under a head tied to the word-embedding table.  mlm_mask_id: the [MASK] id of the tokenizer (103 in BERT's vocabularies)
+    text_mlm: bool = False
+    mlm_prob: float = 0.15
+    mlm_weight: float = 1.0
+    mlm_mask_id: int = 103
 
     @property
     def vit_frozen(self) -> bool:
@@ -216,6 +224,19 @@ class MedMoEConfig:
                 raise ValueError(f"vit_lora_targets must be a non-empty list of distinct names out of query / key / value, got {tg!r}")
             if not float(self.vit_lora_alpha) > 0.0:
                 raise ValueError(f"vit_lora_alpha must be > 0, got {self.vit_lora_alpha}")
+        if self.text_mlm:
+            if self.freeze_text or self.text_lora:
+                raise ValueError("text_mlm (model.mlm) with freeze_text=True (text.freeze_bert: true) or text_lora (text.lora: true): the decoder "
+                                 "is tied to the word-embedding table, which must train - set freeze_text=False without adapters")
+            if not 0.0 < float(self.mlm_prob) < 1.0:
+                raise ValueError(f"mlm_prob (model.mlm.prob) must be in (0, 1), got {self.mlm_prob}")
+            if not 0 <= int(self.mlm_mask_id) < self.vocab:
+                raise ValueError(f"mlm_mask_id (model.mlm.mask_token_id) must be in [0, vocab = {self.vocab}), got {self.mlm_mask_id}")
+            if not float(self.mlm_weight) > 0.0:
+                raise ValueError(f"mlm_weight (model.mlm.weight) must be > 0, got {self.mlm_weight}")
+            if self.deterministic:
+                raise NotImplementedError("text_mlm with deterministic: the objective needs the trainable text tower, which has no "
+                                          "deterministic form yet - a named follow-up (DESIGN 3e)")
         if self.expert_fp8 and self.expert_mx:
             raise ValueError("expert_fp8 and expert_mx are two formats of the same weights: set one")
         if self.expert_mx and (self.d_v % 32 or self.d_out % 64):

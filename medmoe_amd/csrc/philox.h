@@ -14,6 +14,8 @@
 //   image augmentation (augment.hip): site = DROPOUT_SITE_AUGMENT; global sample g owns the groups 4 g + {0 crop / flip / order,
 //              1 affine, 2 colour jitter}, whose words are turned into integers and uniform floats there
 //   LoRA adapters on the image tower: site = DROPOUT_SITE_VIT_LORA + layer, over the [B * n_tok][d_v] array of the layer's ln1
+//   masked-language-model mask (mlm.hip): site = DROPOUT_SITE_MLM; token t of global sample g owns the group g * T + t: word 0
+//              selects it (word < thresh), word 1 picks [MASK] / random / keep, word 2 the random id
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -22,6 +24,7 @@
 #define DROPOUT_SITE_VIT_DROP_PATH 0x40000000u
 #define DROPOUT_SITE_AUGMENT 0x20000000u
 #define DROPOUT_SITE_VIT_LORA 0x50000000u
+#define DROPOUT_SITE_MLM 0x60000000u
 
 struct DropRng {
   uint32_t k0, k1;      // the two halves of the seed

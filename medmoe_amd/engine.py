@@ -211,6 +211,8 @@ class Engine:
                                       "trainable tower's padded pass, not for the packed frozen one")
         if self.text_dropout:
             self._refuse_with_graph("text_hidden_dropout / text_attn_dropout", "model.model.text.hidden_dropout_prob / attention_probs_dropout_prob")
+        if cfg.text_mlm:
+            self._refuse_mlm_with_graph()
         # stochastic depth of the image tower (cfg.vit_drop_path).  train_step draws the per-sample scales of every site of the step
         # (ws["vit_dp"], [n_layer_v, 2, B] fp32: 0 | 1 / (1 - p_l); [:, 0] the attention branch, [:, 1] the feed-forward branch) and points
         # vit_drop_scales at them for its own forward and backward; None everywhere else: eval_step, forward_image outside a training step and the
@@ -292,6 +294,15 @@ class Engine:
             from .text_params import TextStore
             self.tstore = TextStore(cfg, self.device, self.params.text)
             self.params.text = self.tstore.as_dict()             # views of the flat buffers: an optimiser step updates them in place
+        # masked-language-model objective (cfg.text_mlm): the head's arena is stepped next to the towers'.  _mlm_pass = (step, loss
+        # scale) while the text pass that runs is to mask its ids and run the head (train_step, mlm_eval); None everywhere else: eval_step,
+        # embed* and classify_* never mask
+        self.mlm = None
+        self._mlm_pass = None
+        self._mlm_bufs: Dict[tuple, tuple] = {}                      # the mask launch's outputs per batch shape
+        self._seed = seed
+        if cfg.text_mlm:
+            self._make_mlm_head()
         self.apply_optimizer_groups()
         # weight EMA (cfg.ema_decay > 0): every arena this engine steps keeps an fp32 average, updated by its Adam launch;
         # ema_weights() points the working copies at it.  The Lightning module writes the key after the engine exists: optimizer_step looks
@@ -351,6 +362,34 @@ class Engine:
             raise NotImplementedError(f"{keys} > 0 ({hydra_keys}) with MEDMOE_GRAPH=1: the dropout step counter is a by-value launch "
                                       "argument, a replayed graph would repeat one step's masks")
 
+    @staticmethod
+    def _refuse_mlm_with_graph():
+        if os.environ.get("MEDMOE_GRAPH", "0") == "1":
+            raise NotImplementedError("text_mlm (model.mlm) with MEDMOE_GRAPH=1: the mask's step counter is a by-value launch argument, a "
+                                      "replayed graph would repeat one step's mask")
+
+    def _make_mlm_head(self):
+        self._refuse_mlm_with_graph()
+        from .mlm import MLMHead
+        self.mlm = MLMHead(self.cfg.d_t, self.cfg.vocab, self.device, self._seed)
+
+    def enable_mlm(self, prob: float = 0.15, weight: float = 1.0, mask_id: int = 103):
+        """Switch the masked-language-model objective on after construction (the Lightning module reads `model.mlm` when the engine already
+        exists): the config keys, their refusals, the head and its arena, the parameter groups and - with cfg.ema_decay > 0 - its average."""
+        c = self.cfg
+        old = (c.text_mlm, c.mlm_prob, c.mlm_weight, c.mlm_mask_id)
+        c.text_mlm, c.mlm_prob, c.mlm_weight, c.mlm_mask_id = True, float(prob), float(weight), int(mask_id)
+        try:
+            c.validate()
+            if self.mlm is None:
+                self._make_mlm_head()
+        except Exception:
+            c.text_mlm, c.mlm_prob, c.mlm_weight, c.mlm_mask_id = old
+            raise
+        self.apply_optimizer_groups()
+        if c.ema_decay > 0.0:
+            ema_.prepare(self.optimizer_stores().values())
+
     def optimizer_stores(self) -> Dict[str, object]:
         """kind (medmoe_amd.optim_groups) -> the arenas this engine steps."""
         out = {"vit": self.params}
@@ -358,6 +397,8 @@ class Engine:
             out["text"] = self.text_arena()
         if self.vlora is not None:
             out["vit_lora"] = self.vlora
+        if self.mlm is not None:
+            out["mlm"] = self.mlm.store
         return out
 
     def merged_image_params(self) -> Dict[str, torch.Tensor]:
@@ -853,6 +894,14 @@ class Engine:
         regenerates them from (cfg.dropout_seed, the step, the site)."""
         c, ws, lo = self.cfg, self.ws, self.lora
         rows = _TextRows(self, km, self.text_train_varlen, trainable=True)
+        rows.mlm = None
+        if self._mlm_pass is not None:
+            # the tower runs on the MASKED ids (the embedding forward and _text_embed_backward both read rows.ids32); the segment map was
+            # built from the original ids (prefetch_cap_lens): a [MASK] or random id does not change which pieces form a word
+            rows.mlm = ops.mlm_mask(ids32, km, cls_id=self.vocab.cls_id, sep_id=self.vocab.sep_id, pad_id=self.vocab.pad_id, mask_id=c.mlm_mask_id,
+                                    vocab=c.vocab, seed=c.dropout_seed, step=self._mlm_pass[0], p=c.mlm_prob, sample_offset=self.rank * self.B,
+                                    tok_row=rows.tok_row, out=self._mlm_out(ids32))
+            ids32 = rows.mlm[0]
         rows.ids32, rows.tt32 = ids32, tt32
         rows.drop_step = self.dropout_step if training and self.text_dropout else None
         rows.lora_drop_step = self.dropout_step if training and lo is not None and c.text_lora_dropout > 0.0 else None
@@ -868,6 +917,19 @@ class Engine:
                              ws[f"t_dg{l}"], ws[f"t_x2{l}"], ws[f"t_st2{l}"], ws[f"t_x{l + 1}"], ws[f"t_lu{l}"] if lo is not None else None)
         self._tp = rows
         self._text_tail(rows, ids, self._text_blocks(rows, x, bufs))
+        if rows.mlm is not None:
+            _, _, sel_rows, sel_labels, count = rows.mlm
+            self.mlm.forward(rows.last.view(-1, c.d_t), sel_rows, sel_labels, count, self.tstore.w16("word_embeddings"), self._mlm_pass[1])
+
+    def _mlm_out(self, ids32):
+        """The mask launch's five outputs (ids_masked, labels, rows, row_labels, count), kept per batch shape."""
+        key = tuple(ids32.shape)
+        hit = self._mlm_bufs.get(key)
+        if hit is None:
+            n, dev = ids32.numel(), self.device
+            hit = self._mlm_bufs[key] = (torch.empty_like(ids32), torch.empty_like(ids32), torch.empty(n, device=dev, dtype=I32),
+                                         torch.empty(n, device=dev, dtype=I32), torch.zeros(1, device=dev, dtype=I32))
+        return hit
 
     def _text_embed(self, rows, ids32, tt32, x):
         """x = LayerNorm(word + position + token-type embeddings), on all B x T rows or packed."""
@@ -955,6 +1017,8 @@ class Engine:
             ops.call("text_aggregate_bwd", d_words, d_txt_g, tp.seg, dH, B, T, Dt)
         dy, d1, d2 = ws["t_da"], ws["t_db"], ws["t_dc"]
         dy.copy_(dH)                                                 # the last layer's output is always among the summed states
+        if getattr(tp, "mlm", None) is not None:                     # + the MLM head's d hidden at the selected rows; the tied table's and the head's gradients
+            self.mlm.backward(ts.grad("word_embeddings"), dy)
         for l in range(c.n_layer_t - 1, -1, -1):
             b = f"layer.{l}."
             st1, st2 = ws[f"t_st1{l}"], ws[f"t_st2{l}"]
@@ -1478,12 +1542,44 @@ class Engine:
                 self.text_arena().zero_grad()
             if self.vlora is not None:
                 self.vlora.zero_grad()
+            if self.mlm is not None:
+                self.mlm.store.zero_grad()
         try:
+            if self.mlm is not None:                                # this step's mask; the head's loss carries mlm_weight and loss_scale
+                self._mlm_pass = (self.dropout_step, self.cfg.mlm_weight * loss_scale)
             self._forward_both(batch, training=True)
-            return self._train_step_rest(batch, optimizer, loss_scale)
+            out = self._train_step_rest(batch, optimizer, loss_scale)
+            if self.mlm is not None:
+                out.update(self._mlm_result(self.cfg.mlm_weight))
+                out["loss"] = out["loss"] + self.cfg.mlm_weight * out["mlm_loss"]
+            return out
         finally:
             self.vit_drop_scales = None                             # whatever runs next (evaluation, a bare forward_image) drops nothing
             self._vit_lora_drop_step = None
+            self._mlm_pass = None
+
+    def _mlm_result(self, weight: float):
+        """mlm_loss (the head's loss without mlm_weight; it follows loss_scale like the other parts) and mlm_acc (the share of the masked
+        positions whose target is the arg max) of the last MLM pass: device scalars."""
+        b = self.mlm.buf
+        return {"mlm_loss": b.loss[0] / weight, "mlm_acc": b.counts[1].float() / b.counts[0].clamp(min=1).float()}
+
+    def mlm_eval(self, batch: Dict[str, torch.Tensor], step: int = 0, ema: bool = False):
+        """mlm_loss / mlm_acc of a batch under the FIXED mask of `step` (the same step gives the same mask), forward only: the text pass of
+        an evaluation (no dropout) on the masked ids and the head; no gradient, Adam moment, master or working parameter is written."""
+        if self.mlm is None:
+            raise RuntimeError("mlm_eval: this engine has no MLM head (cfg.text_mlm)")
+        if ema and not self._ema_active:
+            with self.ema_weights():
+                return self.mlm_eval(batch, step)
+        self._alloc(batch["ids"].shape[0])
+        self.prefetch_cap_lens(batch["ids"])
+        self._mlm_pass = (int(step), 1.0)
+        try:
+            self.forward_text(batch["ids"], batch["attn_mask"], batch.get("token_type"))
+            return self._mlm_result(1.0)
+        finally:
+            self._mlm_pass = None
 
     def _forward_image_train(self, images: torch.Tensor):
         """forward_image of a training step: with cfg.vit_drop_path > 0 under the stochastic-depth scales of self.dropout_step, drawn here by
@@ -1523,6 +1619,9 @@ class Engine:
         if self.vlora is not None and self.dist and optimizer:    # the image adapters' gradient: one more all-reduce, as the text arena's
             from . import dist as D_
             D_.allreduce_mean_(self.vlora.g32, comm=self.grad_comm(self.vlora))
+        if self.mlm is not None and self.dist and optimizer:      # the MLM head's gradient likewise
+            from . import dist as D_
+            D_.allreduce_mean_(self.mlm.store.g32, comm=self.grad_comm(self.mlm.store))
         self.dropout_step += 1                                      # the next call draws new masks (evaluation never advances it)
         if optimizer:
             self.optimizer_step()
@@ -1546,7 +1645,8 @@ class Engine:
         if self._ema_active:
             raise RuntimeError("optimizer_step inside ema_weights(): the working copies hold the averaged weights - evaluate only")
         lr = c.lr if lr is None else lr
-        side = [a for a in (text, self.vlora) if a is not None]     # the arenas next to the image one: ONE clip norm over all of them
+        mlm = self.mlm.store if self.mlm is not None else None
+        side = [a for a in (text, self.vlora, mlm) if a is not None]     # the arenas next to the image one: ONE clip norm over all of them
         parts = [a.sumsq() for a in side]
         total = image.sumsq()
         for part in parts:

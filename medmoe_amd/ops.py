@@ -721,6 +721,9 @@ _SIGS = {
     "l2_normalize": "ppiif", "sim_topk": "ppiiiipppl", "sim_rank": "pppiiippl",
     # supervised classification (csrc/classify.hip)
     "cls_head_logits": "ppppiii", "cls_head_step": "pppppiffpppppppliii", "auroc_counts": "pppii",
+    # masked-language-model objective (csrc/mlm.hip)
+    "mlm_mask": "ppppppppiiiiiiillll", "rows_gather": "ppppii", "rows_scatter_add": "ppppii", "rows_mul": "ppppii",
+    "vocab_ce_fwd": "pppppfpppppliii", "vocab_ce_bwd_dx": "ppppppfpiii", "vocab_ce_bwd_dw": "ppppppfppiii",
 }
 
 
@@ -1138,3 +1141,163 @@ def auroc_counts(scores, targets):
     out = torch.empty((C, 4), device=scores.device, dtype=torch.int64)
     call(name, scores, targets, out, N, C)
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# masked-language-model objective of the text tower (csrc/mlm.hip)
+# ---------------------------------------------------------------------------------------------
+DROPOUT_SITE_MLM = 0x60000000          # token t of global sample g owns the group g * T + t of this site (csrc/philox.h)
+VOCAB_CE_MAX_D = 1024
+VOCAB_CE_TILE = 256                    # vocabulary entries per forward tile: a row leaves ceil(V / 256) (max, sum) pairs
+
+
+def _mlm_int32(name, arg, t, numel=None):
+    _need(t, torch.int32, f"{name}: {arg}")
+    if not t.is_contiguous() or (numel is not None and t.numel() < numel):
+        raise ValueError(f"{name}: {arg} must be contiguous" + (f" and hold at least {numel} elements" if numel is not None else ""))
+
+
+def mlm_mask(ids, attn, *, cls_id: int, sep_id: int, pad_id: int, mask_id: int, vocab: int, seed: int, step: int, p: float,
+             sample_offset: int = 0, tok_row=None, out=None):
+    """The step's MLM mask (medmoe_mlm_mask; the rule is in include/medmoe_hip.h).  ids int32 [B, T], attn uint8 [B, T]; tok_row (int32
+    [B * T], text_pack) makes `rows` name packed rows.  Returns (ids_masked [B, T], labels [B, T], rows [B * T], row_labels [B * T],
+    count [1]) - device tensors, nothing is read back; `out` may hand the same five in to reuse buffers."""
+    name = "mlm_mask"
+    _need(ids, torch.int32, f"{name}: ids"); _need(attn, torch.uint8, f"{name}: attn")
+    if ids.dim() != 2 or tuple(attn.shape) != tuple(ids.shape) or not ids.is_contiguous() or not attn.is_contiguous():
+        raise ValueError(f"{name}: ids and attn must be contiguous [B, T] tensors of one shape")
+    B, T = ids.shape
+    if B < 1 or T < 1 or B * T >= 1 << 31:
+        raise ValueError(f"{name}: B * T must be in 1 .. 2^31 - 1")
+    if not 0.0 < float(p) < 1.0:
+        raise ValueError(f"{name}: p must be in (0, 1), got {p}")
+    if vocab < 2 or not 0 <= mask_id < vocab:
+        raise ValueError(f"{name}: mask_id must be in [0, vocab = {vocab}), got {mask_id}")
+    if sample_offset < 0:
+        raise ValueError(f"{name}: sample_offset must be >= 0")
+    if tok_row is not None:
+        _mlm_int32(name, "tok_row", tok_row, B * T)
+    dev = ids.device
+    if out is None:
+        out = (torch.empty_like(ids), torch.empty_like(ids), torch.empty(B * T, device=dev, dtype=torch.int32),
+               torch.empty(B * T, device=dev, dtype=torch.int32), torch.empty(1, device=dev, dtype=torch.int32))
+    ids_masked, labels, rows, row_labels, count = out
+    for arg, t, n in (("ids_masked", ids_masked, B * T), ("labels", labels, B * T), ("rows", rows, B * T), ("row_labels", row_labels, B * T),
+                      ("count", count, 1)):
+        _mlm_int32(name, arg, t, n)
+    rng = dropout_rng(seed, step, DROPOUT_SITE_MLM, float(p))
+    call(name, ids, attn, tok_row, ids_masked, labels, rows, row_labels, count, B, T, vocab, cls_id, sep_id, pad_id, mask_id, sample_offset,
+         rng[0], rng[1], rng[3])
+    return ids_masked, labels, rows, row_labels, count
+
+
+def _rows_check(name, count, M_bound, D, **bf16):
+    for arg, t in bf16.items():
+        _need(t, torch.bfloat16, f"{name}: {arg}")
+        if not t.is_contiguous() or t.shape[-1] != D or t.data_ptr() % 16:
+            raise ValueError(f"{name}: {arg} must be contiguous [rows, {D}] and 16-byte aligned")
+    _mlm_int32(name, "count", count, 1)
+    if D % 8 or M_bound < 1:
+        raise ValueError(f"{name}: D must be a multiple of 8 and M_bound >= 1")
+
+
+def rows_gather(src, rows, count, dst):
+    """dst[k] = src[rows[k]] for k < min(count, dst.shape[0]) (bf16 rows; count and rows live on the device)."""
+    M_bound, D = dst.shape
+    _rows_check("rows_gather", count, M_bound, D, src=src, dst=dst)
+    _mlm_int32("rows_gather", "rows", rows, M_bound)
+    call("rows_gather", src, rows, count, dst, M_bound, D)
+    return dst
+
+
+def rows_scatter_add(src, rows, count, dst):
+    """dst[rows[k]] += src[k] for k < min(count, src.shape[0]); the listed rows are distinct (one writer each)."""
+    M_bound, D = src.shape
+    _rows_check("rows_scatter_add", count, M_bound, D, src=src, dst=dst)
+    _mlm_int32("rows_scatter_add", "rows", rows, M_bound)
+    call("rows_scatter_add", src, rows, count, dst, M_bound, D)
+    return dst
+
+
+def rows_mul(a, b, count, dst):
+    """dst[k] = a[k] * b[k] for k < count, 0 for the rows from count to dst.shape[0]."""
+    M_bound, D = dst.shape
+    _rows_check("rows_mul", count, M_bound, D, a=a, b=b, dst=dst)
+    if a.shape[0] < M_bound or b.shape[0] < M_bound:
+        raise ValueError("rows_mul: a and b must hold at least dst.shape[0] rows")
+    call("rows_mul", a, b, count, dst, M_bound, D)
+    return dst
+
+
+def vocab_ce_scratch(M_bound: int, V: int, D: int) -> int:
+    return _scratch_query("vocab_ce_scratch", M_bound, V, D)
+
+
+def _vocab_ce_check(name, z, E, bias, row_labels, count):
+    _need(z, torch.bfloat16, f"{name}: z"); _need(E, torch.bfloat16, f"{name}: E"); _need(bias, torch.float32, f"{name}: bias")
+    if z.dim() != 2 or E.dim() != 2 or not z.is_contiguous() or not E.is_contiguous() or not bias.is_contiguous():
+        raise ValueError(f"{name}: z must be a contiguous [M_bound, D], E a contiguous [V, D] and bias a contiguous [V]")
+    M_bound, D = z.shape
+    V = E.shape[0]
+    if D % 64 or not 64 <= D <= VOCAB_CE_MAX_D:
+        raise ValueError(f"{name}: z has D = {D}; D must be a multiple of 64 in 64 .. {VOCAB_CE_MAX_D}")
+    if E.shape[1] != D:
+        raise ValueError(f"{name}: E has {E.shape[1]} columns, z has D = {D}")
+    if V < 2 or bias.numel() != V:
+        raise ValueError(f"{name}: V = {V} must be >= 2 and bias must hold V values, got {bias.numel()}")
+    if M_bound < 1:
+        raise ValueError(f"{name}: z must hold at least one row")
+    if z.data_ptr() % 16 or E.data_ptr() % 16:
+        raise ValueError(f"{name}: z and E must start at a 16-byte boundary")
+    _mlm_int32(name, "row_labels", row_labels, M_bound)
+    _mlm_int32(name, "count", count, 1)
+    return M_bound, V, D
+
+
+def _vocab_ce_f32(name, arg, t, numel):
+    _need(t, torch.float32, f"{name}: {arg}")
+    if not t.is_contiguous() or t.numel() < numel:
+        raise ValueError(f"{name}: {arg} must be contiguous and hold at least {numel} floats")
+
+
+def vocab_ce_fwd(z, E, bias, row_labels, count, loss_scale: float = 1.0, lse=None, terms=None, loss=None, counts=None, scratch=None):
+    """Decoder + cross-entropy in one pass (medmoe_vocab_ce_fwd): logits = z [M_bound, D] @ E [V, D]^T + bias are never stored.  The first
+    `count` (int32 device tensor) rows of z are live.  Returns (loss fp32 [1] = loss_scale * mean over the live rows of lse - logit[target],
+    counts int32 [2] = (live rows, rows whose target is the arg max), lse fp32 [M_bound], terms fp32 [M_bound])."""
+    name = "vocab_ce_fwd"
+    M_bound, V, D = _vocab_ce_check(name, z, E, bias, row_labels, count)
+    dev = z.device
+    lse = torch.empty(M_bound, device=dev, dtype=torch.float32) if lse is None else lse
+    terms = torch.empty(M_bound, device=dev, dtype=torch.float32) if terms is None else terms
+    loss = torch.empty(1, device=dev, dtype=torch.float32) if loss is None else loss
+    counts = torch.empty(2, device=dev, dtype=torch.int32) if counts is None else counts
+    need = vocab_ce_scratch(M_bound, V, D)
+    scratch = torch.empty(need, device=dev, dtype=torch.float32) if scratch is None else scratch
+    _vocab_ce_f32(name, "lse", lse, M_bound); _vocab_ce_f32(name, "terms", terms, M_bound); _vocab_ce_f32(name, "loss", loss, 1)
+    _vocab_ce_f32(name, "scratch", scratch, need)
+    _mlm_int32(name, "counts", counts, 2)
+    call(name, z, E, bias, row_labels, count, float(loss_scale), lse, terms, loss, counts, scratch, scratch.numel(), M_bound, V, D)
+    return loss, counts, lse, terms
+
+
+def vocab_ce_bwd(z, E, bias, row_labels, lse, count, loss_scale: float = 1.0, dz=None, dE=None, dbias=None):
+    """Backward of vocab_ce_fwd from its lse (medmoe_vocab_ce_bwd_dx / _dw): dz (bf16 [M_bound, D]) is WRITTEN on the live rows when given;
+    dE (fp32 [V, D]) and dbias (fp32 [V]) are ACCUMULATED into when given (both or neither).  No atomics, nothing of size [M, V]."""
+    name = "vocab_ce_bwd"
+    M_bound, V, D = _vocab_ce_check(name, z, E, bias, row_labels, count)
+    _vocab_ce_f32(name, "lse", lse, M_bound)
+    if dz is None and dE is None:
+        raise ValueError(f"{name}: nothing to compute (dz and dE are both None)")
+    if (dE is None) != (dbias is None):
+        raise ValueError(f"{name}: dE and dbias come together")
+    if dz is not None:
+        _need(dz, torch.bfloat16, f"{name}: dz")
+        if tuple(dz.shape) != (M_bound, D) or not dz.is_contiguous():
+            raise ValueError(f"{name}: dz must be a contiguous [{M_bound}, {D}]")
+        call("vocab_ce_bwd_dx", z, E, bias, row_labels, lse, count, float(loss_scale), dz, M_bound, V, D)
+    if dE is not None:
+        _vocab_ce_f32(name, "dE", dE, V * D); _vocab_ce_f32(name, "dbias", dbias, V)
+        if tuple(dE.shape) != (V, D):
+            raise ValueError(f"{name}: dE must be [{V}, {D}]")
+        call("vocab_ce_bwd_dw", z, E, bias, row_labels, lse, count, float(loss_scale), dE, dbias, M_bound, V, D)
+    return dz, dE, dbias

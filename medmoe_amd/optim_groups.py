@@ -81,7 +81,7 @@ def depth_of(kind: str, names: Sequence[str]) -> Tuple[Dict[str, int], int]:
                 out[n] = sum(depths[:int(mm.group(1)) + 1])
             else:
                 out[n] = 0 if n.startswith("embeddings.") else L + 1
-    elif kind == "swin_moe":
+    elif kind in ("swin_moe", "mlm"):      # mlm: the masked-prediction head behind the text tower
         L = 0
         out = {n: 1 for n in names}                                  # behind the tower: depth L + 1, multiplier 1
     else:

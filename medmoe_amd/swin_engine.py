@@ -42,6 +42,9 @@ class SwinEngine:
         if engine.cfg.vit_frozen:
             raise NotImplementedError("freeze_vit / vit_lora (vision.freeze_cnn / vision.lora_vit) with the Swin-T encoder (vision.arch = swin_t, "
                                       "SwinEngine): the frozen backbone and its adapters are built for the engine's ViT tower (DESIGN 3n)")
+        if engine.cfg.text_mlm:
+            raise NotImplementedError("text_mlm (model.mlm) with the Swin-T encoder (vision.arch = swin_t, SwinEngine): the masked-language-model "
+                                      "objective is wired into the ViT Engine's training step (DESIGN 3r)")
         self.eng, self.enc, self.cfg = engine, encoder, engine.cfg
         self.device = encoder.dev
         self.train_text = engine.train_text

@@ -8,10 +8,12 @@ argument order, defaults and return containers, computed by medmoe_amd's HIP ker
   SoftGLORIALocalContrastiveLoss     losses.py:1111-1214 } row by a caption-to-caption score matrix and two thresholds (softXEnt :796-803)
   HardNegativeContrastiveLoss        losses.py:885-927   (margin loss on the nmax hardest in-batch negatives)
   ZEROGlobalContrastiveLoss / ZEROLocalContrastiveLoss   losses.py:740-755, 929-952 (ablation switches: the loss is 0)
+  MaskedPredictionHead / MaskedPredictionLoss            losses.py:150-245 (masked-token prediction; DESIGN 3r: the decoder and its
+                                                         cross-entropy are one fused pass, the loss class never forms the logits)
 
 Inputs must be CUDA tensors; gradients flow to the image-side inputs and to the text side (the local loss differentiates the word
 embeddings for the 196- / 64-region geometries; the reference experiment freezes the text tower, med-moe.yaml:35).  Variants the reference config never selects
-(FLAVA pretraining losses) are out of scope.
+(the other FLAVA pretraining losses: ITM, MIM, the multimodal heads) are out of scope.
 """
 import math
 from dataclasses import dataclass
@@ -407,3 +409,121 @@ def contrastive_loss_with_temperature(embeddings_a: Tensor, embeddings_b: Tensor
         loss_a, loss_b = F.cross_entropy(la, labels, **kw), F.cross_entropy(lb, labels, **kw)
         loss = (loss_a + loss_b) / 2
     return ContrastiveLossOutput(loss=loss, logits_a=la, logits_b=lb, loss_a=loss_a, loss_b=loss_b)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------------
+# masked-token prediction (reference losses.py:150-245; medmoe_amd/mlm.py, csrc/mlm.hip)
+# ------------------------------------------------------------------------------------------------------------------------------------------
+@dataclass
+class MaskedPredictionLossOutput(OrderedDict):
+    logits: Optional[Tensor]
+    loss: Tensor
+
+    def __post_init__(self):                                         # out["loss"] as well as out.loss, as the reference's ModelOutput gives
+        self["logits"], self["loss"] = self.logits, self.loss
+
+
+class MaskedPredictionHead(nn.Module):
+    """The reference's prediction head: dense -> GELU -> LayerNorm -> decoder (no bias of its own) + an output-only bias.  `forward` is the
+    reference's - it returns the logits [..., vocab], for inspection and decoding, and runs without autograd (dense + GELU and the decoder
+    on the bf16 NT GEMM, the LayerNorm kernel in between).  Training goes through MaskedPredictionLoss, which never forms the logits."""
+
+    def __init__(self, hidden_size: int = 768, vocab_size: int = 30522, transform_act_fn: Any = nn.functional.gelu, layer_norm_eps: float = 1e-5,
+                 use_fp32_layer_norm: bool = True, **kwargs: Any):
+        super().__init__()
+        if transform_act_fn is not nn.functional.gelu:
+            raise NotImplementedError("MaskedPredictionHead: the fused transform computes GELU (the reference default)")
+        self.dense = nn.Linear(hidden_size, hidden_size)
+        self.transform_act_fn = transform_act_fn
+        self.layer_norm = nn.LayerNorm(hidden_size, eps=layer_norm_eps)      # statistics in fp32 either way
+        self.decoder = nn.Linear(hidden_size, vocab_size, bias=False)       # tie: head.decoder.weight = the word-embedding Parameter
+        self.bias = nn.Parameter(torch.zeros(vocab_size))
+        self.hidden_size, self.vocab_size = hidden_size, vocab_size
+
+    @torch.no_grad()
+    def forward(self, hidden_states: Tensor) -> Tensor:
+        D, V = self.hidden_size, self.vocab_size
+        x = hidden_states.detach().reshape(-1, D).to(torch.bfloat16).contiguous()
+        M, dev = x.shape[0], x.device
+        t = torch.empty_like(x)
+        ops.gemm_nt(x, self.dense.weight.detach().to(torch.bfloat16).contiguous(), t, bias=_f32c(self.dense.bias), epi=ops.EPI_GELU)
+        z = torch.empty_like(x)
+        stat = torch.empty(2, M, device=dev, dtype=torch.float32)
+        ops.layernorm_fwd(t, _f32c(self.layer_norm.weight), _f32c(self.layer_norm.bias), z, stat[0], stat[1], self.layer_norm.eps)
+        Vp = (V + 7) // 8 * 8                                        # the NT GEMM's column count: whole 16-byte groups (pad rows are zeros)
+        w = torch.zeros(Vp, D, device=dev, dtype=torch.bfloat16)
+        w[:V] = self.decoder.weight.detach()
+        b = torch.zeros(Vp, device=dev, dtype=torch.float32)
+        b[:V] = self.bias.detach()
+        logits = torch.empty(M, Vp, device=dev, dtype=torch.float32)
+        ops.gemm_nt(z, w, logits, bias=b)
+        return logits[:, :V].reshape(*hidden_states.shape[:-1], V)
+
+
+class _MaskedPredictionFn(torch.autograd.Function):
+    """loss = mean over the rows with a label of -log softmax(head(hidden))[label]: forward and backward in one pass of launches
+    (medmoe_amd.mlm.head_forward / head_backward), the gradients kept for `backward`, which scales them by the incoming gradient."""
+
+    @staticmethod
+    def forward(ctx, hidden, labels, ignore_index, eps, w1, b1, gamma, beta, dec, vbias):
+        from medmoe_amd import mlm as M_
+        D, V = w1.shape[0], dec.shape[0]
+        dev = hidden.device
+        h16 = hidden.detach().reshape(-1, D).to(torch.bfloat16).contiguous()
+        R = h16.shape[0]
+        lab = labels.detach().reshape(-1).to(dev)
+        sel = lab.ne(ignore_index)
+        # the selected rows first, in ascending order, without a host copy: a stable sort of the "not selected" flag
+        rows = torch.argsort((~sel).to(torch.int8), stable=True).to(torch.int32)
+        row_labels = lab[rows.long()].to(torch.int32).contiguous()
+        count = sel.sum().to(torch.int32).reshape(1)
+        buf = M_.HeadBuffers(R, D, V, dev)
+        w16 = w1.detach().to(torch.bfloat16).contiguous()
+        e16 = dec.detach().to(torch.bfloat16).contiguous()
+        f = lambda t: t.detach().float().contiguous()
+        loss, counts = M_.head_forward(buf, h16, rows, row_labels, count, w16, f(b1), f(gamma), f(beta), e16, f(vbias), 1.0, float(eps))
+        g = {"w1": torch.zeros(D, D, device=dev), "b1": torch.zeros(D, device=dev), "gamma": torch.zeros(D, device=dev),
+             "beta": torch.zeros(D, device=dev), "dec": torch.zeros(V, D, device=dev), "vbias": torch.zeros(V, device=dev)}
+        dh = torch.zeros(R, D, device=dev, dtype=torch.bfloat16)
+        M_.head_backward(buf, rows, row_labels, count, w16.t().contiguous(), f(gamma), e16, f(vbias), 1.0, g["w1"], g["b1"], g["gamma"], g["beta"],
+                         g["dec"], g["vbias"], dh)
+        ctx.grads = (dh.view(hidden.shape), g)
+        ctx.dtypes = (hidden.dtype, w1.dtype, b1.dtype, gamma.dtype, beta.dtype, dec.dtype, vbias.dtype)
+        ctx.mark_non_differentiable(counts)
+        return loss[0].clone(), counts.clone()
+
+    @staticmethod
+    def backward(ctx, gl, _gc):
+        dh, g = ctx.grads
+        dt = ctx.dtypes
+        s = gl.float()
+        return ((dh.float() * s).to(dt[0]), None, None, None, (g["w1"] * s).to(dt[1]), (g["b1"] * s).to(dt[2]), (g["gamma"] * s).to(dt[3]),
+                (g["beta"] * s).to(dt[4]), (g["dec"] * s).to(dt[5]), (g["vbias"] * s).to(dt[6]))
+
+
+class MaskedPredictionLoss(nn.Module):
+    """The reference's constructor and forward(hidden_states, masked_labels).  The positions whose label differs from ignore_index are
+    gathered, pass through the head, and their cross-entropy against the tied decoder is ONE fused pass: `logits` of the result is None
+    (no [tokens, vocab] array exists; MaskedPredictionHead.forward gives logits where they are wanted).  No masked position gives loss 0,
+    not NaN - the reference's ignore_nan=True behaviour, whatever `ignore_nan` says.  `counts` of the last call: int32 (masked positions,
+    positions whose label is the arg max), a device tensor."""
+
+    def __init__(self, hidden_size: int = 768, vocab_size: int = 30522, transform_act_fn: Any = nn.functional.gelu, layer_norm_eps: float = 1e-5,
+                 ignore_index: int = -1, ignore_nan: bool = False, **kwargs: Any):
+        super().__init__()
+        self.cls = MaskedPredictionHead(hidden_size=hidden_size, vocab_size=vocab_size, transform_act_fn=transform_act_fn,
+                                        layer_norm_eps=layer_norm_eps)
+        self.ignore_index, self.vocab_size, self.ignore_nan = ignore_index, vocab_size, ignore_nan
+        self.counts: Optional[Tensor] = None
+
+    def forward(self, hidden_states: Tensor, masked_labels: Optional[Tensor] = None) -> MaskedPredictionLossOutput:
+        if masked_labels is None:
+            if self.training:
+                raise ValueError("MaskedPredictionLoss: masked labels must be present in training mode")
+            return MaskedPredictionLossOutput(logits=self.cls(hidden_states), loss=hidden_states.sum() * 0)
+        if not hidden_states.is_cuda:
+            raise RuntimeError("MaskedPredictionLoss: medmoe_amd kernels only run on the GPU (no CPU fallback)")
+        c = self.cls
+        loss, self.counts = _MaskedPredictionFn.apply(hidden_states, masked_labels, self.ignore_index, c.layer_norm.eps, c.dense.weight,
+                                                      c.dense.bias, c.layer_norm.weight, c.layer_norm.bias, c.decoder.weight, c.bias)
+        return MaskedPredictionLossOutput(logits=None, loss=loss)

@@ -23,7 +23,7 @@ def _get(cfg: Any, key: str, default=None):
 class MedMoEPretrainingLightningModule(_Base):
     def __init__(self, model: nn.Module, loss: Any, optimizer: Any = None, scheduler: Any = None,
                  compile: bool = False, num_classes: int = 5, fused_step: bool = False, optimizer_groups: Any = None,
-                 grad_comm_dtype: str = "fp32", ema: Any = None, retrieval: Any = None):
+                 grad_comm_dtype: str = "fp32", ema: Any = None, retrieval: Any = None, mlm: Any = None):
         """`fused_step` (MI355X build, `model.fused_step` in the config tree): training steps run `Engine.train_step` - the hand-scheduled
         forward / losses / backward with the embedding all-gather, the reduce-scatter of the gathered-key gradients, the per-layer
         gradient all-reduce overlapped with backward and the fused clip + Adam - instead of torch autograd + a torch optimizer.
@@ -48,7 +48,13 @@ class MedMoEPretrainingLightningModule(_Base):
         `local` (`+model.retrieval.local=true`, `local_k` 1..16, `local_agg` sum | mean): the epoch also keeps the batches' region
         and word features (medmoe_amd.retrieval.LocalBank) and reports val/i2t_local_R@k, val/t2i_local_* - every query's local_k best keys
         re-ranked with the weighted global + GLoRIA local similarity - and, with `zero_shot`, val/zs_local_acc@k.  Every key logged without
-        it keeps its value."""
+        it keeps its value.
+        `mlm` (`+model.mlm.weight=1.0 +model.mlm.prob=0.15 +model.mlm.mask_token_id=103 +model.mlm.validate=true`, fused step with a
+        trainable text tower - text.freeze_bert: false - and the ViT towers only): masked-token prediction as an auxiliary
+        objective.  A training step masks `prob` of the caption tokens on the chip, runs the text tower once on the masked ids and adds
+        `weight` x the cross-entropy of the masked positions under a head tied to the word embeddings (Engine.enable_mlm); the step reports
+        mlm_loss / mlm_acc.  `validate`: validation_step / test_step add val/mlm_loss and val/mlm_acc under the fixed mask of step 0.  The
+        head travels with the checkpoint (`mlm_head`, the reference's key names cls.dense.weight ... cls.bias) with its Adam state."""
         super().__init__()
         self.model = model
         self.loss_cfg = loss
@@ -84,6 +90,19 @@ class MedMoEPretrainingLightningModule(_Base):
                                       "flat stores and updated inside the fused Adam launch; the autograd path steps a torch optimizer")
         if self._ema_validate and not self._ema_decay > 0.0:
             raise ValueError("model.ema.validate=true needs model.ema.decay > 0: there is no average to validate on")
+        self._mlm = None
+        if mlm:
+            unknown = set(dict(mlm).keys()) - {"weight", "prob", "mask_token_id", "validate"}
+            if unknown:
+                raise KeyError(f"model.mlm: unknown keys {sorted(unknown)} (weight, prob, mask_token_id, validate)")
+            if not self.fused_step:
+                raise NotImplementedError("model.mlm needs fused_step=true (model.fused_step=true): the mask, the head and the fused vocabulary "
+                                          "loss run inside Engine.train_step")
+            if getattr(self.model, "swin", None) is not None:
+                raise NotImplementedError("model.mlm with vision.arch = swin_t: the objective is wired into the ViT Engine's training step "
+                                          "(DESIGN 3r)")
+            self._mlm = {"weight": float(_get(mlm, "weight", 1.0)), "prob": float(_get(mlm, "prob", 0.15)),
+                         "mask_token_id": int(_get(mlm, "mask_token_id", 103)), "validate": bool(_get(mlm, "validate", False))}
         self._retrieval, self._bank, self._zs, self._class_emb = self._retrieval_block(retrieval), None, None, None
         self._lbank, self._class_words = None, None              # model.retrieval.local: the local features of the epoch, the prompts' words
         if self.fused_step:
@@ -219,6 +238,8 @@ class MedMoEPretrainingLightningModule(_Base):
         c.grad_comm_dtype = self._grad_comm_dtype
         c.ema_decay, c.ema_warmup = self._ema_decay, self._ema_warmup
         c.validate()
+        if self._mlm is not None:                                    # refuses a frozen tower, adapters, a bad probability or [MASK] id
+            eng.enable_mlm(self._mlm["prob"], self._mlm["weight"], self._mlm["mask_token_id"])
         if self._ema_validate and getattr(self.model, "swin", None) is not None:
             raise NotImplementedError("model.ema.validate=true with vision.arch = swin_t: this model validates through its torch modules, "
                                       "which read the masters - evaluation on the averaged weights is a named follow-up (DESIGN 3k); the "
@@ -291,8 +312,11 @@ class MedMoEPretrainingLightningModule(_Base):
             raise RuntimeError("fused_training_step: construct the module with fused_step=True (model.fused_step=true)")
         eng, eb = self._fused_engine(), self._engine_batch(batch)
         out = eng.train_step(eb, optimizer=optimizer_step, zero_grad=zero_grad, loss_scale=loss_scale)
-        return {"loss": out["loss"], "l_loss": out["l_loss"], "g_loss": out["g_loss"], "classifier_loss": out["classifier_loss"],
-                "classifier_acc": out["classifier_acc"]}
+        res = {"loss": out["loss"], "l_loss": out["l_loss"], "g_loss": out["g_loss"], "classifier_loss": out["classifier_loss"],
+               "classifier_acc": out["classifier_acc"]}
+        if "mlm_loss" in out:                                        # model.mlm
+            res["mlm_loss"], res["mlm_acc"] = out["mlm_loss"], out["mlm_acc"]
+        return res
 
     def fused_eval_step(self, batch: Dict[str, Any]):
         """One batch through Engine.eval_step - the losses of `fused_training_step` forward only, nothing of the model or the optimiser
@@ -306,8 +330,11 @@ class MedMoEPretrainingLightningModule(_Base):
                 return self.model_step(batch)
         eng, eb = self._fused_engine(), self._engine_batch(batch)
         out = eng.eval_step(eb, ema=True) if self._ema_validate else eng.eval_step(eb)
-        return {"loss": out["loss"], "l_loss": out["l_loss"], "g_loss": out["g_loss"], "classifier_loss": out["classifier_loss"],
-                "classifier_acc": out["classifier_acc"]}
+        res = {"loss": out["loss"], "l_loss": out["l_loss"], "g_loss": out["g_loss"], "classifier_loss": out["classifier_loss"],
+               "classifier_acc": out["classifier_acc"]}
+        if self._mlm is not None and self._mlm["validate"]:          # val/mlm_loss, val/mlm_acc under the fixed mask of step 0
+            res.update(eng.mlm_eval(eb, step=0, ema=self._ema_validate))
+        return res
 
     def validation_step(self, batch, batch_idx: int = 0):                                # :114-125
         """The loss dict of a validation batch (`val/loss` is its "loss"): Engine.eval_step in fused mode, `model_step` otherwise."""
@@ -400,6 +427,8 @@ class MedMoEPretrainingLightningModule(_Base):
             out["text"] = m.engine.text_arena()
         if m.engine.vlora is not None:                               # vision.lora_vit: true - the image adapters' Adam state and average travel too
             out["vit_lora"] = m.engine.vlora
+        if getattr(m.engine, "mlm", None) is not None:               # model.mlm: the head's arena
+            out["mlm"] = m.engine.mlm.store
         return out
 
     def on_save_checkpoint(self, checkpoint: Dict[str, Any]) -> None:
@@ -424,12 +453,19 @@ class MedMoEPretrainingLightningModule(_Base):
                                               "ema": (st.e32 if st.ema_updates else st.p32[st.train_from:]).detach().cpu().clone()} for name, st in averaged.items()}
         # the text tower's dropout masks are a function of (seed, step, site, element): the step counter resumes where it stopped
         checkpoint["text_dropout_step"] = int(self.model.engine.dropout_step)
+        # model.mlm: the head is no torch module - its masters travel here under the reference's names (cls.dense.weight ... cls.bias)
+        if getattr(self.model.engine, "mlm", None) is not None:
+            from medmoe_amd.mlm import HEAD_PREFIX
+            checkpoint["mlm_head"] = {k[len(HEAD_PREFIX):]: v for k, v in self.model.engine.mlm.store.export_named().items()}
 
     def on_load_checkpoint(self, checkpoint: Dict[str, Any]) -> None:
         if self.fused_step and "text_dropout_step" in checkpoint:
             self.model.engine.dropout_step = int(checkpoint["text_dropout_step"])
         if not self.fused_step:
             return
+        if "mlm_head" in checkpoint and getattr(self.model.engine, "mlm", None) is not None:
+            from medmoe_amd.mlm import HEAD_PREFIX
+            self.model.engine.mlm.store.load_named({HEAD_PREFIX + k: v for k, v in checkpoint["mlm_head"].items()})
         stores = self._fused_stores()
         for name, rec in (checkpoint.get("fused_adam") or {}).items():
             if name not in stores:
