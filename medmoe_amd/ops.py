@@ -316,12 +316,55 @@ def gemm_tn(g, x, dw, *, db=None, x_rowmap=None, g_rowmap=None, row_off=None, n_
 _TN_FN = {}
 
 
+_LN_COL, _LN_ROW, _LN_X = "must hold D contiguous fp32 values", "must hold one contiguous fp32 value per row", "must be contiguous bf16 sized like x"
+
+
+def _ln_bad(name, nm, what, t):
+    if t.dtype != (torch.bfloat16 if what is _LN_X else torch.float32):
+        raise TypeError(f"{name}: {nm} {what}, got {t.dtype}")
+    raise ValueError(f"{name}: {nm} {what}, got {t.numel()} values{'' if t.is_contiguous() else ', not contiguous'}")
+
+
+def _ln_check(name, rows, D, per_col, per_row, like_x=()):
+    """What the LayerNorm kernels read and write without a bound of their own: per_col (gamma, beta, dgamma, dbeta) fp32, contiguous, D
+    values; per_row (mean, rstd) fp32, contiguous, at least one value per row; like_x (add) bf16, contiguous, rows * D values.  Entries are
+    (tensor, name); a tensor that is None stands for a null pointer the kernel accepts.  On the launch path: a few attribute reads each."""
+    if D <= 0 or D % 8 or D > 2048:
+        raise ValueError(f"{name}: D must be a multiple of 8 and <= 2048, got {D}")
+    f32 = torch.float32
+    for t, nm in per_col:
+        if t is not None:
+            if t.dtype is not f32 or t.numel() != D or not t.is_contiguous():
+                _ln_bad(name, nm, _LN_COL, t)
+            if not t.is_cuda:
+                _require_gpu(t, nm)
+    for t, nm in per_row:
+        if t is not None:
+            if t.dtype is not f32 or t.numel() < rows or not t.is_contiguous():
+                _ln_bad(name, nm, _LN_ROW, t)
+            if not t.is_cuda:
+                _require_gpu(t, nm)
+    for t, nm in like_x:
+        if t is not None:
+            if t.dtype is not torch.bfloat16 or t.numel() != rows * D or not t.is_contiguous():
+                _ln_bad(name, nm, _LN_X, t)
+            if not t.is_cuda:
+                _require_gpu(t, nm)
+
+
 def layernorm_fwd(x, gamma, beta, y, mean, rstd, eps):
+    """mean / rstd may be None (the kernel then keeps the statistic to itself); y is bf16 or fp32."""
     lib = load_library()
-    _need(x, torch.bfloat16, "x"); _need(gamma, torch.float32, "gamma"); _need(beta, torch.float32, "beta")
+    _need(x, torch.bfloat16, "x")
     rows, D = x.numel() // x.shape[-1], x.shape[-1]
     if not x.is_contiguous() or not y.is_contiguous() or y.numel() != x.numel():
         raise ValueError("layernorm_fwd: x/y must be contiguous and equally sized")
+    if y.dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError(f"layernorm_fwd: y must be bf16 or fp32, got {y.dtype}")
+    _require_gpu(y, "y")
+    _ln_check("layernorm_fwd", rows, D, ((gamma, "gamma"), (beta, "beta")), ((mean, "mean"), (rstd, "rstd")))
+    if gamma is None or beta is None:
+        raise ValueError("layernorm_fwd: gamma and beta are required")
     with _Timed("layernorm_fwd_kernel", 4.0 * rows * D, "byte"):
         rc = lib.medmoe_layernorm_fwd(_ptr(x), _ptr(gamma), _ptr(beta), _ptr(y), _ptr(mean), _ptr(rstd),
                                       _c.c_int(rows), _c.c_int(D), _c.c_float(eps),
@@ -358,6 +401,10 @@ def layernorm_bwd(dy, x, mean, rstd, gamma, dx, dgamma=None, dbeta=None, add=Non
         if not t.is_contiguous():
             raise ValueError(f"layernorm_bwd: {nm} must be contiguous")
     rows, D = x.numel() // x.shape[-1], x.shape[-1]
+    if mean is None or rstd is None or gamma is None or (dgamma is None) != (dbeta is None):
+        raise ValueError("layernorm_bwd: mean, rstd and gamma are required, dgamma and dbeta come together")
+    _ln_check("layernorm_bwd", rows, D, ((gamma, "gamma"), (dgamma, "dgamma"), (dbeta, "dbeta")), ((mean, "mean"), (rstd, "rstd")),
+              ((add, "add"),))
     if rows_dev is not None:
         if det is not None:
             raise ValueError("layernorm_bwd: no deterministic form with a device row count")
