@@ -347,6 +347,12 @@ int medmoe_set_option(int key, int value);
  * process launched - 0 gemm_nt_kernel (128x128 tile), 1 gemm_nt256_kernel, 2 gemm_nt512_kernel, 3 gemm_nt512_kernel GROUPED,
  * 4 gemm_nt4w_kernel, 5 gemm_nt4w_kernel GROUPED; -1 before the first call */
 int medmoe_last_gemm_nt_kernel(void);
+/* the same for the weight-gradient family: the kernel the most recent medmoe_gemm_tn / _staged / _det / _cols / _cols_det / _gram / _gram_det
+ * call of this process launched, generation * 8 + build * 2 + staged - generation 0 gemm_tn_kernel (128x128 tile), 1 gemm_tn512_kernel,
+ * 2 gemm_tn4w_kernel; build 0 plain, 1 MAPPED, 2 COLG, 3 COLG + SCALE; staged 1 when the partial tiles went through a scratch and a summing
+ * kernel; -1 before the first call.  A refused call leaves it unchanged.  split (may be NULL) receives that launch's nsplit: the row ranges
+ * per tile, or the ROWS per range in the grouped four-wave form. */
+int medmoe_last_gemm_tn_kernel(int* split);
 
 /* ---- fp8 (OCP e4m3fn) expert weights on the CDNA4 fp8 MFMA (BASELINE.json configs[4]; reference swin.py:18-30 projections) ---- */
 /* bf16 rows (gathered through rowmap when given; times colscale[slot_expert[row / rows_per_slot]][k] when given) -> e4m3 rows q[M][K]

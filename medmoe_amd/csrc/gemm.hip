@@ -836,6 +836,18 @@ __global__ __launch_bounds__(256) void tn_reduce_det_kernel(TnReduceArgs p) {
 
 int g_use_tn512 = 1, g_use_tn4w = 1, g_tn_rows = 1024, g_tn_min_rows = 2048, g_tn_rows4w = 0;      // options.h, keys 3, 8, 4, 9 and 10
 
+// Which TN kernel the most recent launch of this process took (medmoe_last_gemm_tn_kernel): host-side state only, written at every launch
+// site below and never by a refused call.  id = generation * 8 + build * 2 + staged:  generation 0 gemm_tn_kernel (128 x 128 tile),
+// 1 gemm_tn512_kernel, 2 gemm_tn4w_kernel;  build 0 plain, 1 MAPPED, 2 COLG, 3 COLG + SCALE;  staged 1: the partial tiles went through a
+// scratch and a summing kernel.  split: the launch's nsplit (row ranges per tile; the ROWS per range in the grouped four-wave form).
+enum { TN_G128 = 0, TN_G512 = 1, TN_G4W = 2, TN_B_PLAIN = 0, TN_B_MAPPED = 1, TN_B_COLG = 2, TN_B_SCALE = 3 };
+static int g_last_tn_kernel = -1, g_last_tn_split = 0;
+static inline void tn_ran(int gen, int build, bool staged, int split) { g_last_tn_kernel = gen * 8 + build * 2 + (staged ? 1 : 0); g_last_tn_split = split; }
+extern "C" int medmoe_last_gemm_tn_kernel(int* split) {
+  if (split) *split = g_last_tn_split;
+  return g_last_tn_kernel;
+}
+
 // Every entry point below: validate, tn_args, set what this form needs, launch, return mm_check_launch().
 static GemmTNArgs tn_args(const void* G, int ldg, const void* X, int ldx, float* dW, int ldw, int M, int Nn, int Kk) {
   GemmTNArgs p;
@@ -859,6 +871,7 @@ static void tn128_launch(GemmTNArgs& p, int nsplit, hipStream_t stream) {
   const int grid = p.tiles_n * p.tiles_k * nsplit * p.n_groups;
   if (p.x_rowmap || p.g_rowmap) hipLaunchKernelGGL(gemm_tn_kernel<true>, dim3(grid), dim3(256), 0, stream, p);
   else hipLaunchKernelGGL(gemm_tn_kernel<false>, dim3(grid), dim3(256), 0, stream, p);
+  tn_ran(TN_G128, (p.x_rowmap || p.g_rowmap) ? TN_B_MAPPED : TN_B_PLAIN, false, nsplit);
 }
 
 extern "C" int medmoe_gemm_tn(const void* G, int ldg, const void* X, int ldx, float* dW, int ldw,
@@ -879,6 +892,7 @@ extern "C" int medmoe_gemm_tn(const void* G, int ldg, const void* X, int ldx, fl
     if (p.nsplit > 1) ++g_mm_nondet;
     if (g_use_tn4w) hipLaunchKernelGGL(gemm_tn4w_kernel<false>, dim3(ntile * p.nsplit), dim3(256), 0, stream, p);
     else hipLaunchKernelGGL(gemm_tn512_kernel<false>, dim3(ntile * p.nsplit), dim3(512), 0, stream, p);
+    tn_ran(g_use_tn4w ? TN_G4W : TN_G512, TN_B_PLAIN, false, p.nsplit);
     return mm_check_launch();
   }
   // grouped (row_off) and/or ONE row-mapped operand, ragged row counts, Nn a multiple of 128: the MAPPED build
@@ -898,11 +912,13 @@ extern "C" int medmoe_gemm_tn(const void* G, int ldg, const void* X, int ldx, fl
       p.nsplit = (int)R;
       const int max_ranges = (int)(M / R) + n_groups;
       hipLaunchKernelGGL(gemm_tn4w_kernel<true>, dim3(ntile * max_ranges), dim3(256), 0, stream, p);
+      tn_ran(TN_G4W, TN_B_MAPPED, false, p.nsplit);
       return mm_check_launch();
     }
     p.nsplit = max(1, M / n_groups / g_tn_rows);
     if (g_use_tn4w) hipLaunchKernelGGL(gemm_tn4w_kernel<true>, dim3(ntile * p.nsplit * n_groups), dim3(256), 0, stream, p);
     else hipLaunchKernelGGL(gemm_tn512_kernel<true>, dim3(ntile * p.nsplit * n_groups), dim3(512), 0, stream, p);
+    tn_ran(g_use_tn4w ? TN_G4W : TN_G512, TN_B_MAPPED, false, p.nsplit);
     return mm_check_launch();
   }
   p.n_groups = n_groups;
@@ -942,6 +958,7 @@ extern "C" int medmoe_gemm_tn_staged(const void* G, int ldg, const void* X, int 
       } else {
         hipLaunchKernelGGL(tn_reduce_kernel, dim3(ntile * 64), dim3(256), 0, stream, scratch, dW, ldw, ntile, p.tiles_k, nvalid);
       }
+      tn_ran(TN_G4W, TN_B_PLAIN, true, p.nsplit);
       return mm_check_launch();
     }
   }
@@ -979,10 +996,12 @@ static int tn_cols_impl(const void* G, int ldg, const void* X, int ldx, float* d
     TnReduceArgs q{scratch, nullptr, dW, nullptr, nullptr, strideW, 0, ldw, Nn, Kk, p.tiles_n, p.tiles_k, 0, p.nsplit, (M + chunk - 1) / chunk,
                    n_groups, 0, tn_vec_ok(dW, ldw, strideW) ? 1 : 0};
     hipLaunchKernelGGL(tn_reduce_det_kernel, dim3((unsigned)(ntile * 64)), dim3(256), 0, stream, q);
+    tn_ran(TN_G4W, TN_B_COLG, true, p.nsplit);
     return mm_check_launch();
   }
   if (p.nsplit > 1) ++g_mm_nondet;
   hipLaunchKernelGGL((gemm_tn4w_kernel<false, true>), dim3((unsigned)(ntile * p.nsplit)), dim3(256), 0, stream, p);
+  tn_ran(TN_G4W, TN_B_COLG, false, p.nsplit);
   return mm_check_launch();
 }
 
@@ -1024,6 +1043,7 @@ static int tn_gram_impl(const void* A, int lda, const float* w, long long w_gstr
   p.nsplit = det ? 1 : tn_row_split(ntile, M);   // det: ONE workgroup adds to an output tile
   if (p.nsplit > 1) ++g_mm_nondet;
   hipLaunchKernelGGL((gemm_tn4w_kernel<false, true, true>), dim3((unsigned)(ntile * p.nsplit)), dim3(256), 0, stream, p);
+  tn_ran(TN_G4W, TN_B_SCALE, false, p.nsplit);
   return mm_check_launch();
 }
 
@@ -1072,6 +1092,7 @@ extern "C" int medmoe_gemm_tn_det(const void* G, int ldg, const void* X, int ldx
     hipLaunchKernelGGL(gemm_tn4w_kernel<true>, dim3(pl.slots), dim3(256), 0, stream, p);
   }
   hipLaunchKernelGGL(tn_reduce_det_kernel, dim3((unsigned)(n_groups * ntile * 64)), dim3(256), 0, stream, q);
+  tn_ran(TN_G4W, pl.kind == det_plan::TN_PLAIN ? TN_B_PLAIN : TN_B_MAPPED, true, pl.nsplit);
   return mm_check_launch();
 }
 

@@ -48,6 +48,31 @@ def _nt_label():
     return _NT_KERNELS.get(load_library().medmoe_last_gemm_nt_kernel(), "gemm_nt?")
 
 
+TN_GENERATIONS = ("gemm_tn_kernel", "gemm_tn512_kernel", "gemm_tn4w_kernel")
+TN_BUILDS = ("", "<MAPPED>", "<COLG>", "<COLG, SCALE>")
+
+
+def tn_kernel_id(generation: int, build: int = 0, staged: bool = False) -> int:
+    """The id medmoe_last_gemm_tn_kernel reports: generation 0 / 1 / 2 (128x128, tn512, tn4w), build 0..3 (plain, MAPPED, COLG, COLG + SCALE)."""
+    return generation * 8 + build * 2 + (1 if staged else 0)
+
+
+def last_gemm_tn_kernel():
+    """medmoe_last_gemm_tn_kernel: (id, split, label) of the most recent TN launch of this process - id as tn_kernel_id (-1 before the first
+    launch), split the launch's nsplit (the ROWS per range in the grouped four-wave form)."""
+    f = _FN.get("last_gemm_tn_kernel")
+    if f is None:
+        f = load_library().medmoe_last_gemm_tn_kernel
+        f.argtypes = [_c.POINTER(_c.c_int)]
+        f.restype = _c.c_int
+        _FN["last_gemm_tn_kernel"] = f
+    split = _c.c_int(0)
+    k = int(f(_c.byref(split)))
+    if k < 0:
+        return k, 0, "gemm_tn?"
+    return k, int(split.value), TN_GENERATIONS[k >> 3] + TN_BUILDS[(k >> 1) & 3] + (" staged" if k & 1 else "")
+
+
 def _ptr(t: Optional[torch.Tensor]):
     return _vp(0) if t is None else _vp(t.data_ptr())
 

@@ -28,14 +28,14 @@ def ops():
 
 
 @contextlib.contextmanager
-def forced(ops, opts):
-    """Kernel-selection options for one launch; the defaults come back whatever happens."""
+def forced(ops, opts, defaults=X.OPTION_DEFAULTS):
+    """Kernel-selection options for one launch; the defaults (of the family under test) come back whatever happens."""
     try:
         for k, v in opts:
             ops.set_option(k, v)
         yield
     finally:
-        for k, v in X.OPTION_DEFAULTS.items():
+        for k, v in defaults.items():
             ops.set_option(k, v)
 
 

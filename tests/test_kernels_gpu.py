@@ -262,10 +262,12 @@ def test_gemm_tn_groups_rowmap(ops):
 
 @pytest.mark.parametrize("mapped", ["x", "g", "none"])
 def test_gemm_tn512_groups_rowmap(ops, mapped):
-    """Grouped / row-mapped wgrad on the 256x256 kernel: ragged group sizes (not multiples of 32), Nn = 1.5 tiles."""
+    """Grouped / row-mapped wgrad on the 256x256 kernel: ragged group sizes (not multiples of 32), Nn = 1.5 tiles.  No workgroup of this
+    launch walks more than 4096 rows (the dispatch cuts every group into ranges of at most that), so the refill of the 8192-entry row-map
+    ring does not run here: test_gemm_tn_exact_gpu.py covers it (groups-ring, rowmap-12320: one range of 12320 rows)."""
     torch.manual_seed(8)
     Nn, Kk = 384, 512
-    counts = [30000, 4099, 0, 6213]        # the first group is longer than the 8192-entry row-map ring of one workgroup
+    counts = [30000, 4099, 0, 6213]        # the first group is longer than the row-map ring, but it is cut into ranges of 4096 rows
     M = sum(counts)
     bounds = [0]
     for c in counts: bounds.append(bounds[-1] + c)
