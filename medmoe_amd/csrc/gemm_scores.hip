@@ -277,7 +277,7 @@ __global__ __launch_bounds__(512, 2) void scores512_kernel(ScoresArgs p) {
       const int cj = t.c0 + wn * CW + c;
       const bool cap_ok = cj < p.n_cap;
       const int cap_i = p.cap_list[min(cj, p.n_cap - 1)];
-      const int cap = min(min(p.cap_lens[cap_i], p.T), TP);
+      const int cap = max(1, min(min(p.cap_lens[cap_i], p.T), TP));   // an empty caption counts as its first word (as in epilogue_t)
 #pragma unroll
       for (int tm = 0; tm < TMW; ++tm) {
         float mx = -INFINITY;

@@ -507,7 +507,7 @@ __global__ __launch_bounds__(256) void local_pair_kernel(const bf16_t* __restric
   const int fr = lane & 15, g = lane >> 4;
   const int pid = xcd_remap(blockIdx.x, gridDim.x);
   const int b = pid / Bc, i = pid - b * Bc;
-  const int cap = min(cap_lens[i], T);
+  const int cap = max(1, min(cap_lens[i], T));       // an empty caption counts as its first word (as in local_pair2 / local_pair3)
 
   // ---------------- GEMM1: S = ctx_b . W_i^T ----------------
   f32x4_t acc[MH][NTT];
@@ -894,7 +894,7 @@ __global__ __launch_bounds__(256) void local_scores_kernel(const bf16_t* __restr
   const int cap_j = min(tile_n * 2 + wc, n_cap - 1);        // this wave's caption slot (clamped; stores predicated)
   const int cap_i = cap_list ? cap_list[cap_j] : cap_j;
   const bool cap_ok = tile_n * 2 + wc < n_cap;
-  const int cap = min(min(cap_lens[cap_i], T), TP);
+  const int cap = max(1, min(min(cap_lens[cap_i], T), TP));   // an empty caption counts as its first word (as in the pair kernels)
 
   const bf16_t* src[NI];
 #pragma unroll
