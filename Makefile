@@ -36,7 +36,13 @@ check-topk: tools/topk_list_check.cpp $(CSRC)/topk_list.h
 	$(CXX) -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I$(CSRC) $< -o build/topk_list_check
 	build/topk_list_check
 
+# host-only check of the LAMB record enumeration (lamb_plan.h, shared with lamb.hip): random segment tables, under the sanitizers
+check-lamb-plan: tools/lamb_plan_check.cpp $(CSRC)/lamb_plan.h
+	@mkdir -p build
+	$(CXX) -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I$(CSRC) $< -o build/lamb_plan_check
+	build/lamb_plan_check
+
 clean:
 	rm -rf build $(LIB)
 
-.PHONY: all clean check-plan check-exchange check-topk
+.PHONY: all clean check-plan check-exchange check-topk check-lamb-plan

@@ -330,6 +330,30 @@ int medmoe_adam_groups_step_ema(float* p, const float* g, float* m, float* v, vo
 int medmoe_adam_step_ema_g16(float* p, const void* g_bf16, float* m, float* v, void* p_bf16, long long n, double lr, double beta1, double beta2, double eps, double weight_decay, int step, const float* grad_normsq, float max_norm, float grad_scale, float* ema, float one_minus_decay, hipStream_t stream);
 int medmoe_adam_groups_step_ema_g16(float* p, const void* g_bf16, float* m, float* v, void* p_bf16, long long n, const long long* run_end, const float* run_lr_mult, const float* run_wd_mult, int n_runs, double lr, double beta1, double beta2, double eps, double weight_decay, int decoupled, int step, const float* grad_normsq, float max_norm, float grad_scale, float* ema, float one_minus_decay, hipStream_t stream);
 
+/* LAMB on a flat arena (csrc/lamb.hip; You et al. 2019, apex FusedLAMB use_nvlamb = 0): three launches per arena and step.
+   Segments: seg_end (device int64[n_segs], ascending, last == n; a boundary may fall on any element), one per parameter tensor, with
+   seg_lr_mult / seg_wd_mult (device fp32[n_segs]) and rec_base (device int64[n_segs], from medmoe_lamb_plan on the HOST copy of seg_end).
+     moments: g' = g grad_scale clip (medmoe_adam_step's coefficient, kept in scratch[medmoe_lamb_coef_slot]), m, v as Adam's (m formed in
+              double and rounded once); u = (m / bc1) / (sqrt(v) / sqrt(bc2) + eps) +
+              weight_decay wd_mult p stays in registers, the partial sums of p^2 and u^2 per (chunk of medmoe_lamb_chunk() elements, segment)
+              go to `scratch` (scratch_floats >= medmoe_lamb_scratch_floats(n, n_segs)) with plain stores
+     ratios:  ratios[s] = |p_s| / |u_s| where both are > 0 and (always_adapt or weight_decay wd_mult_s != 0), else 1; min(., 1) with
+              trust_clip; a segment's records are added in index order.  ratios: 3 n_segs floats (the ratios, then (sum p^2, sum u^2) pairs)
+     apply:   p -= ((lr lr_mult_s) ratios[s]) u with u recomputed to the same bits, p_bf16 = bf16_rne(p); the _ema form averages as
+              medmoe_adam_step_ema does
+   No floating-point atomics, nothing read from the host: two runs from the same inputs give the same bits. */
+long long medmoe_lamb_chunk(void);
+long long medmoe_lamb_threads(void);
+long long medmoe_lamb_ratio_threads(void);
+long long medmoe_lamb_scratch_floats(long long n, long long n_segs);
+long long medmoe_lamb_coef_slot(long long n, long long n_segs);   /* scratch[slot]: the clip coefficient the last moments launch used */
+long long medmoe_lamb_plan(const long long* seg_end_host, long long n_segs, long long n, long long* rec_base_host);
+int medmoe_lamb_moments(const float* p, const float* g, float* m, float* v, long long n, const long long* seg_end, const float* seg_wd_mult, const long long* rec_base, int n_segs, float* scratch, long long scratch_floats, double beta1, double beta2, double eps, double weight_decay, int step, const float* grad_normsq, float max_norm, float grad_scale, hipStream_t stream);
+int medmoe_lamb_moments_g16(const float* p, const void* g_bf16, float* m, float* v, long long n, const long long* seg_end, const float* seg_wd_mult, const long long* rec_base, int n_segs, float* scratch, long long scratch_floats, double beta1, double beta2, double eps, double weight_decay, int step, const float* grad_normsq, float max_norm, float grad_scale, hipStream_t stream);
+int medmoe_lamb_ratios(const float* scratch, long long scratch_floats, const long long* seg_end, const float* seg_wd_mult, const long long* rec_base, int n_segs, long long n, double weight_decay, int always_adapt, int trust_clip, float* ratios, hipStream_t stream);
+int medmoe_lamb_apply(float* p, const float* m, const float* v, void* p_bf16, long long n, const long long* seg_end, const float* seg_lr_mult, const float* seg_wd_mult, int n_segs, const float* ratios, double lr, double beta1, double beta2, double eps, double weight_decay, int step, hipStream_t stream);
+int medmoe_lamb_apply_ema(float* p, const float* m, const float* v, void* p_bf16, long long n, const long long* seg_end, const float* seg_lr_mult, const float* seg_wd_mult, int n_segs, const float* ratios, double lr, double beta1, double beta2, double eps, double weight_decay, int step, float* ema, float one_minus_decay, hipStream_t stream);
+
 /* fp32 -> bf16 copy of the master weights */
 int medmoe_cast_bf16(const float* src, void* dst, long long n, hipStream_t stream);
 

@@ -115,6 +115,10 @@ class MedMoEConfig:
     no_decay_1d: bool = False
     text_lr_mult: float = 1.0
     layer_decay: float = 1.0
+    # optimizer = "lamb" (DESIGN 3s): Adam's moments (adam_betas / adam_eps), the decay inside the update and one trust ratio per parameter
+    # tensor.  lamb_always_adapt: the ratio also for tensors without decay (apex use_nvlamb, timm always_adapt); lamb_trust_clip: min(ratio, 1)
+    lamb_always_adapt: bool = False
+    lamb_trust_clip: bool = False
     # exponential moving average of the weights (no reference counterpart): 0 = off.  Every arena the fused step steps keeps an fp32
     # average e <- e + (1 - d_t) (p - e), updated inside the Adam launch; d_t = ema_decay, or with ema_warmup min(ema_decay, (1 + t) / (10 + t))
     # at the t-th update.  Engine.ema_weights() / eval_step(ema=True) evaluate on it, checkpoints and exports carry it
@@ -179,8 +183,11 @@ class MedMoEConfig:
             raise ValueError(f"grad_comm_dtype must be 'fp32' or 'bf16', got {self.grad_comm_dtype!r}")
         if not 0.0 <= float(self.ema_decay) < 1.0:
             raise ValueError(f"ema_decay must be in [0, 1) (0 = off), got {self.ema_decay}")
-        if self.optimizer not in ("adam", "adamw"):
-            raise ValueError(f"optimizer must be 'adam' or 'adamw', got {self.optimizer!r}")
+        if self.optimizer not in ("adam", "adamw", "lamb"):
+            raise ValueError(f"optimizer must be 'adam', 'adamw' or 'lamb', got {self.optimizer!r}")
+        for key in ("lamb_always_adapt", "lamb_trust_clip"):
+            if not isinstance(getattr(self, key), bool):
+                raise ValueError(f"{key} must be a bool, got {getattr(self, key)!r}")
         if len(tuple(self.adam_betas)) != 2 or not all(0.0 <= float(b) < 1.0 for b in self.adam_betas):
             raise ValueError(f"adam_betas must be two values in [0, 1), got {self.adam_betas}")
         if not float(self.adam_eps) > 0.0:

@@ -23,6 +23,7 @@ from .local_generic import GenericLocalLoss
 from .local_ragged import RaggedLocalLoss
 from .local_transposed import TransposedLocalLoss, local_sim_forward, ragged_layout  # noqa: F401  (ragged_layout: the tests and tools use it from here)
 from .config import MedMoEConfig
+from .flat import fused_step_of
 from .params import ParamStore
 
 BF = torch.bfloat16
@@ -1640,7 +1641,9 @@ class Engine:
         """clip_grad_norm_(cfg.clip) + torch.optim.Adam(lr, weight_decay) (cfg.optimizer = "adamw": torch.optim.AdamW; cfg.adam_betas /
         adam_eps; the parameter groups the stores carry), fused, on the gradients the stores hold; the working copies follow.  ONE clip
         norm over both towers' gradients when the text tower trains, as clip_grad_norm_ over all parameters computes it.
-        cfg.ema_decay > 0: the same launches also advance every stepped arena's weight average."""
+        cfg.ema_decay > 0: the same launches also advance every stepped arena's weight average.
+        cfg.optimizer = "lamb": behind the same clip norm every arena takes FlatArena.lamb_step instead - three launches, one trust ratio per
+        parameter tensor."""
         c, image, text = self.cfg, self.params, self.text_arena() if self.train_text else None
         if self._ema_active:
             raise RuntimeError("optimizer_step inside ema_weights(): the working copies hold the averaged weights - evaluate only")
@@ -1651,12 +1654,12 @@ class Engine:
         total = image.sumsq()
         for part in parts:
             total.add_(part)
-        kw = dict(betas=tuple(c.adam_betas), eps=c.adam_eps, decoupled=c.optimizer == "adamw")
+        step, kw = fused_step_of(c)                                 # adam_step, or lamb_step (cfg.optimizer = "lamb")
         if c.ema_decay > 0.0:                                       # the same launches in their _ema form: every arena, the same decay arguments
             ema_.prepare([image] + side)
             kw.update(ema_.step_kwargs(c))
         for a in [image] + side:
-            a.adam_step(total, lr, c.weight_decay, c.clip, **kw)
+            getattr(a, step)(total, lr, c.weight_decay, c.clip, **kw)
 
     # ------------------------------------------------------------------------------------------
     # evaluation (medmoe_module.py:114-134 validation_step / test_step: model_step without a backward)
@@ -1736,6 +1739,9 @@ class Engine:
         Gradient accumulation as in train_step: optimizer=False for all but the last micro-batch, zero_grad=False for all but the first,
         loss_scale = 1 / number of micro-batches.  Always eager.  Returns device scalars: loss, n_valid, n_correct, acc."""
         self._classify_refuse(train_tower)
+        if self.cfg.optimizer == "lamb":
+            raise NotImplementedError("classify_step with cfg.optimizer = 'lamb' (model.optimizer._target_: src.optim.Lamb): the head's fused "
+                                      "step carries its own Adam - LAMB for the classification head is a named follow-up (DESIGN 3s)")
         if self._ema_active:
             raise RuntimeError("classify_step inside ema_weights(): the working copies hold the averaged weights - evaluate only")
         c, images = self.cfg, batch["image"]

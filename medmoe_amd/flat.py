@@ -7,6 +7,8 @@ summed in a fixed order (`sumsq`), and clip + Adam + the bf16 copy are one launc
 With the weight EMA (`enable_ema`) an arena also holds `e32`, the fp32 average of the master in the same layout: `adam_step` takes the
 `_ema` form of its launch, which averages the parameter it has just updated, and `load_ema()` / `restore_master()` point the working copies at
 the average and back.
+With `lamb_step` the step is LAMB instead: `segments()` cuts the trainable range into one segment per parameter tensor, three
+launches form Adam's moments, one trust ratio per segment from norms summed in a fixed order, and the step; the state is Adam's.
 With the bf16 gradient exchange an arena also holds `g16`, the bf16 copy that `pack` fills and the ranks all-reduce: `g32` keeps
 the rank-local fp32 sum (what accumulation over micro-batches needs), and while `g16_reduced` is set the clip norm and Adam read `g16`.
 
@@ -35,6 +37,15 @@ def _numel(shape) -> int:
 
 def _pad(n: int) -> int:
     return (n + _ALIGN - 1) // _ALIGN * _ALIGN
+
+
+def fused_step_of(cfg):
+    """(name of the arena method, its keyword arguments) of the optimiser a configuration names: `adam_step` for "adam" / "adamw",
+    `lamb_step` for "lamb" (DESIGN 3s).  The engines call it on every arena they step, behind the one clip norm."""
+    kw = dict(betas=tuple(cfg.adam_betas), eps=cfg.adam_eps)
+    if cfg.optimizer == "lamb":
+        return "lamb_step", dict(kw, always_adapt=bool(cfg.lamb_always_adapt), trust_clip=bool(cfg.lamb_trust_clip))
+    return "adam_step", dict(kw, decoupled=cfg.optimizer == "adamw")
 
 
 class FlatArena:
@@ -106,6 +117,11 @@ class FlatArena:
         self.e32 = None
         self.ema_updates = 0
         self.ema_loaded = False
+        # LAMB: the segment table (one segment per parameter tensor; built lazily, dropped with the parameter groups) and, from the
+        # first lamb_step on, the record scratch of the segmented norms and the trust ratios of the last step
+        self._segments = self._seg_table = None
+        self._lamb_scratch = self._lamb_ratios = None
+        self._lamb_floats, self._lamb_coef_slot = 2, 0
 
     # -- views: built once per buffer (a backward asks for a few hundred of them per step) -----------------------------------------------
     def view(self, flat, name, shape=None):
@@ -280,9 +296,11 @@ class FlatArena:
                 runs.append((end, float(lm), float(wm)))
         self.runs = runs
         self._run_table = self._upload_runs(runs)
+        self._segments = self._seg_table = None                      # the segment table carries the runs' multipliers: rebuilt on next need
 
     def clear_param_groups(self):
         self.runs = self._run_table = None
+        self._segments = self._seg_table = None
 
     def adam_step(self, normsq_total: torch.Tensor, lr: float, weight_decay: float, clip: float, grad_scale: float = 1.0, *,
                   betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, decoupled: bool = False, ema_decay: float = 0.0,
@@ -320,6 +338,109 @@ class FlatArena:
             ends, lrm, wdm = self._run_table if self.runs is not None else self._one_run
             ops.call("adam_groups_step" + sfx, p32, g, m, v, p16, self.n_train, ends, lrm, wdm, ends.numel(), lr, b1, b2, eps,
                      weight_decay, 1 if decoupled else 0, self.step_count, normsq_total, clip, grad_scale, *ema_args)
+        if ema_args:
+            self.ema_updates += 1
+        self.g16_reduced = False
+        self._derive(step=True)
+
+    # -- LAMB: per-tensor trust ratios -----------------------------------------------------------------------------------------
+    def _segment_parts(self, name) -> List[Tuple[str, int]]:
+        """Hook: the parameter tensors of the reference model one stored entry holds, as (name, elements) in storage order - the entry itself
+        unless a store stacks several tensors in one entry (ParamStore's per-expert weights)."""
+        return [(name, _numel(self.shapes[name]))]
+
+    def segments(self) -> List[Tuple[str, int]]:
+        """[(name, end)] in storage order: segment k is elements [end_{k-1}, end_k) of the trainable tail (of g32, m, v), the last end is
+        n_train.  One segment per stored entry - the members of a group alias individually, never the alias - split further by
+        `_segment_parts`; an entry's alignment padding belongs to the segment in front of it.  With a frozen head only the tail has
+        segments.  Built on first need and again after the parameter groups changed; the device form (ends, the run multipliers of every
+        segment, the first record of every segment) is uploaded once, then."""
+        if self._segments is None:
+            self._build_segments()
+        return self._segments
+
+    def _build_segments(self):
+        tf, dev = self.train_from, self.device
+        entries = sorted((o, n) for n, o in self.offsets.items() if n not in self.groups)
+        segs: List[Tuple[str, int]] = []
+        for k, (o, name) in enumerate(entries):
+            if o < tf:
+                continue
+            nxt = entries[k + 1][0] if k + 1 < len(entries) else self.numel
+            parts = self._segment_parts(name)
+            if sum(c for _, c in parts) != _numel(self.shapes[name]):
+                raise AssertionError(f"FlatArena.segments: the parts of {name} do not add up to its {_numel(self.shapes[name])} elements")
+            pos = o
+            for j, (pn, cnt) in enumerate(parts):
+                pos += cnt
+                segs.append((pn, (nxt if j + 1 == len(parts) else pos) - tf))
+        runs = self.runs if self.runs is not None else [(self.numel, 1.0, 1.0)]
+        lrm, wdm, r, start = [], [], 0, 0
+        for name, end in segs:
+            while runs[r][0] - tf <= start and r + 1 < len(runs):
+                r += 1
+            # runs break at entry boundaries, so a tensor lies in ONE run: its trust ratio belongs to one (lr_mult, wd_mult)
+            assert end <= runs[r][0] - tf or end == start, f"FlatArena.segments: {name} [{start}, {end}) straddles the run ending at {runs[r][0] - tf}"
+            lrm.append(runs[r][1]); wdm.append(runs[r][2])
+            start = end
+        assert segs and segs[-1][1] == self.n_train
+        ends = torch.tensor([e for _, e in segs], dtype=torch.int64)
+        self._seg_table = (ends.to(dev), torch.tensor(lrm, device=dev, dtype=torch.float32), torch.tensor(wdm, device=dev, dtype=torch.float32),
+                           ops.lamb_plan(ends, self.n_train).to(dev))
+        self._lamb_floats = max(ops.lamb_scratch_floats(self.n_train, len(segs)), 2)   # the record scratch this table needs
+        self._lamb_coef_slot = ops.lamb_coef_slot(self.n_train, len(segs))
+        self._segments = segs
+
+    def trust_ratios(self):
+        """(segment names, fp32 device tensor of their trust ratios) of the last lamb_step - for logging and for the tests."""
+        if self._lamb_ratios is None:
+            raise RuntimeError("FlatArena.trust_ratios: no lamb_step yet")
+        segs = self.segments()
+        return [n for n, _ in segs], self._lamb_ratios[:len(segs)]
+
+    def last_clip_coef(self) -> torch.Tensor:
+        """fp32 device scalar: grad_scale * the clip coefficient the last lamb_step scaled this arena's gradient by (the moments launch forms
+        it as the Adam launches do and leaves it behind its records) - for logging and for the tests."""
+        if self._lamb_scratch is None:
+            raise RuntimeError("FlatArena.last_clip_coef: no lamb_step yet")
+        return self._lamb_scratch[self._lamb_coef_slot]
+
+    def lamb_step(self, normsq_total: torch.Tensor, lr: float, weight_decay: float, clip: float, grad_scale: float = 1.0, *,
+                  betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-6, always_adapt: bool = False, trust_clip: bool = False,
+                  ema_decay: float = 0.0, ema_warmup: bool = False):
+        """clip (against `normsq_total`, as adam_step) + LAMB on the fp32 master: Adam's moments, u = m_hat / (sqrt(v_hat) + eps) + wd p, and
+        per segment (`segments()`: one parameter tensor) the trust ratio r = |p| / |u| - 1 where either norm is 0, and where the tensor has
+        no decay unless always_adapt; min(r, 1) with trust_clip - then p -= lr r u.  Three launches (medmoe_lamb_moments / _ratios /
+        _apply): the norms are summed from per-chunk records in a fixed order, no atomics, nothing read from the host.  adam_step's
+        contract otherwise: the gradient in g32 or, after a bf16 exchange, in g16 (the moments launch in its _g16 form; the flag is
+        cleared), the bf16 copy written by the applying launch, ema_decay > 0 selects its _ema form, the derived copies follow.  The state
+        is Adam's (m, v, step_count); the scratch and the ratios are allocated on the first call."""
+        if self.ema_loaded:
+            raise RuntimeError("FlatArena.lamb_step: the working copies hold the average (restore_master() first)")
+        ema_args = ()
+        if float(ema_decay) > 0.0:
+            if self.e32 is None:
+                raise RuntimeError("FlatArena.lamb_step(ema_decay > 0): this arena keeps no average (enable_ema())")
+            ema_args = (self.e32, one_minus_decay(self.ema_updates, ema_decay, ema_warmup))
+        m, v = self.adam_state()
+        n_seg = len(self.segments())
+        ends, lrm, wdm, base = self._seg_table
+        if self._lamb_scratch is None or self._lamb_scratch.numel() < self._lamb_floats:
+            self._lamb_scratch = torch.zeros(self._lamb_floats, device=self.device, dtype=torch.float32)
+        if self._lamb_ratios is None or self._lamb_ratios.numel() != 3 * n_seg:
+            self._lamb_ratios = torch.zeros(3 * n_seg, device=self.device, dtype=torch.float32)
+        self.step_count += 1
+        b1, b2 = float(betas[0]), float(betas[1])
+        g, sfx = (self.g16, "_g16") if self.g16_reduced else (self.g32, "")
+        tf = self.train_from
+        p32, p16 = (self.p32[tf:], self.p16[tf:]) if tf else (self.p32, self.p16)
+        scratch, ratios = self._lamb_scratch, self._lamb_ratios
+        ops.call("lamb_moments" + sfx, p32, g, m, v, self.n_train, ends, wdm, base, n_seg, scratch, scratch.numel(), b1, b2, eps,
+                 weight_decay, self.step_count, normsq_total, clip, grad_scale)
+        ops.call("lamb_ratios", scratch, scratch.numel(), ends, wdm, base, n_seg, self.n_train, weight_decay, 1 if always_adapt else 0,
+                 1 if trust_clip else 0, ratios)
+        ops.call("lamb_apply" + ("_ema" if ema_args else ""), p32, m, v, p16, self.n_train, ends, lrm, wdm, n_seg, ratios, lr, b1, b2, eps,
+                 weight_decay, self.step_count, *ema_args)
         if ema_args:
             self.ema_updates += 1
         self.g16_reduced = False

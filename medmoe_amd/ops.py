@@ -251,6 +251,54 @@ def nondet_launches() -> int:
     return int(f())
 
 
+def _ll_query(name: str, *ints) -> int:
+    f = _FN.get(name)
+    if f is None:
+        f = getattr(load_library(), "medmoe_" + name)
+        f.argtypes = [_c.c_longlong] * len(ints)
+        f.restype = _c.c_longlong
+        _FN[name] = f
+    return int(f(*ints))
+
+
+def lamb_chunk() -> int:
+    """Elements per chunk of the LAMB moments launch: a segment leaves one record per chunk it touches (csrc/lamb_plan.h)."""
+    return _ll_query("lamb_chunk")
+
+
+def lamb_sum_shape():
+    """(threads of a moments workgroup, threads of a ratios workgroup): with lamb_chunk() what the tests derive their summation bars from."""
+    return _ll_query("lamb_threads"), _ll_query("lamb_ratio_threads")
+
+
+def lamb_scratch_floats(n: int, n_segments: int) -> int:
+    """fp32 elements of the record buffer the LAMB launches of an arena of n elements and n_segments segments need."""
+    return _ll_query("lamb_scratch_floats", int(n), int(n_segments))
+
+
+def lamb_coef_slot(n: int, n_segments: int) -> int:
+    """Index into that buffer of the clip coefficient (grad_scale * min(1, clip / norm)) the moments launch leaves behind the records."""
+    return _ll_query("lamb_coef_slot", int(n), int(n_segments))
+
+
+def lamb_plan(seg_end: torch.Tensor, n: int) -> torch.Tensor:
+    """seg_end: HOST int64 tensor of segment ends (ascending, last == n).  Returns the host int64 table of each segment's first record, by
+    the enumeration the kernels use (csrc/lamb_plan.h through medmoe_lamb_plan)."""
+    if seg_end.device.type != "cpu" or seg_end.dtype != torch.int64 or not seg_end.is_contiguous() or seg_end.dim() != 1:
+        raise ValueError("lamb_plan: seg_end must be a contiguous host int64 vector")
+    f = _FN.get("lamb_plan")
+    if f is None:
+        f = load_library().medmoe_lamb_plan
+        f.argtypes = [_vp, _c.c_longlong, _c.c_longlong, _vp]
+        f.restype = _c.c_longlong
+        _FN["lamb_plan"] = f
+    base = torch.zeros_like(seg_end)
+    recs = int(f(seg_end.data_ptr(), seg_end.numel(), int(n), base.data_ptr()))
+    if recs < 0:
+        raise ValueError(f"lamb_plan: the segment table is not ascending or does not end at n = {n}")
+    return base
+
+
 def _scratch_query(name: str, *ints) -> int:
     f = _FN.get(name)
     if f is None:
@@ -789,6 +837,9 @@ _SIGS = {
     # the four optimiser steps with the weight EMA: their sibling's arguments + (ema, one_minus_decay)
     "adam_step_ema": "pppppldddddipffpf", "adam_groups_step_ema": "ppppplpppidddddiipffpf",
     "adam_step_ema_g16": "pppppldddddipffpf", "adam_groups_step_ema_g16": "ppppplpppidddddiipffpf",
+    # LAMB (csrc/lamb.hip): three launches per arena - moments (fp32 / bf16 gradient), ratios, apply (plain / with the weight EMA)
+    "lamb_moments": "pppplpppiplddddipff", "lamb_moments_g16": "pppplpppiplddddipff", "lamb_ratios": "plpppildiip",
+    "lamb_apply": "pppplpppipdddddi", "lamb_apply_ema": "pppplpppipdddddipf",
     # retrieval and zero-shot evaluation (csrc/retrieval.hip)
     "l2_normalize": "ppiif", "sim_topk": "ppiiiipppl", "sim_rank": "pppiiippl",
     # supervised classification (csrc/classify.hip)
@@ -881,6 +932,10 @@ _COSTS = {
     "adam_groups_step_ema": lambda a: ("adam_groups_kernel<LDS, float, EMA>", 42.0 * a[5], "byte"),
     "adam_step_ema_g16": lambda a: ("adam_kernel<bf16, EMA>", 40.0 * a[5], "byte"),
     "adam_groups_step_ema_g16": lambda a: ("adam_groups_kernel<LDS, bf16, EMA>", 40.0 * a[5], "byte"),
+    "lamb_moments": lambda a: ("lamb_moments_kernel", 24.0 * a[4], "byte"),                        # p, g, m, v read; m, v written
+    "lamb_moments_g16": lambda a: ("lamb_moments_kernel<LDS, bf16>", 22.0 * a[4], "byte"),
+    "lamb_apply": lambda a: ("lamb_apply_kernel", 18.0 * a[4], "byte"),                            # p, m, v read; p, bf16 copy written
+    "lamb_apply_ema": lambda a: ("lamb_apply_kernel<LDS, EMA>", 26.0 * a[4], "byte"),
     "grad_pack_bf16": lambda a: ("grad_pack_bf16_kernel", 6.0 * a[2], "byte"),                     # fp32 read, bf16 written
     "scale_attn_bwd": lambda a: ("scale_attn_bwd_kernel", 2.0 * a[17] * (4 * (2 * a[18] + 2 * a[19]) + 2 * a[18]), "byte"),    # G, dG, H1, dH1 x 4 scales + eout, d_img_l rows
     "scale_attn_bwd_det": lambda a: ("scale_attn_bwd_kernel<DET> + scale_attn_bwd_reduce_kernel", 2.0 * a[17] * (4 * (2 * a[18] + 2 * a[19]) + 2 * a[18]), "byte"),

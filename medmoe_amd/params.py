@@ -215,6 +215,22 @@ class ParamStore(FlatArena):
                 out[name] = v
         return out
 
+    def _segment_parts(self, name):
+        """LAMB's segments (FlatArena.segments): a stacked per-expert entry is one parameter tensor PER EXPERT in the reference
+        model, so it gives E segments under named_views()' names - the table agrees one to one with named_views().  The patch-embedding
+        weight is one segment with its zero k-step padding columns."""
+        E = self.cfg.n_expert
+        per = 1
+        for d in self.shapes[name][1:]:
+            per *= int(d)
+        if name.startswith("moe.proj."):
+            s, leaf = name.split(".")[2], name.split(".")[3]
+            return [(f"moe.experts.{e}.proj_convs.{s}.0.{leaf}", per) for e in range(E)]
+        if name.startswith("moe.attn0.") or name.startswith("moe.attn2."):
+            k, leaf = name.split(".")[1][-1], name.split(".")[2]
+            return [(f"moe.experts.{e}.attn_proj.{k}.{leaf}", per) for e in range(E)]
+        return super()._segment_parts(name)
+
     def export_named(self, flat=None) -> Dict[str, torch.Tensor]:
         """Reference-style names -> fp32 CPU tensors (flat = p32 for weights, g32 for grads)."""
         return {k: v.detach().float().cpu().contiguous() for k, v in self.named_views(flat).items()}

@@ -26,6 +26,7 @@ import torch
 from . import ema as ema_
 from . import ops
 from .engine import Engine
+from .flat import fused_step_of
 from .local_generic import GenericLocalLoss
 from .swin_moe import SwinMoEEncoder
 
@@ -189,14 +190,14 @@ class SwinEngine:
         torch.add(st_t.sumsq(), st_m.sumsq(), out=self._normsq)
         if self.train_text:
             self._normsq.add_(self.eng.text_arena().sumsq())
-        kw = dict(betas=tuple(c.adam_betas), eps=c.adam_eps, decoupled=c.optimizer == "adamw")
+        step, kw = fused_step_of(c)                                 # adam_step, or lamb_step (cfg.optimizer = "lamb")
         if c.ema_decay > 0.0:                                       # weight EMA: every store's launch in its _ema form
             ema_.prepare(self.optimizer_stores().values())
             kw.update(ema_.step_kwargs(c))
-        st_t.adam_step(self._normsq, lr, c.weight_decay, c.clip, **kw)
-        st_m.adam_step(self._normsq, lr, c.weight_decay, c.clip, **kw)
+        getattr(st_t, step)(self._normsq, lr, c.weight_decay, c.clip, **kw)
+        getattr(st_m, step)(self._normsq, lr, c.weight_decay, c.clip, **kw)
         if self.train_text:
-            self.eng.text_arena().adam_step(self._normsq, lr, c.weight_decay, c.clip, **kw)
+            getattr(self.eng.text_arena(), step)(self._normsq, lr, c.weight_decay, c.clip, **kw)
         self.enc.tower.refresh(cast=False)                          # patch-embedding pad form, bias tables
 
     def ema_weights(self):

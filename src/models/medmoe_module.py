@@ -71,6 +71,11 @@ class MedMoEPretrainingLightningModule(_Base):
         if self._optimizer_groups and not self.fused_step:
             raise NotImplementedError("optimizer_groups needs fused_step=true: the autograd path steps ONE flat parameter, which cannot be "
                                       "cut into groups (the fused step groups runs of the engine's flat stores)")
+        from src.optim import Lamb
+        if not self.fused_step and getattr(optimizer, "func", None) is Lamb:
+            raise NotImplementedError("model.optimizer._target_ = src.optim.Lamb needs fused_step=true (model.fused_step=true): the autograd "
+                                      "path steps ONE flat parameter, and a trust ratio over the whole model would be meaningless (the fused "
+                                      "step keeps one ratio per parameter tensor of the engine's flat stores)")
         self._grad_comm_dtype = str(grad_comm_dtype)
         if self._grad_comm_dtype not in ("fp32", "bf16"):
             raise ValueError(f"grad_comm_dtype must be 'fp32' or 'bf16', got {grad_comm_dtype!r}")
@@ -217,11 +222,14 @@ class MedMoEPretrainingLightningModule(_Base):
                                       f"got {type(self.global_loss).__name__} / {type(self.local_loss).__name__}, soft_label={self.soft_label}")
         if _get(self.loss_cfg, "agg", "sum") != "sum":
             raise NotImplementedError("fused_step: only loss.agg = 'sum' (the reference default)")
+        from src.optim import Lamb
         opt = self._optimizer
-        if not isinstance(opt, functools.partial) or opt.func not in (torch.optim.Adam, torch.optim.AdamW) or opt.args \
-                or set(opt.keywords) - {"lr", "weight_decay", "betas", "eps"}:
+        lamb = isinstance(opt, functools.partial) and opt.func is Lamb
+        if not isinstance(opt, functools.partial) or opt.func not in (torch.optim.Adam, torch.optim.AdamW, Lamb) or opt.args \
+                or set(opt.keywords) - ({"lr", "weight_decay", "betas", "eps"} | ({"always_adapt", "trust_clip"} if lamb else set())):
             raise NotImplementedError("fused_step fuses torch.optim.Adam or torch.optim.AdamW (lr, weight_decay, betas, eps; the experiment's "
-                                      "optimizer is Adam, med-moe_pretraining.yaml:7-11); no other optimizer and no other keyword")
+                                      "optimizer is Adam, med-moe_pretraining.yaml:7-11) or src.optim.Lamb (the same keywords, always_adapt, "
+                                      "trust_clip); no other optimizer and no other keyword")
         c = eng.cfg
         c.temp1, c.temp2 = float(_get(self.loss_cfg, "temp1", 4.0)), float(_get(self.loss_cfg, "temp2", 5.0))
         c.temp3 = float(_get(self.loss_cfg, "temp3", 10.0))
@@ -231,10 +239,12 @@ class MedMoEPretrainingLightningModule(_Base):
         c.threshold0, c.threshold1 = float(_get(self.loss_cfg, "threshold0", 0.98)), float(_get(self.loss_cfg, "threshold1", 0.97))
         adamw = opt.func is torch.optim.AdamW
         c.lr = float(opt.keywords.get("lr", 1e-3))
-        c.weight_decay = float(opt.keywords.get("weight_decay", 1e-2 if adamw else 0.0))      # the two classes' own defaults
-        c.optimizer = "adamw" if adamw else "adam"
+        c.weight_decay = float(opt.keywords.get("weight_decay", 1e-2 if adamw or lamb else 0.0))      # the classes' own defaults
+        c.optimizer = "lamb" if lamb else "adamw" if adamw else "adam"
         c.adam_betas = tuple(float(b) for b in opt.keywords.get("betas", (0.9, 0.999)))
-        c.adam_eps = float(opt.keywords.get("eps", 1e-8))
+        c.adam_eps = float(opt.keywords.get("eps", 1e-6 if lamb else 1e-8))
+        c.lamb_always_adapt = bool(opt.keywords.get("always_adapt", False)) if lamb else False
+        c.lamb_trust_clip = bool(opt.keywords.get("trust_clip", False)) if lamb else False
         c.grad_comm_dtype = self._grad_comm_dtype
         c.ema_decay, c.ema_warmup = self._ema_decay, self._ema_warmup
         c.validate()
