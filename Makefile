@@ -42,7 +42,14 @@ check-lamb-plan: tools/lamb_plan_check.cpp $(CSRC)/lamb_plan.h
 	$(CXX) -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I$(CSRC) $< -o build/lamb_plan_check
 	build/lamb_plan_check
 
+# host-only check of the upsample supports of the segmentation head (seg_plan.h, shared with segment.hip): for random (g, H) the supports
+# partition the (pixel, corner) pairs of non-zero weight and gather equals scatter in exact integers, under the sanitizers
+check-seg-plan: tools/seg_plan_check.cpp $(CSRC)/seg_plan.h
+	@mkdir -p build
+	$(CXX) -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I$(CSRC) $< -o build/seg_plan_check
+	build/seg_plan_check
+
 clean:
 	rm -rf build $(LIB)
 
-.PHONY: all clean check-plan check-exchange check-topk check-lamb-plan
+.PHONY: all clean check-plan check-exchange check-topk check-lamb-plan check-seg-plan

@@ -583,6 +583,31 @@ long long medmoe_vocab_ce_scratch(int M_bound, int V, int D);
 int medmoe_vocab_ce_bwd_dx(const void* z, const void* E, const float* bias, const int* row_labels, const float* lse, const int* count, float loss_scale, void* dz, int M_bound, int V, int D, hipStream_t stream);
 int medmoe_vocab_ce_bwd_dw(const void* z, const void* E, const float* bias, const int* row_labels, const float* lse, const int* count, float loss_scale, float* dE, float* dbias, int M_bound, int V, int D, hipStream_t stream);
 
+/* ---- semantic segmentation on the region features (csrc/segment.hip) ----
+   A linear decoder with independent sigmoids per class.  1 <= C <= 8, D % 64 == 0, 64 <= D <= 2048, 1 <= g <= 64 patches per axis,
+   H >= g and W >= g (anything else returns -2 before a launch).  No fp32 atomic: every sum leaves as per-workgroup records added in index
+   order, two calls give the same bits and medmoe_nondet_launches() never moves.
+   z [N][C] fp32 = feat [N][D] (bf16, 16-byte aligned) W^T [C][D] + b [C] (fp32), fp32 arithmetic. */
+int medmoe_seg_head_fwd(const void* feat, const float* W, const float* b, float* z, int N, int D, int C, hipStream_t stream);
+/* z [B][g g][C] against masks int8 [B][C][H][W] in {0, 1, -1} (-1: ignored, enters no sum and no gradient; 16-byte aligned).  zf[b][c][y][x] is
+   the bilinear upsample of z to H x W (torch interpolate, align_corners = false: src = (dst + 0.5) g / H - 0.5 clamped at 0), recomputed per
+   pixel and never stored.  loss [1] = loss_scale (w_bce L_bce + w_dice L_dice) is WRITTEN:
+     L_bce  = 1 / |K| sum over the valid (pixel, class) pairs of pos_weight_c t softplus(-zf) + (1 - t) softplus(zf)   (pos_weight NULL: 1)
+     L_dice = 1 - mean over the classes with a valid pixel of (2 I_c + eps) / (P_c + T_c + eps),  I = sum p t, P = sum p, T = sum t, p = sigmoid(zf)
+   |K| = 0: loss 0, dz 0.  counts int64 [C][4] = (n_valid, TP, FP, FN) at the threshold zf > 0 is WRITTEN (|K| = sum of n_valid).
+   dz [B][g g][C] (NULL: evaluation, no gradient pass) is WRITTEN with d loss / d z, the adjoint of the upsample in gather form.
+   scratch_floats >= medmoe_seg_scratch(B, g, H, W, D, C) for any D (-1 otherwise). */
+int medmoe_seg_loss(const float* z, const signed char* masks, const float* pos_weight, float w_bce, float w_dice, float dice_eps, float loss_scale, float* dz, float* loss, long long* counts, float* scratch, long long scratch_floats, int B, int g, int H, int W, int C, hipStream_t stream);
+/* dfeat [N][D] bf16 = dz W is WRITTEN (NULL: not formed); dW [C][D] += dz^T feat and db [C] += sum dz through records per row range, added
+   in range order.  scratch as for medmoe_seg_loss (the two launches may share it: they run one after the other). */
+int medmoe_seg_head_bwd(const float* dz, const void* feat, const float* W, void* dfeat, float* dW, float* db, float* scratch, long long scratch_floats, int N, int D, int C, hipStream_t stream);
+/* masks uint8 [B][C][H][W] = (zf > 0) (16-byte aligned); zf fp32 [B][C][H][W] is written too when not NULL */
+int medmoe_seg_predict(const float* z, unsigned char* masks, float* zf, int B, int g, int H, int W, int C, hipStream_t stream);
+/* scratch floats of medmoe_seg_loss / medmoe_seg_head_bwd, 0 for a shape they refuse */
+long long medmoe_seg_scratch(int B, int g, int H, int W, int D, int C);
+/* the share of it medmoe_seg_head_bwd alone needs (it knows no mask size): the records of dW / db, 0 for a shape it refuses */
+long long medmoe_seg_head_bwd_scratch(int N, int D, int C);
+
 #ifdef __cplusplus
 }
 #endif

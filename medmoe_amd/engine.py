@@ -1799,6 +1799,93 @@ class Engine:
         out = head.evaluate(self.ws["img_g"], batch["label"])
         return head.last_logits, self._classify_result(out)
 
+    # -- semantic segmentation on the region features ------------------------------------------------------------------------
+    def _segment_refuse(self, train_tower: bool):
+        if self.dist:
+            raise NotImplementedError("segment_step / segment_eval under data parallelism (self.dist: WORLD_SIZE > 1, trainer.devices > 1): the "
+                                      "head's gradient and the batch-Dice sums have no all-reduce yet - data-parallel segmentation is a named "
+                                      "follow-up (DESIGN 3t)")
+        if train_tower and self.cfg.ema_decay > 0.0:
+            raise NotImplementedError("segment_step(train_tower=True) with cfg.ema_decay > 0 (model.ema.decay): the head keeps no average, so "
+                                      "the towers' averages would pair with an un-averaged head - EMA of the head is a named follow-up (DESIGN 3t)")
+
+    def segment_step(self, batch: Dict[str, torch.Tensor], head, train_tower: bool, optimizer: bool = True, zero_grad: bool = True,
+                     loss_scale: float = 1.0, head_lr: Optional[float] = None):
+        """One supervised step of `head` (medmoe_amd.segment.SegmenterHead) on ws["img_l"] of batch["image"] against batch["mask"] (int8
+        [B, C, H, W] in {0, 1, -1}, -1 = ignored; the other forms of segment.prepare_masks are accepted).  The mask size is free: any
+        H, W >= the patch grid.  No caption is read, the text tower is not run.
+        train_tower=False, the online probe: forward_image in its evaluation form (no drop path, no adapter dropout), the head's four
+        launches, the head's Adam step - not one parameter, gradient, Adam or EMA buffer of the engine's own stores is written, and
+        dropout_step stays.
+        train_tower=True, fine-tuning: the training form of the image pass (drop path, adapter dropout and recomputation as in train_step),
+        the head WRITES d loss / d img_l into all of ws["d_img_l"], ws["d_img_g"] is zeroed and backward(None) runs unchanged - so a
+        freeze_vit engine fine-tunes MoE + head and a vit_lora engine adapters + MoE + head.  ONE clip norm over the image arena, the
+        adapters and the head, then Adam on each, the head at head_lr (default cfg.lr); dropout_step advances.
+        Gradient accumulation as in train_step (optimizer=False for all but the last micro-batch, zero_grad=False for all but the first,
+        loss_scale = 1 / number of micro-batches) reproduces the one-batch step only for a head with w_dice = 0: the Dice sums run over the
+        micro-batch a call sees (batch Dice is not additive).  Always eager.  Returns device tensors: loss, counts int64 [C, 4] =
+        (n_valid, TP, FP, FN), n_valid (their sum over the classes)."""
+        self._segment_refuse(train_tower)
+        if self.cfg.optimizer == "lamb":
+            raise NotImplementedError("segment_step with cfg.optimizer = 'lamb' (model.optimizer._target_: src.optim.Lamb): the head's fused "
+                                      "step carries its own Adam - LAMB for the segmentation head is a named follow-up (DESIGN 3t)")
+        if self._ema_active:
+            raise RuntimeError("segment_step inside ema_weights(): the working copies hold the averaged weights - evaluate only")
+        c, images = self.cfg, batch["image"]
+        self._alloc(images.shape[0])
+        ws = self.ws
+        lr = c.lr if head_lr is None else float(head_lr)
+        kw = dict(betas=tuple(c.adam_betas), eps=c.adam_eps, decoupled=c.optimizer == "adamw")
+        if not train_tower:
+            self.forward_image(images)
+            if zero_grad:
+                head.store.zero_grad()
+            out = head.step(ws["img_l"], batch["mask"], loss_scale)
+            if optimizer:
+                head.adam_step(lr, c.weight_decay, c.clip, **kw)
+            return self._segment_result(out)
+        towers = [self.params] + ([self.vlora] if self.vlora is not None else [])
+        if zero_grad:
+            for a in towers:
+                a.zero_grad()
+            head.store.zero_grad()
+        try:
+            self._forward_image_train(images)
+            out = head.step(ws["img_l"], batch["mask"], loss_scale, dfeat=ws["d_img_l"])
+            ws["d_img_g"].zero_()
+            self.backward(None, loss_scale)
+        finally:
+            self.vit_drop_scales = None
+            self._vit_lora_drop_step = None
+        self.dropout_step += 1
+        if optimizer:
+            parts = [a.sumsq() for a in towers[1:] + [head.store]]
+            total = self.params.sumsq()
+            for part in parts:
+                total.add_(part)
+            for a in towers:
+                a.adam_step(total, c.lr, c.weight_decay, c.clip, **kw)
+            head.adam_step(lr, c.weight_decay, c.clip, normsq_total=total, **kw)
+        return self._segment_result(out)
+
+    @staticmethod
+    def _segment_result(out):
+        loss, counts = out
+        return {"loss": loss, "counts": counts, "n_valid": counts[:, 0].sum()}
+
+    def segment_eval(self, batch: Dict[str, torch.Tensor], head, ema: bool = False):
+        """(patch logits, loss dict) of `head` on a batch, forward only: the evaluation form of the image pass, the head's row pass and the
+        stats half of its loss launch at loss_scale 1 - no parameter, gradient or optimiser state of the engine or the head is written.
+        patch logits: fp32 [B, P, C] view of the head's workspace, valid until its next launch (head.predict / ops.seg_predict turn them
+        into masks); dict["counts"] feeds a segment.SegBank.  ema=True: the image pass runs on the averaged weights; the head keeps no average."""
+        self._segment_refuse(False)
+        if ema and not self._ema_active:
+            with self.ema_weights():
+                return self.segment_eval(batch, head)
+        self.forward_image(batch["image"])
+        out = head.evaluate(self.ws["img_l"], batch["mask"])
+        return head.last_logits, self._segment_result(out)
+
     def _local_loss_eval(self):
         """GLoRIA local loss value (losses.py:961-1026) of ws["img_l"] against ws["words"] into loss_parts[3]; ws["gsim"] is the heads' scratch.
         The transposed object lends medmoe_local_sim_fwd its Gram matrices, tile tables and word norms - its pair matrices are not touched

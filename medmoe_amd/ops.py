@@ -847,6 +847,8 @@ _SIGS = {
     # masked-language-model objective (csrc/mlm.hip)
     "mlm_mask": "ppppppppiiiiiiillll", "rows_gather": "ppppii", "rows_scatter_add": "ppppii", "rows_mul": "ppppii",
     "vocab_ce_fwd": "pppppfpppppliii", "vocab_ce_bwd_dx": "ppppppfpiii", "vocab_ce_bwd_dw": "ppppppfppiii",
+    # semantic segmentation (csrc/segment.hip)
+    "seg_head_fwd": "ppppiii", "seg_loss": "pppffffppppliiiii", "seg_head_bwd": "pppppppliii", "seg_predict": "pppiiiii",
 }
 
 
@@ -1268,6 +1270,173 @@ def auroc_counts(scores, targets):
     out = torch.empty((C, 4), device=scores.device, dtype=torch.int64)
     call(name, scores, targets, out, N, C)
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# semantic segmentation on the region features (csrc/segment.hip)
+# ---------------------------------------------------------------------------------------------
+SEG_MAX_CLASSES = 8
+SEG_MAX_D = 2048
+SEG_MAX_GRID = 64                       # patches per axis
+
+
+def _seg_tensor(name, arg, t, dtype, shape=None, align=False):
+    """A contiguous tensor of `dtype` (of `shape`, 16-byte aligned when asked): ValueError naming the argument otherwise."""
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+        raise ValueError(f"{name}: {arg} must be a {dtype} tensor, got {getattr(t, 'dtype', type(t))}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: {arg} must be contiguous")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: {arg} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+    if align and t.data_ptr() % 16:
+        raise ValueError(f"{name}: {arg} must start at a 16-byte boundary")
+
+
+def _seg_head_check(name, feat, W, b=None):
+    _seg_tensor(name, "feat", feat, torch.bfloat16, align=True)
+    _seg_tensor(name, "W", W, torch.float32, align=True)
+    if b is not None:
+        _seg_tensor(name, "b", b, torch.float32)
+    if feat.dim() != 2 or W.dim() != 2 or (b is not None and b.dim() != 1):
+        raise ValueError(f"{name}: feat must be [N, D], W [C, D] and b [C]")
+    N, D = feat.shape
+    C = W.shape[0]
+    if D % 64 or not 64 <= D <= SEG_MAX_D:
+        raise ValueError(f"{name}: feat has D = {D}; D must be a multiple of 64 in 64 .. {SEG_MAX_D}")
+    if not 1 <= C <= SEG_MAX_CLASSES:
+        raise ValueError(f"{name}: W has C = {C} rows; 1 <= C <= {SEG_MAX_CLASSES}")
+    if W.shape[1] != D:
+        raise ValueError(f"{name}: W has {W.shape[1]} columns, feat has D = {D}")
+    if b is not None and b.shape[0] != C:
+        raise ValueError(f"{name}: b holds {b.shape[0]} values, W has C = {C} rows")
+    if N < 1:
+        raise ValueError(f"{name}: feat must hold at least one row")
+    return N, D, C
+
+
+def _seg_map_check(name, z, size):
+    """(B, g, H, W, C) of patch logits z fp32 [B, g*g, C] against the mask size (H, W)."""
+    _seg_tensor(name, "z", z, torch.float32)
+    if z.dim() != 3 or z.shape[0] < 1:
+        raise ValueError(f"{name}: z must be [B, P, C] with B >= 1, got {tuple(z.shape)}")
+    B, P, C = z.shape
+    g = int(round(P ** 0.5))
+    if g * g != P or not 1 <= g <= SEG_MAX_GRID:
+        raise ValueError(f"{name}: z has P = {P} patches; P must be a square g * g with 1 <= g <= {SEG_MAX_GRID}")
+    if not 1 <= C <= SEG_MAX_CLASSES:
+        raise ValueError(f"{name}: z has C = {C} classes; 1 <= C <= {SEG_MAX_CLASSES}")
+    H, W = int(size[0]), int(size[1])
+    if H < g:
+        raise ValueError(f"{name}: H = {H} is smaller than the patch grid g = {g}; the head upsamples only")
+    if W < g:
+        raise ValueError(f"{name}: W = {W} is smaller than the patch grid g = {g}; the head upsamples only")
+    return B, g, H, W, C
+
+
+def _seg_same_device(name, ref, **tensors):
+    _require_gpu(ref, name)
+    for arg, t in tensors.items():
+        if t is not None:
+            _require_gpu(t, f"{name}: {arg}")
+            if t.device != ref.device:
+                raise ValueError(f"{name}: {arg} is on {t.device}, the first argument on {ref.device}")
+
+
+def seg_scratch(B: int, g: int, H: int, W: int, D: int, C: int) -> int:
+    return _scratch_query("seg_scratch", B, g, H, W, D, C)
+
+
+def seg_head_bwd_scratch(N: int, D: int, C: int) -> int:
+    return _scratch_query("seg_head_bwd_scratch", N, D, C)
+
+
+def seg_head_fwd(feat, W, b, z=None):
+    """z fp32 [N, C] = feat bf16 [N, D] @ W fp32 [C, D]^T + b [C] in fp32 arithmetic (medmoe_seg_head_fwd): the patch logits."""
+    name = "seg_head_fwd"
+    N, D, C = _seg_head_check(name, feat, W, b)
+    if z is None:
+        z = torch.empty((N, C), device=feat.device, dtype=torch.float32)
+    _seg_tensor(name, "z", z, torch.float32)
+    if z.numel() != N * C:
+        raise ValueError(f"{name}: z must hold {N} x {C} values, got {tuple(z.shape)}")
+    _seg_same_device(name, feat, W=W, b=b, z=z)
+    call(name, feat, W, b, z, N, D, C)
+    return z
+
+
+def seg_loss(z, masks, *, pos_weight=None, w_bce: float = 1.0, w_dice: float = 1.0, dice_eps: float = 1.0, loss_scale: float = 1.0, dz=None,
+             loss=None, counts=None, scratch=None):
+    """BCE + batch-Dice loss of the patch logits z fp32 [B, g*g, C] against masks int8 [B, C, H, W] in {0, 1, -1} (medmoe_seg_loss; the
+    formulas are in include/medmoe_hip.h).  dz [B, g*g, C], when given, is WRITTEN with d loss / d z.  Returns (loss fp32 [1], counts int64
+    [C, 4] = (n_valid, TP, FP, FN)) - device tensors, nothing is read back."""
+    name = "seg_loss"
+    _seg_tensor(name, "masks", masks, torch.int8, align=True)
+    if masks.dim() != 4:
+        raise ValueError(f"{name}: masks must be [B, C, H, W], got {tuple(masks.shape)}")
+    B, g, H, W, C = _seg_map_check(name, z, masks.shape[2:])
+    if tuple(masks.shape[:2]) != (B, C):
+        raise ValueError(f"{name}: masks must have shape ({B}, {C}, H, W) for z {tuple(z.shape)}, got {tuple(masks.shape)}")
+    if pos_weight is not None:
+        _seg_tensor(name, "pos_weight", pos_weight, torch.float32, (C,))
+    if not float(dice_eps) >= 0.0:
+        raise ValueError(f"{name}: dice_eps must be >= 0, got {dice_eps}")
+    dev = z.device
+    if dz is not None:
+        _seg_tensor(name, "dz", dz, torch.float32, tuple(z.shape))
+    if loss is None:
+        loss = torch.empty(1, device=dev, dtype=torch.float32)
+    if counts is None:
+        counts = torch.empty((C, 4), device=dev, dtype=torch.int64)
+    need = seg_scratch(B, g, H, W, 64, C)
+    if scratch is None:
+        scratch = torch.empty(need, device=dev, dtype=torch.float32)
+    _seg_tensor(name, "loss", loss, torch.float32, (1,))
+    _seg_tensor(name, "counts", counts, torch.int64, (C, 4))
+    _seg_tensor(name, "scratch", scratch, torch.float32, align=True)
+    if scratch.numel() < need:
+        raise ValueError(f"{name}: scratch holds {scratch.numel()} floats, seg_scratch({B}, {g}, {H}, {W}, 64, {C}) = {need}")
+    _seg_same_device(name, z, masks=masks, pos_weight=pos_weight, dz=dz, loss=loss, counts=counts, scratch=scratch)
+    call(name, z, masks, pos_weight, float(w_bce), float(w_dice), float(dice_eps), float(loss_scale), dz, loss, counts, scratch, scratch.numel(),
+         B, g, H, W, C)
+    return loss, counts
+
+
+def seg_head_bwd(dz, feat, W, dW, db, dfeat=None, scratch=None):
+    """The head's backward (medmoe_seg_head_bwd): dfeat bf16 [N, D] = dz W, when given, is WRITTEN; dW [C, D] and db [C] are ACCUMULATED into
+    (records per row range, added in range order)."""
+    name = "seg_head_bwd"
+    N, D, C = _seg_head_check(name, feat, W)
+    _seg_tensor(name, "dz", dz, torch.float32)
+    if dz.numel() != N * C:
+        raise ValueError(f"{name}: dz must hold {N} x {C} values, got {tuple(dz.shape)}")
+    _seg_tensor(name, "dW", dW, torch.float32, (C, D))
+    _seg_tensor(name, "db", db, torch.float32, (C,))
+    if dfeat is not None:
+        _seg_tensor(name, "dfeat", dfeat, torch.bfloat16, align=True)
+        if dfeat.numel() != N * D:
+            raise ValueError(f"{name}: dfeat must hold {N} x {D} values, got {tuple(dfeat.shape)}")
+    need = seg_head_bwd_scratch(N, D, C)
+    if scratch is None:
+        scratch = torch.empty(need, device=feat.device, dtype=torch.float32)
+    _seg_tensor(name, "scratch", scratch, torch.float32, align=True)
+    if scratch.numel() < need:
+        raise ValueError(f"{name}: scratch holds {scratch.numel()} floats, seg_head_bwd_scratch({N}, {D}, {C}) = {need}")
+    _seg_same_device(name, feat, dz=dz, W=W, dW=dW, db=db, dfeat=dfeat, scratch=scratch)
+    call(name, dz, feat, W, dfeat, dW, db, scratch, scratch.numel(), N, D, C)
+
+
+def seg_predict(z, size, masks=None, want_logits: bool = False):
+    """masks uint8 [B, C, H, W] = (zf > 0) of the patch logits z fp32 [B, g*g, C] upsampled to size = (H, W) (medmoe_seg_predict); with
+    want_logits also zf fp32 [B, C, H, W].  Returns masks, or (masks, zf)."""
+    name = "seg_predict"
+    B, g, H, W, C = _seg_map_check(name, z, size)
+    if masks is None:
+        masks = torch.empty((B, C, H, W), device=z.device, dtype=torch.uint8)
+    _seg_tensor(name, "masks", masks, torch.uint8, (B, C, H, W), align=True)
+    zf = torch.empty((B, C, H, W), device=z.device, dtype=torch.float32) if want_logits else None
+    _seg_same_device(name, z, masks=masks)
+    call(name, z, masks, zf, B, g, H, W, C)
+    return (masks, zf) if want_logits else masks
 
 
 # ---------------------------------------------------------------------------------------------

@@ -232,6 +232,13 @@ class SwinEngine:
     def classify_eval(self, *a, **kw):
         self.classify_step()
 
+    def segment_step(self, *a, **kw):
+        raise NotImplementedError("SwinEngine.segment_step / segment_eval (vision.arch = swin_t): the segmentation head trains on the ViT "
+                                  "Engine's region features and backward (DESIGN 3t); the Swin tower is a named follow-up")
+
+    def segment_eval(self, *a, **kw):
+        self.segment_step()
+
     def eval_step(self, batch: Dict[str, torch.Tensor]):
         """Forward + losses without gradients reaching the parameters (validation): the same launch sequence minus the encoder backward."""
         was = self.training

@@ -26,8 +26,12 @@ except Exception:                                        # noqa: BLE001
 class UnimedDataModule(_Base):
     def __init__(self, data_dir: str = "data/", transformations: Any = None, batch_size: int = 64, num_workers: int = 0,
                  pin_memory: bool = False, train_data_paths: Optional[str] = None, val_data_paths: Optional[str] = None,
-                 synthetic_size: int = 4096, max_len: int = 77, synthetic_vocab: int = 28996, synthetic_classes: int = 5) -> None:
+                 synthetic_size: int = 4096, max_len: int = 77, synthetic_vocab: int = 28996, synthetic_classes: int = 5,
+                 masks: Any = None) -> None:
         super().__init__()
+        if masks is not None and transformations is not None:
+            raise NotImplementedError("data.masks with data.transformations: the augmentation moves the image and not its mask - augmented "
+                                      "segmentation is a named follow-up (DESIGN 3t)")
         self.data_dir, self.transformations = data_dir, transformations
         # the block is read (and refused, naming its key) here, not at the first batch; augment_step counts the TRAINING batches handed
         # to device_batch and is the `step` of the augmentation's random stream, carried by state_dict()
@@ -43,7 +47,7 @@ class UnimedDataModule(_Base):
             if wds is not None and paths:                # unimed_datamodule.py:44-46
                 return wds.WebDataset(paths, resampled=True, shardshuffle=True, nodesplitter=wds.split_by_node) \
                     .decode("pil").to_tuple("jpg", "txt", "cls")
-            return SyntheticUnimed(synthetic_size, max_len=max_len, vocab=synthetic_vocab, n_classes=synthetic_classes, seed=seed)
+            return SyntheticUnimed(synthetic_size, max_len=max_len, vocab=synthetic_vocab, n_classes=synthetic_classes, seed=seed, masks=masks)
 
         self.data_train = make(train_data_paths, 12345)
         self.data_val = make(val_data_paths, 54321)
@@ -90,8 +94,11 @@ class UnimedDataModule(_Base):
     def _with_captions(image, batch: Dict[str, Any], device) -> Dict[str, Any]:
         ids = torch.stack([torch.as_tensor(c) for c in batch["caption"]]).to(device)
         mask = (ids != 0).long()
-        return {"image": image, "ids": ids, "attn_mask": mask, "token_type": torch.zeros_like(ids), "label": batch["label"].to(device),
-                "caption": {"ids": ids, "attn_mask": mask}}
+        out = {"image": image, "ids": ids, "attn_mask": mask, "token_type": torch.zeros_like(ids), "label": batch["label"].to(device),
+               "caption": {"ids": ids, "attn_mask": mask}}
+        if "mask" in batch:                                  # segmentation masks (data.masks) travel as they are
+            out["mask"] = batch["mask"].to(device)
+        return out
 
     def device_batch(self, batch: Dict[str, Any], device, size: int = 224, train: bool = True) -> Dict[str, Any]:
         """to_device_batch with the `transformations` block applied.  No block: to_device_batch itself (the same launches, the same bits).

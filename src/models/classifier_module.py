@@ -11,7 +11,7 @@ from typing import Any, Dict
 import torch
 from torch import nn
 
-from .medmoe_module import MedMoEPretrainingLightningModule, _Base, _get
+from .head_module import HeadOnEngineModule, _Base
 
 _KEYS = ("num_classes", "task", "mode", "label_key", "label_smoothing", "pos_weight", "head_lr", "pretrained_ckpt", "class_names")
 _MODES = ("linear_probe", "finetune")
@@ -44,7 +44,7 @@ def classifier_block(classifier: Any) -> Dict[str, Any]:
     return out
 
 
-class MedMoEClassifierLightningModule(MedMoEPretrainingLightningModule):
+class MedMoEClassifierLightningModule(HeadOnEngineModule):
     """Keys under `model.classifier`: num_classes; task (multiclass | multilabel); mode (linear_probe | finetune); label_key (default
     "label": batch[label_key] holds int [B] class indices or, multilabel, int [B, C] in {0, 1, -1}; -1 = not counted); label_smoothing
     (multiclass); pos_weight ([C], multilabel); head_lr (default: the optimizer's lr; the scheduler scales both alike); pretrained_ckpt (a
@@ -52,27 +52,13 @@ class MedMoEClassifierLightningModule(MedMoEPretrainingLightningModule):
     The checkpoint hooks, configure_fused, set_deterministic and configure_optimizers are the pretraining module's; the head's weights
     travel in the state dict as classifier.weight / classifier.bias and its Adam moments under fused_adam["head"]."""
 
+    _KIND, _STEP, _LAUNCH, _FEATURE, _DESIGN = "classifier", "Engine.classify_step", "fused loss / backward launch", "global embedding", "3p"
+
     def __init__(self, model: nn.Module, classifier: Any = None, optimizer: Any = None, scheduler: Any = None, compile: bool = False,
                  fused_step: bool = True):
         _Base.__init__(self)
         self._cls = classifier_block(classifier)
-        if not fused_step:
-            raise NotImplementedError("the classifier module runs on the HIP engine only (model.fused_step=true): Engine.classify_step has the "
-                                      "head's fused loss / backward launch, there is no autograd path")
-        self.model = model
-        self._optimizer, self._scheduler = optimizer, scheduler
-        self.fused_step = True
-        self._fused_acc, self._fused_clip, self._fused_opt = 1, None, None
-        self._ema_decay, self._ema_warmup, self._ema_validate = 0.0, False, False      # EMA of the head: a named follow-up (DESIGN 3p)
-        self._retrieval, self._bank = None, None
-        self._swin_engine = None
-        self.automatic_optimization = False
-        eng = getattr(model, "engine", None)
-        if eng is None:
-            raise NotImplementedError("the classifier module needs the HIP engine behind self.model (src.models.components.med_moe.MedMoE)")
-        if getattr(model, "swin", None) is not None:
-            raise NotImplementedError("model.classifier with vision.arch = swin_t: the head trains on the ViT Engine's global embedding and "
-                                      "backward; the Swin tower is a named follow-up (DESIGN 3p)")
+        eng = self._init_on_engine(model, optimizer, scheduler, fused_step)
         from medmoe_amd.classify import ClassifierHead, ScoreBank
         c = self._cls
         pw = None if c["pos_weight"] is None else torch.tensor(c["pos_weight"], dtype=torch.float32)
@@ -83,35 +69,11 @@ class MedMoEClassifierLightningModule(MedMoEPretrainingLightningModule):
         self.classifier.weight = nn.Parameter(self.head.weight)
         self.classifier.bias = nn.Parameter(self.head.bias)
         self._scores = ScoreBank(c["num_classes"], eng.device, task=c["task"])
-        self._configure_engine()
-        if c["pretrained_ckpt"]:
-            state = torch.load(str(c["pretrained_ckpt"]), map_location="cpu", weights_only=True)
-            self.load_state_dict(state.get("state_dict", state), strict=False)
+        self._finish_init(c["head_lr"], c["pretrained_ckpt"])
 
     @property
     def train_tower(self) -> bool:
         return self._cls["mode"] == "finetune"
-
-    def _configure_engine(self):
-        """The optimiser's keys into the engine's config (Adam or AdamW: lr, weight_decay, betas, eps)."""
-        import functools
-        opt, c = self._optimizer, self.model.engine.cfg
-        self._head_lr_mult = 1.0
-        if opt is None:
-            return
-        if not isinstance(opt, functools.partial) or opt.func not in (torch.optim.Adam, torch.optim.AdamW) or opt.args \
-                or set(opt.keywords) - {"lr", "weight_decay", "betas", "eps"}:
-            raise NotImplementedError("the classifier module fuses torch.optim.Adam or torch.optim.AdamW (lr, weight_decay, betas, eps); no other "
-                                      "optimizer and no other keyword")
-        adamw = opt.func is torch.optim.AdamW
-        c.lr = float(opt.keywords.get("lr", 1e-3))
-        c.weight_decay = float(opt.keywords.get("weight_decay", 1e-2 if adamw else 0.0))
-        c.optimizer = "adamw" if adamw else "adam"
-        c.adam_betas = tuple(float(b) for b in opt.keywords.get("betas", (0.9, 0.999)))
-        c.adam_eps = float(opt.keywords.get("eps", 1e-8))
-        c.validate()
-        if self._cls["head_lr"] is not None:
-            self._head_lr_mult = self._cls["head_lr"] / c.lr
 
     def _batch(self, batch: Dict[str, Any]) -> Dict[str, torch.Tensor]:
         key = self._cls["label_key"]
@@ -124,18 +86,11 @@ class MedMoEClassifierLightningModule(MedMoEPretrainingLightningModule):
         eng = self._fused_engine()
         return self.head.logits(eng.embed_image(batch["image"].contiguous())).clone()
 
-    def model_step(self, batch: Dict[str, Any]):
-        return self.fused_eval_step(batch)
-
-    def training_step(self, batch, batch_idx: int = 0):
-        acc = self._fused_acc
-        return self.fused_training_step(batch, optimizer_step=(batch_idx + 1) % acc == 0, zero_grad=batch_idx % acc == 0, loss_scale=1.0 / acc)["loss"]
-
     def fused_training_step(self, batch: Dict[str, Any], optimizer_step: bool = True, zero_grad: bool = True, loss_scale: float = 1.0):
         """One micro-batch through Engine.classify_step: {"loss", "acc"} as device scalars."""
         eng = self._fused_engine()
         out = eng.classify_step(self._batch(batch), self.head, self.train_tower, optimizer=optimizer_step, zero_grad=zero_grad,
-                                loss_scale=loss_scale, head_lr=eng.cfg.lr * self._head_lr_mult)
+                                loss_scale=loss_scale, head_lr=self._head_lr())
         return {"loss": out["loss"], "acc": out["acc"]}
 
     def fused_eval_step(self, batch: Dict[str, Any]):
@@ -145,12 +100,6 @@ class MedMoEClassifierLightningModule(MedMoEPretrainingLightningModule):
         self._scores.add(logits, eb["label"])
         return {"loss": out["loss"], "acc": out["acc"]}
 
-    def validation_step(self, batch, batch_idx: int = 0):
-        return self.fused_eval_step(batch)
-
-    def test_step(self, batch, batch_idx: int = 0):
-        return self.fused_eval_step(batch)
-
     def on_validation_epoch_start(self):
         self._scores.reset()
 
@@ -158,12 +107,6 @@ class MedMoEClassifierLightningModule(MedMoEPretrainingLightningModule):
         """{"acc" (multiclass), "auroc_mean", "auroc/<class>"} over the epoch's bank; the trainer files them under val/... or test/...."""
         from medmoe_amd.classify import classification_metrics
         return classification_metrics(self._scores, self._cls["class_names"])
-
-    def on_test_epoch_start(self):
-        return self.on_validation_epoch_start()
-
-    def on_test_epoch_end(self):
-        return self.on_validation_epoch_end()
 
     def _fused_stores(self) -> Dict[str, Any]:
         out = super()._fused_stores()
