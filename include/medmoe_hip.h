@@ -608,6 +608,28 @@ long long medmoe_seg_scratch(int B, int g, int H, int W, int D, int C);
 /* the share of it medmoe_seg_head_bwd alone needs (it knows no mask size): the records of dW / db, 0 for a shape it refuses */
 long long medmoe_seg_head_bwd_scratch(int N, int D, int C);
 
+/* ---- phrase grounding: word-region heat maps scored against boxes (csrc/ground.hip) ----
+   One owner per output element, nothing is combined through memory: two calls give the same bits and medmoe_nondet_launches() never moves.
+   h fp32 [n][P] is WRITTEN for the n entries (image b, caption i, word_lo, word_hi) of `entries` (device int32 [n][4], 16-byte aligned; the
+   span is half-open, 0 <= word_lo < word_hi <= cap_lens[i]; the caller validates the table, the kernel trusts it).  ctx bf16 [B][P][D], words
+   bf16 [Bc][T][D] (16-byte aligned), cap_lens int32 [Bc].  s_raw[t][p] = <ctx[b][p], words[i][t]>: bf16 products, fp32 accumulation on
+   v_mfma_f32_16x16x32_bf16, fp32 after it.
+     mode 0 (attention): s[.][p] = softmax of s_raw[.][p] over the words t < cap_lens[i]; a[t][.] = softmax of temp1 s[t][.] over the regions;
+                         h[p] = mean of a[t][p] over the span (a one-word span over a matched pair: a row of the local loss's attention map).
+     mode 1 (cosine):    h[p] = <ctx_p, u> / max(|ctx_p| |u|, eps), u = the sum of words[i][t] over the span.
+   P = g g with g <= 32, 1 <= T <= 80, D % 64 == 0, 64 <= D <= 2048 (anything else returns -2 before a launch); 0 <= temp1 <= 64, mode in
+   {0, 1} (-1 otherwise); n == 0 returns 0 without a launch. */
+int medmoe_ground_maps(const void* ctx, const void* words, const int* cap_lens, const int* entries, float* h, int n, int B, int Bc, int P, int T, int D, int mode, float temp1, float eps, hipStream_t stream);
+/* Scores n grid maps h fp32 [n][g g] (any map, not only medmoe_ground_maps') against boxes int32 [n][NB][4] = (x0, y0, x1, y1), half-open pixel
+   rectangles of the H x W frame (x1 <= x0 or y1 <= y0: absent), 1 <= NB <= 8, at the thresholds theta fp32 [NTH], 0 <= NTH <= 4; 1 <= g <= 32,
+   H >= g, W >= g, H W <= 2^30 (-2 otherwise).  hf[y][x] is the bilinear upsample of h to H x W - the map of medmoe_seg_loss (seg_plan.h) -
+   recomputed per pixel; hf fp32 [n][H][W], when not NULL, is WRITTEN with exactly the values the statistics saw.
+     rec_f fp32 [n][2 + NTH]    = (max, min, thr_0, ...), thr_k = min + theta_k (max - min)
+     rec_i int32 [n][4 + 2 NTH] = (y, x, hit, area, inter_0, pred_0, ...): (y, x) the first maximal pixel in row-major order, hit = it lies in the
+                                  union of the boxes, area = the union's pixels, pred_k = #{hf >= thr_k}, inter_k = #{hf >= thr_k, in the union}
+     rec_d fp64 [n][4]          = (S_in, Q_in, S_all, Q_all): the sums of hf and hf^2 over the union and over the frame, in a fixed order */
+int medmoe_ground_score(const float* h, const int* boxes, const float* theta, float* hf, float* rec_f, int* rec_i, double* rec_d, int n, int g, int H, int W, int NB, int NTH, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1886,6 +1886,58 @@ class Engine:
         out = head.evaluate(self.ws["img_l"], batch["mask"])
         return head.last_logits, self._segment_result(out)
 
+    # -- phrase grounding: word-region heat maps scored against boxes ---------------------------------------------------------
+    def _ground_refuse(self):
+        c = self.cfg
+        if c.d_t != c.d_out:
+            raise NotImplementedError(f"Engine.ground: word features of width d_t = {c.d_t} against regions of d_out = {c.d_out} - the score of a "
+                                      "word against a region needs one width")
+
+    def ground(self, batch: Dict[str, torch.Tensor], mode: str = "attention", thetas=(0.5,), size=None, ema: bool = False, want_map: bool = False):
+        """Phrase grounding of the matched pairs of a batch: the forward launches of `embed` and nothing after them, then the two launches
+        of csrc/ground.hip (`ground_workspace`).  batch["span"]: int [B, 2] half-open WORD spans (rows of ws["words"]), or batch["tok_span"]:
+        int [B, 2] token spans, mapped through the word-piece segment map (ground.word_spans); batch["box"]: int [B, NB, 4] = (x0, y0, x1, y1)
+        half-open pixel rectangles of the `size` = (H, W) frame (default: the image size), absent ones empty.  Returns the records of
+        ops.ground_score (a dict of device tensors, what a ground.GroundBank adds) with "h", the grid maps fp32 [B, P], and with want_map
+        "hf" fp32 [B, H, W].  No parameter, gradient, moment or EMA buffer is written.  ema=True: on the averaged weights.  More than one
+        rank: every rank scores its own shard."""
+        self._ground_refuse()
+        if ema and not self._ema_active:
+            with self.ema_weights():
+                return self.ground(batch, mode, thetas, size, False, want_map)
+        self.embed(batch)
+        return self.ground_workspace(batch, mode, thetas, size, want_map)
+
+    def ground_workspace(self, batch: Dict[str, torch.Tensor], mode: str = "attention", thetas=(0.5,), size=None, want_map: bool = False,
+                         span_key: str = "span", box_key: str = "box"):
+        """The two grounding launches on the features the last forward of this batch left in the workspace (ws["img_l"], ws["words"],
+        cap_lens) - `ground` without its forward; a validation step that already ran the towers calls this."""
+        from . import ground as ground_
+        self._ground_refuse()
+        ws, B = self.ws, self.B
+        if span_key in batch:
+            spans = torch.as_tensor(batch[span_key]).detach().cpu().to(torch.int64).reshape(-1, 2)
+        elif "tok_span" in batch:
+            tok = torch.as_tensor(batch["tok_span"]).detach().cpu().to(torch.int64).reshape(-1, 2)
+            seg = ws.get("seg")                                      # the segment map prefetch_cap_lens wrote for this batch
+            if seg is None or tuple(seg.shape) != tuple(batch["ids"].shape):
+                seg = self.vocab.segment_map(batch["ids"])[0]
+            spans = ground_.word_spans(seg, tok[:, 0], tok[:, 1])
+        else:
+            raise KeyError(f"Engine.ground: the batch holds neither '{span_key}' (word spans) nor 'tok_span' (token spans)")
+        if box_key not in batch:
+            raise KeyError(f"Engine.ground: the batch holds no '{box_key}'")
+        if spans.shape[0] != B:
+            raise ValueError(f"Engine.ground: {spans.shape[0]} spans for a batch of {B}")
+        if size is None:
+            size = tuple(batch["image"].shape[-2:])
+        pair = torch.arange(B, dtype=torch.int64)
+        entries = torch.stack([pair, pair, spans[:, 0], spans[:, 1]], dim=1)
+        h = ops.ground_maps(ws["img_l"], ws["words"], self.cap_lens, entries, mode=mode, temp1=self.cfg.temp1, cap_lens_host=self._cap_lens_host())
+        out = ops.ground_score(h, batch[box_key], size, thetas=thetas, want_map=want_map)
+        out["h"] = h
+        return out
+
     def _local_loss_eval(self):
         """GLoRIA local loss value (losses.py:961-1026) of ws["img_l"] against ws["words"] into loss_parts[3]; ws["gsim"] is the heads' scratch.
         The transposed object lends medmoe_local_sim_fwd its Gram matrices, tile tables and word norms - its pair matrices are not touched

@@ -849,6 +849,8 @@ _SIGS = {
     "vocab_ce_fwd": "pppppfpppppliii", "vocab_ce_bwd_dx": "ppppppfpiii", "vocab_ce_bwd_dw": "ppppppfppiii",
     # semantic segmentation (csrc/segment.hip)
     "seg_head_fwd": "ppppiii", "seg_loss": "pppffffppppliiiii", "seg_head_bwd": "pppppppliii", "seg_predict": "pppiiiii",
+    # phrase grounding (csrc/ground.hip)
+    "ground_maps": "pppppiiiiiiiff", "ground_score": "pppppppiiiiii",
 }
 
 
@@ -1437,6 +1439,143 @@ def seg_predict(z, size, masks=None, want_logits: bool = False):
     _seg_same_device(name, z, masks=masks)
     call(name, z, masks, zf, B, g, H, W, C)
     return (masks, zf) if want_logits else masks
+
+
+# ---------------------------------------------------------------------------------------------
+# phrase grounding: word-region heat maps scored against boxes (csrc/ground.hip)
+# ---------------------------------------------------------------------------------------------
+GROUND_MAX_GRID = 32                    # regions per axis
+GROUND_MAX_T = 80                       # word rows of a caption
+GROUND_MAX_D = 2048
+GROUND_MAX_TEMP1 = 64.0                 # exp(temp1 (s - 1)) runs without a running maximum
+GROUND_MAX_BOXES = 8
+GROUND_MAX_THETAS = 4
+GROUND_MODES = {"attention": 0, "cosine": 1}
+
+
+def _ground_host_table(name, arg, t, cols):
+    """An integer table as a host int64 array [n, *cols] (tensor on any device, numpy array or nested list)."""
+    import numpy as np
+    if isinstance(t, torch.Tensor):
+        if t.dtype.is_floating_point or t.dtype == torch.bool:
+            raise ValueError(f"{name}: {arg} must be an integer table, got {t.dtype}")
+        t = t.detach().cpu().numpy()
+    a = np.asarray(t)
+    if a.size and a.dtype.kind not in "iu":
+        raise ValueError(f"{name}: {arg} must be an integer table, got {a.dtype}")
+    try:
+        return np.ascontiguousarray(a.astype(np.int64).reshape((-1,) + tuple(cols)))
+    except ValueError:
+        raise ValueError(f"{name}: {arg} must be [n, {', '.join(str(c) for c in cols)}], got {tuple(a.shape)}") from None
+
+
+def ground_maps(ctx, words, cap_lens, entries, mode: str = "attention", temp1: float = 4.0, eps: float = 1e-8, cap_lens_host=None):
+    """h fp32 [n, P]: the heat map over the P = g * g regions of image b for the words [word_lo, word_hi) of caption i, for every entry
+    (b, i, word_lo, word_hi) of `entries` (medmoe_ground_maps).  ctx bf16 [B, P, D], words bf16 [Bc, T, D] and cap_lens int32 [Bc] as
+    Engine.embed leaves them in the workspace; word positions are the rows of `words`.  mode "attention": the region attention of the
+    local loss (softmax over the caption's words, then softmax over the regions at temp1), averaged over the span - each map sums to 1;
+    "cosine": cos(ctx_p, sum of the span's word vectors).  `entries` is a HOST table (tensor, numpy array or list): the kernel trusts
+    it, so every image, caption and span is checked here against cap_lens (cap_lens_host, when given, spares the read-back) before anything
+    is uploaded or launched.  n = 0 returns an empty map without a launch."""
+    import numpy as np
+    name = "ground_maps"
+    _seg_tensor(name, "ctx", ctx, torch.bfloat16, align=True)
+    _seg_tensor(name, "words", words, torch.bfloat16, align=True)
+    _seg_tensor(name, "cap_lens", cap_lens, torch.int32)
+    if ctx.dim() != 3 or words.dim() != 3 or ctx.shape[0] < 1 or words.shape[0] < 1:
+        raise ValueError(f"{name}: ctx must be [B, P, D] and words [Bc, T, D], got {tuple(ctx.shape)} and {tuple(words.shape)}")
+    B, P, D = ctx.shape
+    Bc, T, Dw = words.shape
+    g = int(round(P ** 0.5))
+    if g * g != P or not 1 <= g <= GROUND_MAX_GRID:
+        raise ValueError(f"{name}: ctx has P = {P} regions; P must be a square g * g with 1 <= g <= {GROUND_MAX_GRID}")
+    if D % 64 or not 64 <= D <= GROUND_MAX_D:
+        raise ValueError(f"{name}: ctx has D = {D}; D must be a multiple of 64 in 64 .. {GROUND_MAX_D}")
+    if Dw != D:
+        raise ValueError(f"{name}: words has D = {Dw}, ctx has D = {D}")
+    if not 1 <= T <= GROUND_MAX_T:
+        raise ValueError(f"{name}: words has T = {T} rows per caption; 1 <= T <= {GROUND_MAX_T}")
+    if cap_lens.numel() != Bc:
+        raise ValueError(f"{name}: cap_lens holds {cap_lens.numel()} lengths, words {Bc} captions")
+    if mode not in GROUND_MODES:
+        raise ValueError(f"{name}: mode must be one of {sorted(GROUND_MODES)}, got {mode!r}")
+    if not 0.0 <= float(temp1) <= GROUND_MAX_TEMP1:
+        raise ValueError(f"{name}: temp1 = {temp1} lies outside [0, {GROUND_MAX_TEMP1:g}] (the region softmax runs without a running maximum)")
+    if not float(eps) >= 0.0:
+        raise ValueError(f"{name}: eps must be >= 0, got {eps}")
+    tab = _ground_host_table(name, "entries", entries, (4,))
+    n = tab.shape[0]
+    if n:
+        lens_h = _ground_host_table(name, "cap_lens_host", cap_lens if cap_lens_host is None else cap_lens_host, ())
+        if lens_h.shape[0] != Bc:
+            raise ValueError(f"{name}: cap_lens_host holds {lens_h.shape[0]} lengths, words {Bc} captions")
+        if tab[:, 0].min() < 0 or tab[:, 0].max() >= B:
+            raise ValueError(f"{name}: entries names an image outside [0, {B})")
+        if tab[:, 1].min() < 0 or tab[:, 1].max() >= Bc:
+            raise ValueError(f"{name}: entries names a caption outside [0, {Bc})")
+        lens_e = lens_h[tab[:, 1]]
+        if lens_e.min() < 1 or lens_e.max() > T:
+            raise ValueError(f"{name}: cap_lens of a listed caption lies outside [1, {T}]")
+        bad = (tab[:, 2] < 0) | (tab[:, 2] >= tab[:, 3]) | (tab[:, 3] > lens_e)
+        if bad.any():
+            k = int(np.argmax(bad))
+            raise ValueError(f"{name}: entries[{k}] has the word span [{tab[k, 2]}, {tab[k, 3]}); a span must satisfy 0 <= word_lo < word_hi <= "
+                             f"cap_lens[{tab[k, 1]}] = {lens_e[k]}")
+    _seg_same_device(name, ctx, words=words, cap_lens=cap_lens)
+    h = torch.empty((n, P), device=ctx.device, dtype=torch.float32)
+    if n == 0:
+        return h
+    ent = torch.from_numpy(tab.astype(np.int32)).to(ctx.device, non_blocking=True)
+    call(name, ctx, words, cap_lens, ent, h, n, B, Bc, P, T, D, GROUND_MODES[mode], float(temp1), float(eps))
+    return h
+
+
+def ground_score(h, boxes, size, thetas=(), want_map: bool = False):
+    """Scores grid maps h fp32 [n, g * g] (any map) against boxes int [n, NB, 4] = (x0, y0, x1, y1), half-open pixel rectangles of the
+    size = (H, W) frame, 1 <= NB <= 8; a rectangle with x1 <= x0 or y1 <= y0 is absent; boxes are clipped to the frame here
+    (medmoe_ground_score).  hf is the bilinear upsample of h to (H, W), the map of seg_loss, recomputed per pixel.  Returns a dict of device
+    tensors: rec_f fp32 [n, 2 + NTH] = (max, min, thr_k = min + theta_k (max - min)), rec_i int32 [n, 4 + 2 NTH] = (y, x, hit, area, inter_0,
+    pred_0, ...) with (y, x) the first maximal pixel in row-major order, rec_d fp64 [n, 4] = the sums of hf and hf^2 over the union of the
+    boxes and over the frame, "size" and "thetas"; with want_map also "hf" fp32 [n, H, W], bit for bit the values the records saw."""
+    name = "ground_score"
+    _seg_tensor(name, "h", h, torch.float32)
+    if h.dim() != 2:
+        raise ValueError(f"{name}: h must be [n, P], got {tuple(h.shape)}")
+    n, P = h.shape
+    g = int(round(P ** 0.5))
+    if g * g != P or not 1 <= g <= GROUND_MAX_GRID:
+        raise ValueError(f"{name}: h has P = {P} regions; P must be a square g * g with 1 <= g <= {GROUND_MAX_GRID}")
+    if not isinstance(boxes, torch.Tensor) or boxes.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{name}: boxes must be an int32 or int64 tensor, got {getattr(boxes, 'dtype', type(boxes))}")
+    if boxes.dim() != 3 or boxes.shape[0] != n or boxes.shape[2] != 4:
+        raise ValueError(f"{name}: boxes must be [{n}, NB, 4], got {tuple(boxes.shape)}")
+    NB = boxes.shape[1]
+    if not 1 <= NB <= GROUND_MAX_BOXES:
+        raise ValueError(f"{name}: boxes has NB = {NB} rectangles per entry; 1 <= NB <= {GROUND_MAX_BOXES}")
+    th = [float(t) for t in thetas]
+    if len(th) > GROUND_MAX_THETAS:
+        raise ValueError(f"{name}: thetas holds NTH = {len(th)} thresholds; 0 <= NTH <= {GROUND_MAX_THETAS}")
+    H, W = int(size[0]), int(size[1])
+    if H < g:
+        raise ValueError(f"{name}: H = {H} is smaller than the region grid g = {g}; the map is upsampled only")
+    if W < g:
+        raise ValueError(f"{name}: W = {W} is smaller than the region grid g = {g}; the map is upsampled only")
+    if H * W > 1 << 30:
+        raise ValueError(f"{name}: size = ({H}, {W}) holds more than 2^30 pixels")
+    _require_gpu(h, name)
+    dev = h.device
+    hi = torch.tensor([W, H, W, H], dtype=torch.int64)
+    bx = torch.minimum(boxes.detach().cpu().to(torch.int64).clamp(min=0), hi).to(torch.int32).contiguous().to(dev, non_blocking=True)
+    NTH = len(th)
+    theta = torch.tensor(th, dtype=torch.float32).to(dev, non_blocking=True) if NTH else None
+    out = {"rec_f": torch.empty((n, 2 + NTH), device=dev, dtype=torch.float32), "rec_i": torch.empty((n, 4 + 2 * NTH), device=dev, dtype=torch.int32),
+           "rec_d": torch.empty((n, 4), device=dev, dtype=torch.float64), "size": (H, W), "thetas": tuple(th)}
+    hf = torch.empty((n, H, W), device=dev, dtype=torch.float32) if want_map else None
+    if n:
+        call(name, h, bx, theta, hf, out["rec_f"], out["rec_i"], out["rec_d"], n, g, H, W, NB, NTH)
+    if want_map:
+        out["hf"] = hf
+    return out
 
 
 # ---------------------------------------------------------------------------------------------

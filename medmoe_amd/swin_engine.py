@@ -239,6 +239,13 @@ class SwinEngine:
     def segment_eval(self, *a, **kw):
         self.segment_step()
 
+    def ground(self, *a, **kw):
+        raise NotImplementedError("SwinEngine.ground / ground_workspace (vision.arch = swin_t): phrase grounding reads the ViT Engine's region "
+                                  "features (DESIGN 3u); maps for the Swin tower are a named follow-up")
+
+    def ground_workspace(self, *a, **kw):
+        self.ground()
+
     def eval_step(self, batch: Dict[str, torch.Tensor]):
         """Forward + losses without gradients reaching the parameters (validation): the same launch sequence minus the encoder backward."""
         was = self.training

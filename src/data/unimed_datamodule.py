@@ -27,8 +27,11 @@ class UnimedDataModule(_Base):
     def __init__(self, data_dir: str = "data/", transformations: Any = None, batch_size: int = 64, num_workers: int = 0,
                  pin_memory: bool = False, train_data_paths: Optional[str] = None, val_data_paths: Optional[str] = None,
                  synthetic_size: int = 4096, max_len: int = 77, synthetic_vocab: int = 28996, synthetic_classes: int = 5,
-                 masks: Any = None) -> None:
+                 masks: Any = None, boxes: Any = None) -> None:
         super().__init__()
+        if boxes is not None and transformations is not None:
+            raise NotImplementedError("data.boxes with data.transformations: the augmentation moves the image and not its boxes - augmented "
+                                      "grounding is a named follow-up (DESIGN 3u)")
         if masks is not None and transformations is not None:
             raise NotImplementedError("data.masks with data.transformations: the augmentation moves the image and not its mask - augmented "
                                       "segmentation is a named follow-up (DESIGN 3t)")
@@ -47,7 +50,7 @@ class UnimedDataModule(_Base):
             if wds is not None and paths:                # unimed_datamodule.py:44-46
                 return wds.WebDataset(paths, resampled=True, shardshuffle=True, nodesplitter=wds.split_by_node) \
                     .decode("pil").to_tuple("jpg", "txt", "cls")
-            return SyntheticUnimed(synthetic_size, max_len=max_len, vocab=synthetic_vocab, n_classes=synthetic_classes, seed=seed, masks=masks)
+            return SyntheticUnimed(synthetic_size, max_len=max_len, vocab=synthetic_vocab, n_classes=synthetic_classes, seed=seed, masks=masks, boxes=boxes)
 
         self.data_train = make(train_data_paths, 12345)
         self.data_val = make(val_data_paths, 54321)
@@ -98,6 +101,9 @@ class UnimedDataModule(_Base):
                "caption": {"ids": ids, "attn_mask": mask}}
         if "mask" in batch:                                  # segmentation masks (data.masks) travel as they are
             out["mask"] = batch["mask"].to(device)
+        for key in ("box", "span"):                          # grounding annotations (data.boxes): host tables, validated on the host
+            if key in batch:
+                out[key] = batch[key]
         return out
 
     def device_batch(self, batch: Dict[str, Any], device, size: int = 224, train: bool = True) -> Dict[str, Any]:

@@ -23,7 +23,7 @@ def _get(cfg: Any, key: str, default=None):
 class MedMoEPretrainingLightningModule(_Base):
     def __init__(self, model: nn.Module, loss: Any, optimizer: Any = None, scheduler: Any = None,
                  compile: bool = False, num_classes: int = 5, fused_step: bool = False, optimizer_groups: Any = None,
-                 grad_comm_dtype: str = "fp32", ema: Any = None, retrieval: Any = None, mlm: Any = None):
+                 grad_comm_dtype: str = "fp32", ema: Any = None, retrieval: Any = None, mlm: Any = None, grounding: Any = None):
         """`fused_step` (MI355X build, `model.fused_step` in the config tree): training steps run `Engine.train_step` - the hand-scheduled
         forward / losses / backward with the embedding all-gather, the reduce-scatter of the gathered-key gradients, the per-layer
         gradient all-reduce overlapped with backward and the fused clip + Adam - instead of torch autograd + a torch optimizer.
@@ -54,7 +54,12 @@ class MedMoEPretrainingLightningModule(_Base):
         objective.  A training step masks `prob` of the caption tokens on the chip, runs the text tower once on the masked ids and adds
         `weight` x the cross-entropy of the masked positions under a head tied to the word embeddings (Engine.enable_mlm); the step reports
         mlm_loss / mlm_acc.  `validate`: validation_step / test_step add val/mlm_loss and val/mlm_acc under the fixed mask of step 0.  The
-        head travels with the checkpoint (`mlm_head`, the reference's key names cls.dense.weight ... cls.bias) with its Adam state."""
+        head travels with the checkpoint (`mlm_head`, the reference's key names cls.dense.weight ... cls.bias) with its Adam state.
+        `grounding` (`model.grounding`: mode attention | cosine, thetas, size, span_key, box_key; fused step with the ViT towers only; DESIGN
+        3u): validation / test epochs also report phrase grounding - val/pg_acc, val/cnr_mean, val/ground_iou@<theta>.  The maps of a
+        batch's (image, caption, batch[span_key]) pairs are formed from the features the validation forward left in the workspace
+        (Engine.ground_workspace: no second forward) and scored against batch[box_key]; a medmoe_amd.ground.GroundBank keeps the epoch's
+        sums on the device, ranks add theirs.  Every key logged without the block keeps its value."""
         super().__init__()
         self.model = model
         self.loss_cfg = loss
@@ -110,6 +115,7 @@ class MedMoEPretrainingLightningModule(_Base):
                          "mask_token_id": int(_get(mlm, "mask_token_id", 103)), "validate": bool(_get(mlm, "validate", False))}
         self._retrieval, self._bank, self._zs, self._class_emb = self._retrieval_block(retrieval), None, None, None
         self._lbank, self._class_words = None, None              # model.retrieval.local: the local features of the epoch, the prompts' words
+        self._grounding, self._gbank = self._grounding_block(grounding), None
         if self.fused_step:
             self.automatic_optimization = False                                  # Lightning: manual optimisation (the engine steps itself)
             self._configure_engine()
@@ -151,6 +157,39 @@ class MedMoEPretrainingLightningModule(_Base):
                                               "regions of cfg4 / cfg3 are a named follow-up (DESIGN 3q)")
             blk.update({"local": True, "local_k": int(local_k), "local_agg": local_agg})     # absent without local: the block of DESIGN 3o as it was
         return blk
+
+    def _grounding_block(self, grounding: Any):
+        """The validated `model.grounding` block (None when absent)."""
+        if grounding is None:
+            return None
+        r = dict(grounding)
+        valid = ("mode", "thetas", "size", "span_key", "box_key")
+        unknown = set(r) - set(valid)
+        if unknown:
+            raise KeyError(f"model.grounding: unknown keys {sorted(unknown)} ({', '.join(valid)})")
+        if not self.fused_step:
+            raise NotImplementedError("model.grounding needs fused_step=true (model.fused_step=true): the region and word features are read "
+                                      "from the HIP engine's workspace after Engine.eval_step; the autograd path keeps none")
+        if getattr(self.model, "swin", None) is not None:
+            raise NotImplementedError("model.grounding with vision.arch = swin_t: that model validates through model_step, not Engine.eval_step - "
+                                      "maps for the Swin engine are a named follow-up (DESIGN 3u)")
+        from medmoe_amd import ops
+        mode = str(r.get("mode", "attention"))
+        if mode not in ops.GROUND_MODES:
+            raise ValueError(f"model.grounding.mode must be one of {sorted(ops.GROUND_MODES)}, got {mode!r}")
+        thetas = r.get("thetas", (0.5,))
+        thetas = tuple(float(t) for t in ((thetas,) if isinstance(thetas, (int, float)) else thetas))
+        if not 1 <= len(thetas) <= ops.GROUND_MAX_THETAS:
+            raise ValueError(f"model.grounding.thetas must hold 1 .. {ops.GROUND_MAX_THETAS} thresholds, got {thetas}")
+        size = r.get("size")
+        if size is not None:
+            size = (int(size), int(size)) if isinstance(size, (int, float)) else tuple(int(v) for v in size)
+            if len(size) != 2 or min(size) < 1:
+                raise ValueError(f"model.grounding.size must be a side or (H, W), got {r.get('size')!r}")
+        cfg = getattr(getattr(self.model, "engine", None), "cfg", None)
+        if cfg is not None and cfg.d_t != cfg.d_out:
+            raise NotImplementedError(f"model.grounding: word features of width d_t = {cfg.d_t} against regions of d_out = {cfg.d_out}")
+        return {"mode": mode, "thetas": thetas, "size": size, "span_key": str(r.get("span_key", "span")), "box_key": str(r.get("box_key", "box"))}
 
     def forward(self, batch):
         return self.model(batch)
@@ -340,6 +379,8 @@ class MedMoEPretrainingLightningModule(_Base):
                 return self.model_step(batch)
         eng, eb = self._fused_engine(), self._engine_batch(batch)
         out = eng.eval_step(eb, ema=True) if self._ema_validate else eng.eval_step(eb)
+        if self._grounding is not None:                              # on the features this forward left, before anything overwrites them
+            self._ground_add(eng, batch)
         res = {"loss": out["loss"], "l_loss": out["l_loss"], "g_loss": out["g_loss"], "classifier_loss": out["classifier_loss"],
                "classifier_acc": out["classifier_acc"]}
         if self._mlm is not None and self._mlm["validate"]:          # val/mlm_loss, val/mlm_acc under the fixed mask of step 0
@@ -357,6 +398,29 @@ class MedMoEPretrainingLightningModule(_Base):
 
     def test_step(self, batch, batch_idx: int = 0):                                      # :127-134
         return self.validation_step(batch, batch_idx)
+
+    # ---- phrase grounding of an evaluation epoch (model.grounding) -----------------------------------------------------------
+    def _ground_add(self, eng, batch: Dict[str, Any]):
+        from medmoe_amd.ground import GroundBank
+        g = self._grounding
+        if self._gbank is None:
+            self._gbank = GroundBank(g["thetas"], eng.device)
+        rec = eng.ground_workspace(batch, mode=g["mode"], thetas=g["thetas"], size=g["size"], span_key=g["span_key"], box_key=g["box_key"])
+        self._gbank.add(rec)
+
+    def _ground_metrics(self) -> Dict[str, float]:
+        """pg_acc, cnr_mean and ground_iou@<theta> of the epoch; under data parallelism the ranks' sums are added first."""
+        if self._grounding is None or self._gbank is None or len(self._gbank) == 0:
+            return {}
+        from medmoe_amd.ground import grounding_metrics, theta_key
+        import torch.distributed as tdist
+        if tdist.is_available() and tdist.is_initialized() and tdist.get_world_size() > 1:
+            tdist.all_reduce(self._gbank.ints)
+            tdist.all_reduce(self._gbank.sums)
+        met = grounding_metrics(self._gbank)
+        out = {"pg_acc": met["pg_acc"], "cnr_mean": met["cnr_mean"]}
+        out.update({f"ground_iou@{theta_key(t)}": met[f"iou@{theta_key(t)}"] for t in self._gbank.thetas})
+        return out
 
     # ---- retrieval / zero-shot metrics of an evaluation epoch (model.retrieval, DESIGN 3o) ----------------------------------------------
     def _bank_add(self, batch: Dict[str, Any]):
@@ -376,6 +440,8 @@ class MedMoEPretrainingLightningModule(_Base):
 
     def on_validation_epoch_start(self):
         """Empty the bank; with model.retrieval.zero_shot, embed the class prompts under the weights this epoch validates on."""
+        if self._gbank is not None:
+            self._gbank.reset()
         if self._retrieval is None:
             return
         if self._bank is not None:
@@ -400,8 +466,9 @@ class MedMoEPretrainingLightningModule(_Base):
 
     def on_validation_epoch_end(self):
         """The epoch's retrieval (and zero-shot) metrics as plain floats; the trainer files them under val/... or test/...."""
+        ground = self._ground_metrics()
         if self._retrieval is None or self._bank is None:
-            return None
+            return ground or None
         from medmoe_amd.retrieval import retrieval_metrics, zero_shot_metrics
         loc = dict(local=self._lbank, local_k=self._retrieval["local_k"], local_agg=self._retrieval["local_agg"]) if self._lbank is not None else {}
         out = {k: float(v) for k, v in retrieval_metrics(self._bank, self._retrieval["ks"], **loc).items()}
@@ -414,6 +481,7 @@ class MedMoEPretrainingLightningModule(_Base):
                     out.update({f"{k}/{names[c]}": float(x) for c, x in enumerate(v.tolist())})
                 else:
                     out[k] = float(v)
+        out.update(ground)
         return out
 
     def on_test_epoch_start(self):
