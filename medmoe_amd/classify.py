@@ -2,9 +2,9 @@
 (medmoe_amd.ops.cls_head_step, csrc/classify.hip), the linear probe on a bank of frozen features, and accuracy / AUROC over a growing
 bank of logits.
 
-The head's parameters are a `FlatStore` like every other trained arena, so the clip norm, the fused Adam launch, zero_grad and the
-Adam-state export are the arena code that already exists.  The head itself is fp32 throughout: the kernels read the fp32 master, the
-bf16 working copy the arena keeps is not used.
+The head's parameters are a `FlatStore` like every other trained arena (head.LinearHead, shared with the segmentation head), so the clip
+norm, the fused Adam launch, zero_grad and the Adam-state export are the arena code that already exists.  The head itself is fp32
+throughout: the kernels read the fp32 master, the bf16 working copy the arena keeps is not used.
 
 Initialisation.  The head starts at ZERO (init="zeros"): the first loss is then exactly ln C (multiclass) or ln 2 (multilabel) whatever
 the features are, and because dx = dz W the tower's first gradient under fine-tuning is exactly zero - the first step moves the head
@@ -14,7 +14,7 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from . import ops
-from .flat import FlatStore
+from .head import LinearHead
 
 TASKS = ("multiclass", "multilabel")
 WEIGHT, BIAS = "classifier.weight", "classifier.bias"
@@ -41,65 +41,28 @@ def targets_as_int8(targets: torch.Tensor, task: str, num_classes: int) -> torch
     return out.contiguous()
 
 
-class ClassifierHead:
+class ClassifierHead(LinearHead):
+    WEIGHT, BIAS, MAX_D, MAX_CLASSES = WEIGHT, BIAS, ops.CLS_MAX_D, ops.CLS_MAX_CLASSES
+
     def __init__(self, d: int, num_classes: int, device, task: str = "multiclass", label_smoothing: float = 0.0,
                  pos_weight: Optional[torch.Tensor] = None, init: str = "zeros", std: float = 0.01, seed: int = 0):
         if task not in TASKS:
             raise ValueError(f"ClassifierHead: task must be one of {TASKS}, got {task!r}")
-        if d % 64 or not 64 <= d <= ops.CLS_MAX_D:
-            raise ValueError(f"ClassifierHead: d must be a multiple of 64 in 64 .. {ops.CLS_MAX_D}, got {d}")
-        if not 1 <= int(num_classes) <= ops.CLS_MAX_CLASSES:
-            raise ValueError(f"ClassifierHead: 1 <= num_classes <= {ops.CLS_MAX_CLASSES}, got {num_classes}")
         if not 0.0 <= float(label_smoothing) < 1.0 or (task == "multilabel" and float(label_smoothing) != 0.0):
             raise ValueError("ClassifierHead: label_smoothing must be in [0, 1) and is defined for the multiclass task only")
         if pos_weight is not None and task != "multilabel":
             raise ValueError("ClassifierHead: pos_weight is defined for the multilabel task only")
-        if init not in ("zeros", "normal"):
-            raise ValueError(f"ClassifierHead: init must be 'zeros' or 'normal', got {init!r}")
-        self.d, self.C, self.task, self.device = int(d), int(num_classes), task, torch.device(device)
-        self.label_smoothing = float(label_smoothing)
-        w = torch.zeros(self.C, self.d)
-        if init == "normal":
-            w = torch.randn(self.C, self.d, generator=torch.Generator().manual_seed(int(seed))) * float(std)
-        self.store = FlatStore({WEIGHT: w, BIAS: torch.zeros(self.C)}, self.device)
-        self.pos_weight = None
-        if pos_weight is not None:
-            pw = torch.as_tensor(pos_weight, dtype=torch.float32).reshape(-1)
-            if pw.numel() != self.C:
-                raise ValueError(f"ClassifierHead: pos_weight must hold {self.C} values, got {pw.numel()}")
-            self.pos_weight = pw.to(self.device).contiguous()
-        self._ws: Dict[str, torch.Tensor] = {}                       # z / loss / counts / scratch of the last batch size, allocated on first use
-        self._n = 0
-
-    # -- parameters ------------------------------------------------------------------------------------------------------------------------
-    @property
-    def weight(self) -> torch.Tensor:
-        return self.store.f32(WEIGHT)
-
-    @property
-    def bias(self) -> torch.Tensor:
-        return self.store.f32(BIAS)
-
-    def state_dict(self) -> Dict[str, torch.Tensor]:
-        return {WEIGHT: self.weight.detach().clone(), BIAS: self.bias.detach().clone()}
-
-    def load_state_dict(self, state: Dict[str, torch.Tensor]):
-        for name, view in ((WEIGHT, self.weight), (BIAS, self.bias)):
-            if name not in state:
-                raise KeyError(f"ClassifierHead.load_state_dict: {name} is missing")
-            if tuple(state[name].shape) != tuple(view.shape):
-                raise ValueError(f"ClassifierHead.load_state_dict: {name} has shape {tuple(state[name].shape)}, this head {tuple(view.shape)}")
-            view.copy_(state[name].to(self.device, torch.float32))
-        self.store.refresh()
+        super().__init__(d, num_classes, device, pos_weight, init, std, seed)
+        self.task, self.label_smoothing = task, float(label_smoothing)
 
     # -- launches --------------------------------------------------------------------------------------------------------------------------
     def _buffers(self, N: int) -> Dict[str, torch.Tensor]:
-        if N != self._n:
+        if N != self._key:
             dev, f32 = self.device, torch.float32
             self._ws = {"z": torch.empty((N, self.C), device=dev, dtype=f32), "loss": torch.zeros(1, device=dev, dtype=f32),
                         "counts": torch.zeros(2, device=dev, dtype=torch.int32),
                         "scratch": torch.empty(ops.cls_head_scratch(N, self.d, self.C), device=dev, dtype=f32)}
-            self._n = N
+            self._key = N
         return self._ws
 
     def logits(self, feat: torch.Tensor) -> torch.Tensor:
@@ -127,15 +90,6 @@ class ClassifierHead:
                           pos_weight=self.pos_weight, loss_scale=loss_scale, z=ws["z"], dx=dfeat, loss=ws["loss"], counts=ws["counts"],
                           scratch=ws["scratch"])
         return ws["loss"][0], ws["counts"][0], ws["counts"][1]
-
-    @property
-    def last_logits(self) -> torch.Tensor:
-        return self._ws["z"]
-
-    def adam_step(self, lr: float, weight_decay: float = 0.0, clip: float = 0.0, normsq_total: Optional[torch.Tensor] = None, **kw):
-        """The arena's fused clip + Adam launch on the head; normsq_total None: the head's own gradient norm."""
-        total = self.store.sumsq() if normsq_total is None else normsq_total
-        self.store.adam_step(total, lr, weight_decay, clip, **kw)
 
 
 class ScoreBank:

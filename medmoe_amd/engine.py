@@ -12,7 +12,7 @@ model_step (medmoe_module.py:284-316) -> GLORIA local/global losses (losses.py:7
 import collections
 import contextlib
 import os
-from typing import Dict, Optional
+from typing import Callable, Dict, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -197,6 +197,38 @@ def vit_activation_plan(cfg: MedMoEConfig, B: int, mode: str) -> Dict[str, tuple
 def plan_bytes(plan: Dict[str, tuple]) -> int:
     """Total bytes of a buffer plan (vit_activation_plan)."""
     return sum(int(np.prod(shape)) * {BF: 2, F32: 4}[dt] for shape, dt in plan.values())
+
+
+class HeadSpec(NamedTuple):
+    """What Engine._head_step / _head_eval need to know of a supervised task (one constant per task below): where the head reads its
+    features, which workspace gradient it writes and which stays zero, the batch key of its targets, how its output tuple becomes the
+    result dict, and the words of the refusals."""
+    feat: str                       # ws key of the features the head reads
+    d_written: str                  # ws key of the gradient the head writes under fine-tuning ...
+    d_zeroed: str                   # ... and of the one that is zeroed: backward(None) reads both
+    target: str                     # batch key of the targets
+    result: Callable                # the head's output tuple -> the dict a step returns (device tensors)
+    step: str                       # the public methods' names, the task's, its DESIGN section and what an all-reduce would have to carry
+    eval: str
+    task: str
+    design: str
+    unreduced: str
+
+
+def _classify_result(out):
+    loss, n_valid, n_correct = out
+    return {"loss": loss, "n_valid": n_valid, "n_correct": n_correct, "acc": n_correct.float() / n_valid.clamp(min=1).float()}
+
+
+def _segment_result(out):
+    loss, counts = out
+    return {"loss": loss, "counts": counts, "n_valid": counts[:, 0].sum()}
+
+
+CLASSIFY = HeadSpec("img_g", "d_img_g", "d_img_l", "label", _classify_result, "classify_step", "classify_eval", "classification", "3p",
+                    "the head's gradient has")
+SEGMENT = HeadSpec("img_l", "d_img_l", "d_img_g", "mask", _segment_result, "segment_step", "segment_eval", "segmentation", "3t",
+                   "the head's gradient and the batch-Dice sums have")
 
 
 class Engine:
@@ -1555,8 +1587,7 @@ class Engine:
                 out["loss"] = out["loss"] + self.cfg.mlm_weight * out["mlm_loss"]
             return out
         finally:
-            self.vit_drop_scales = None                             # whatever runs next (evaluation, a bare forward_image) drops nothing
-            self._vit_lora_drop_step = None
+            self._end_training_pass()
             self._mlm_pass = None
 
     def _mlm_result(self, weight: float):
@@ -1570,17 +1601,15 @@ class Engine:
         an evaluation (no dropout) on the masked ids and the head; no gradient, Adam moment, master or working parameter is written."""
         if self.mlm is None:
             raise RuntimeError("mlm_eval: this engine has no MLM head (cfg.text_mlm)")
-        if ema and not self._ema_active:
-            with self.ema_weights():
-                return self.mlm_eval(batch, step)
-        self._alloc(batch["ids"].shape[0])
-        self.prefetch_cap_lens(batch["ids"])
-        self._mlm_pass = (int(step), 1.0)
-        try:
-            self.forward_text(batch["ids"], batch["attn_mask"], batch.get("token_type"))
-            return self._mlm_result(1.0)
-        finally:
-            self._mlm_pass = None
+        with self._weights(ema):
+            self._alloc(batch["ids"].shape[0])
+            self.prefetch_cap_lens(batch["ids"])
+            self._mlm_pass = (int(step), 1.0)
+            try:
+                self.forward_text(batch["ids"], batch["attn_mask"], batch.get("token_type"))
+                return self._mlm_result(1.0)
+            finally:
+                self._mlm_pass = None
 
     def _forward_image_train(self, images: torch.Tensor):
         """forward_image of a training step: with cfg.vit_drop_path > 0 under the stochastic-depth scales of self.dropout_step, drawn here by
@@ -1594,6 +1623,12 @@ class Engine:
         if self.vlora is not None and c.vit_lora_dropout > 0.0:     # the adapters' masks of this step, for the forward and the backward
             self._vit_lora_drop_step = self.dropout_step
         self.forward_image(images)
+
+    def _end_training_pass(self):
+        """Whatever runs after a training pass (evaluation, a bare forward_image) drops nothing: in the `finally` of every step that ran
+        _forward_image_train."""
+        self.vit_drop_scales = None
+        self._vit_lora_drop_step = None
 
     def _train_step_rest(self, batch: Dict[str, torch.Tensor], optimizer: bool, loss_scale: float):
         """train_step from the losses on: backward, gradient exchange, optimiser."""
@@ -1650,16 +1685,28 @@ class Engine:
         lr = c.lr if lr is None else lr
         mlm = self.mlm.store if self.mlm is not None else None
         side = [a for a in (text, self.vlora, mlm) if a is not None]     # the arenas next to the image one: ONE clip norm over all of them
-        parts = [a.sumsq() for a in side]
-        total = image.sumsq()
-        for part in parts:
-            total.add_(part)
+        total = self._clip_total([image] + side)
         step, kw = fused_step_of(c)                                 # adam_step, or lamb_step (cfg.optimizer = "lamb")
         if c.ema_decay > 0.0:                                       # the same launches in their _ema form: every arena, the same decay arguments
             ema_.prepare([image] + side)
             kw.update(ema_.step_kwargs(c))
         for a in [image] + side:
             getattr(a, step)(total, lr, c.weight_decay, c.clip, **kw)
+
+    @staticmethod
+    def _clip_total(arenas):
+        """The squared gradient norm over `arenas` (the image arena first): a device scalar, the image arena's own sumsq() buffer.  The
+        others' partials are launched first and then added in list order - fp32 addition is not associative, so that order decides the
+        bits of the clip factor."""
+        parts = [a.sumsq() for a in arenas[1:]]
+        total = arenas[0].sumsq()
+        for part in parts:
+            total.add_(part)
+        return total
+
+    def _weights(self, ema: bool):
+        """The context of a forward-only method's body: ema_weights() for ema=True (unless the caller is already inside it), else nothing."""
+        return self.ema_weights() if ema and not self._ema_active else contextlib.nullcontext()
 
     # ------------------------------------------------------------------------------------------
     # evaluation (medmoe_module.py:114-134 validation_step / test_step: model_step without a backward)
@@ -1671,59 +1718,102 @@ class Engine:
         only evaluates never allocates the ragged pair matrices; other geometries run the forward launches of the generic formulation.
         The router's cross-entropy and accuracy come from medmoe_router_eval.  Always eager (no hipGraph replay).
         ema=True: this one evaluation runs on the averaged weights (inside ema_weights())."""
-        if ema and not self._ema_active:
-            with self.ema_weights():
-                return self.eval_step(batch)
-        c = self.cfg
-        B = batch["image"].shape[0]
-        self._alloc(B)
-        self.prefetch_cap_lens(batch["ids"])
-        self._forward_both(batch)
-        self.global_loss(grad=False)
-        self._local_loss_eval()
-        ops.call("router_eval", self.ws["probs"], batch["label"].to(I32).contiguous(), self.ws["loss_parts"], B, c.n_expert)
-        return self._step_result(None)
+        with self._weights(ema):
+            B = batch["image"].shape[0]
+            self._alloc(B)
+            self.prefetch_cap_lens(batch["ids"])
+            self._forward_both(batch)
+            self.global_loss(grad=False)
+            self._local_loss_eval()
+            ops.call("router_eval", self.ws["probs"], batch["label"].to(I32).contiguous(), self.ws["loss_parts"], B, self.cfg.n_expert)
+            return self._step_result(None)
 
     # -- embeddings without a loss (retrieval and zero-shot evaluation, DESIGN 3o) ---------------------------------------------------------
     def embed(self, batch: Dict[str, torch.Tensor], ema: bool = False):
         """(img_g, txt_g): the global image and sentence embeddings of a batch, fp32 [B, d_out] VIEWS of ws["img_g"] / ws["txt_g"], valid until
         the next engine call.  The forward launches of `eval_step` and nothing after them: no loss, and no parameter, gradient, Adam or EMA
         buffer is written.  ema=True: on the averaged weights (inside ema_weights()), as eval_step(ema=True)."""
-        if ema and not self._ema_active:
-            with self.ema_weights():
-                return self.embed(batch)
-        self._alloc(batch["image"].shape[0])
-        self.prefetch_cap_lens(batch["ids"])
-        self._forward_both(batch)
-        return self.ws["img_g"], self.ws["txt_g"]
+        with self._weights(ema):
+            self._alloc(batch["image"].shape[0])
+            self.prefetch_cap_lens(batch["ids"])
+            self._forward_both(batch)
+            return self.ws["img_g"], self.ws["txt_g"]
 
     def embed_image(self, images: torch.Tensor, ema: bool = False):
         """The image half of `embed` alone: fp32 [B, d_out] view of ws["img_g"], valid until the next engine call."""
-        if ema and not self._ema_active:
-            with self.ema_weights():
-                return self.embed_image(images)
-        self.forward_image(images)
-        return self.ws["img_g"]
+        with self._weights(ema):
+            self.forward_image(images)
+            return self.ws["img_g"]
 
     def embed_text(self, ids: torch.Tensor, attn_mask: torch.Tensor, token_type: Optional[torch.Tensor] = None, ema: bool = False):
         """The text half of `embed` alone - needs no image pass before it (a set of class prompts has none): fp32 [B, d_out] view of
         ws["txt_g"], valid until the next engine call."""
-        if ema and not self._ema_active:
-            with self.ema_weights():
-                return self.embed_text(ids, attn_mask, token_type)
-        self._alloc(ids.shape[0])
-        self.prefetch_cap_lens(ids)
-        self.forward_text(ids, attn_mask, token_type)
-        return self.ws["txt_g"]
+        with self._weights(ema):
+            self._alloc(ids.shape[0])
+            self.prefetch_cap_lens(ids)
+            self.forward_text(ids, attn_mask, token_type)
+            return self.ws["txt_g"]
 
-    # -- supervised classification on the global image embedding (DESIGN 3p) -------------------------------------------------------------
-    def _classify_refuse(self, train_tower: bool):
+    # -- supervised heads on the image features: classification on the global embedding (DESIGN 3p), segmentation on the regions (3t) ------
+    def _head_refuse(self, spec: HeadSpec, train_tower: Optional[bool]):
+        """What the head steps are not built for; train_tower None: an evaluation."""
         if self.dist:
-            raise NotImplementedError("classify_step / classify_eval under data parallelism (self.dist: WORLD_SIZE > 1, trainer.devices > 1): the "
-                                      "head's gradient has no all-reduce yet - data-parallel classification is a named follow-up (DESIGN 3p)")
+            raise NotImplementedError(f"{spec.step} / {spec.eval} under data parallelism (self.dist: WORLD_SIZE > 1, trainer.devices > 1): "
+                                      f"{spec.unreduced} no all-reduce yet - data-parallel {spec.task} is a named follow-up (DESIGN {spec.design})")
         if train_tower and self.cfg.ema_decay > 0.0:
-            raise NotImplementedError("classify_step(train_tower=True) with cfg.ema_decay > 0 (model.ema.decay): the head keeps no average, so "
-                                      "the towers' averages would pair with an un-averaged head - EMA of the head is a named follow-up (DESIGN 3p)")
+            raise NotImplementedError(f"{spec.step}(train_tower=True) with cfg.ema_decay > 0 (model.ema.decay): the head keeps no average, so the "
+                                      f"towers' averages would pair with an un-averaged head - EMA of the head is a named follow-up (DESIGN {spec.design})")
+        if train_tower is not None and self.cfg.optimizer == "lamb":
+            raise NotImplementedError(f"{spec.step} with cfg.optimizer = 'lamb' (model.optimizer._target_: src.optim.Lamb): the head's fused step "
+                                      f"carries its own Adam - LAMB for the {spec.task} head is a named follow-up (DESIGN 3s)")
+
+    def _head_step(self, batch: Dict[str, torch.Tensor], head, spec: HeadSpec, train_tower: bool, optimizer: bool, zero_grad: bool,
+                   loss_scale: float, head_lr: Optional[float]):
+        """One supervised step of `head` (a head.LinearHead) on ws[spec.feat] of batch["image"] against batch[spec.target]: what
+        classify_step and segment_step document."""
+        self._head_refuse(spec, train_tower)
+        if self._ema_active:
+            raise RuntimeError(f"{spec.step} inside ema_weights(): the working copies hold the averaged weights - evaluate only")
+        c, images = self.cfg, batch["image"]
+        self._alloc(images.shape[0])
+        ws = self.ws
+        lr = c.lr if head_lr is None else float(head_lr)
+        kw = dict(betas=tuple(c.adam_betas), eps=c.adam_eps, decoupled=c.optimizer == "adamw")
+        if not train_tower:
+            self.forward_image(images)
+            if zero_grad:
+                head.store.zero_grad()
+            out = head.step(ws[spec.feat], batch[spec.target], loss_scale)
+            if optimizer:
+                head.adam_step(lr, c.weight_decay, c.clip, **kw)
+            return spec.result(out)
+        towers = [self.params] + ([self.vlora] if self.vlora is not None else [])
+        if zero_grad:
+            for a in towers:
+                a.zero_grad()
+            head.store.zero_grad()
+        try:
+            self._forward_image_train(images)
+            out = head.step(ws[spec.feat], batch[spec.target], loss_scale, dfeat=ws[spec.d_written])
+            ws[spec.d_zeroed].zero_()
+            self.backward(None, loss_scale)
+        finally:
+            self._end_training_pass()
+        self.dropout_step += 1
+        if optimizer:
+            total = self._clip_total(towers + [head.store])
+            for a in towers:
+                a.adam_step(total, c.lr, c.weight_decay, c.clip, **kw)
+            head.adam_step(lr, c.weight_decay, c.clip, normsq_total=total, **kw)
+        return spec.result(out)
+
+    def _head_eval(self, batch: Dict[str, torch.Tensor], head, spec: HeadSpec, ema: bool):
+        """(logits, loss dict) of `head` on a batch, forward only: what classify_eval and segment_eval document."""
+        self._head_refuse(spec, None)
+        with self._weights(ema):
+            self.forward_image(batch["image"])
+            out = head.evaluate(self.ws[spec.feat], batch[spec.target])
+            return head.last_logits, spec.result(out)
 
     def classify_step(self, batch: Dict[str, torch.Tensor], head, train_tower: bool, optimizer: bool = True, zero_grad: bool = True,
                       loss_scale: float = 1.0, head_lr: Optional[float] = None):
@@ -1738,76 +1828,14 @@ class Engine:
         adapters and the head, then Adam on each, the head at head_lr (default cfg.lr); dropout_step advances.
         Gradient accumulation as in train_step: optimizer=False for all but the last micro-batch, zero_grad=False for all but the first,
         loss_scale = 1 / number of micro-batches.  Always eager.  Returns device scalars: loss, n_valid, n_correct, acc."""
-        self._classify_refuse(train_tower)
-        if self.cfg.optimizer == "lamb":
-            raise NotImplementedError("classify_step with cfg.optimizer = 'lamb' (model.optimizer._target_: src.optim.Lamb): the head's fused "
-                                      "step carries its own Adam - LAMB for the classification head is a named follow-up (DESIGN 3s)")
-        if self._ema_active:
-            raise RuntimeError("classify_step inside ema_weights(): the working copies hold the averaged weights - evaluate only")
-        c, images = self.cfg, batch["image"]
-        self._alloc(images.shape[0])
-        ws = self.ws
-        lr = c.lr if head_lr is None else float(head_lr)
-        kw = dict(betas=tuple(c.adam_betas), eps=c.adam_eps, decoupled=c.optimizer == "adamw")
-        if not train_tower:
-            self.forward_image(images)
-            if zero_grad:
-                head.store.zero_grad()
-            out = head.step(ws["img_g"], batch["label"], loss_scale)
-            if optimizer:
-                head.adam_step(lr, c.weight_decay, c.clip, **kw)
-            return self._classify_result(out)
-        towers = [self.params] + ([self.vlora] if self.vlora is not None else [])
-        if zero_grad:
-            for a in towers:
-                a.zero_grad()
-            head.store.zero_grad()
-        try:
-            self._forward_image_train(images)
-            out = head.step(ws["img_g"], batch["label"], loss_scale, dfeat=ws["d_img_g"])
-            ws["d_img_l"].zero_()
-            self.backward(None, loss_scale)
-        finally:
-            self.vit_drop_scales = None
-            self._vit_lora_drop_step = None
-        self.dropout_step += 1
-        if optimizer:
-            parts = [a.sumsq() for a in towers[1:] + [head.store]]
-            total = self.params.sumsq()
-            for part in parts:
-                total.add_(part)
-            for a in towers:
-                a.adam_step(total, c.lr, c.weight_decay, c.clip, **kw)
-            head.adam_step(lr, c.weight_decay, c.clip, normsq_total=total, **kw)
-        return self._classify_result(out)
-
-    @staticmethod
-    def _classify_result(out):
-        loss, n_valid, n_correct = out
-        return {"loss": loss, "n_valid": n_valid, "n_correct": n_correct, "acc": n_correct.float() / n_valid.clamp(min=1).float()}
+        return self._head_step(batch, head, CLASSIFY, train_tower, optimizer, zero_grad, loss_scale, head_lr)
 
     def classify_eval(self, batch: Dict[str, torch.Tensor], head, ema: bool = False):
         """(logits, loss dict) of `head` on a batch, forward only: the evaluation form of the image pass, then the head launch with
         loss_scale 1 into gradient buffers of its own that nobody reads (ClassifierHead.evaluate) - no parameter, gradient or optimiser
         state of the engine or the head is written.  logits: fp32 [B, C] view of the head's workspace, valid until its next launch.
         ema=True: the image pass runs on the averaged weights (inside ema_weights()); the head keeps no average."""
-        self._classify_refuse(False)
-        if ema and not self._ema_active:
-            with self.ema_weights():
-                return self.classify_eval(batch, head)
-        self.forward_image(batch["image"])
-        out = head.evaluate(self.ws["img_g"], batch["label"])
-        return head.last_logits, self._classify_result(out)
-
-    # -- semantic segmentation on the region features (DESIGN 3t) ------------------------------------------------------------------------
-    def _segment_refuse(self, train_tower: bool):
-        if self.dist:
-            raise NotImplementedError("segment_step / segment_eval under data parallelism (self.dist: WORLD_SIZE > 1, trainer.devices > 1): the "
-                                      "head's gradient and the batch-Dice sums have no all-reduce yet - data-parallel segmentation is a named "
-                                      "follow-up (DESIGN 3t)")
-        if train_tower and self.cfg.ema_decay > 0.0:
-            raise NotImplementedError("segment_step(train_tower=True) with cfg.ema_decay > 0 (model.ema.decay): the head keeps no average, so "
-                                      "the towers' averages would pair with an un-averaged head - EMA of the head is a named follow-up (DESIGN 3t)")
+        return self._head_eval(batch, head, CLASSIFY, ema)
 
     def segment_step(self, batch: Dict[str, torch.Tensor], head, train_tower: bool, optimizer: bool = True, zero_grad: bool = True,
                      loss_scale: float = 1.0, head_lr: Optional[float] = None):
@@ -1825,66 +1853,14 @@ class Engine:
         loss_scale = 1 / number of micro-batches) reproduces the one-batch step only for a head with w_dice = 0: the Dice sums run over the
         micro-batch a call sees (batch Dice is not additive).  Always eager.  Returns device tensors: loss, counts int64 [C, 4] =
         (n_valid, TP, FP, FN), n_valid (their sum over the classes)."""
-        self._segment_refuse(train_tower)
-        if self.cfg.optimizer == "lamb":
-            raise NotImplementedError("segment_step with cfg.optimizer = 'lamb' (model.optimizer._target_: src.optim.Lamb): the head's fused "
-                                      "step carries its own Adam - LAMB for the segmentation head is a named follow-up (DESIGN 3t)")
-        if self._ema_active:
-            raise RuntimeError("segment_step inside ema_weights(): the working copies hold the averaged weights - evaluate only")
-        c, images = self.cfg, batch["image"]
-        self._alloc(images.shape[0])
-        ws = self.ws
-        lr = c.lr if head_lr is None else float(head_lr)
-        kw = dict(betas=tuple(c.adam_betas), eps=c.adam_eps, decoupled=c.optimizer == "adamw")
-        if not train_tower:
-            self.forward_image(images)
-            if zero_grad:
-                head.store.zero_grad()
-            out = head.step(ws["img_l"], batch["mask"], loss_scale)
-            if optimizer:
-                head.adam_step(lr, c.weight_decay, c.clip, **kw)
-            return self._segment_result(out)
-        towers = [self.params] + ([self.vlora] if self.vlora is not None else [])
-        if zero_grad:
-            for a in towers:
-                a.zero_grad()
-            head.store.zero_grad()
-        try:
-            self._forward_image_train(images)
-            out = head.step(ws["img_l"], batch["mask"], loss_scale, dfeat=ws["d_img_l"])
-            ws["d_img_g"].zero_()
-            self.backward(None, loss_scale)
-        finally:
-            self.vit_drop_scales = None
-            self._vit_lora_drop_step = None
-        self.dropout_step += 1
-        if optimizer:
-            parts = [a.sumsq() for a in towers[1:] + [head.store]]
-            total = self.params.sumsq()
-            for part in parts:
-                total.add_(part)
-            for a in towers:
-                a.adam_step(total, c.lr, c.weight_decay, c.clip, **kw)
-            head.adam_step(lr, c.weight_decay, c.clip, normsq_total=total, **kw)
-        return self._segment_result(out)
-
-    @staticmethod
-    def _segment_result(out):
-        loss, counts = out
-        return {"loss": loss, "counts": counts, "n_valid": counts[:, 0].sum()}
+        return self._head_step(batch, head, SEGMENT, train_tower, optimizer, zero_grad, loss_scale, head_lr)
 
     def segment_eval(self, batch: Dict[str, torch.Tensor], head, ema: bool = False):
         """(patch logits, loss dict) of `head` on a batch, forward only: the evaluation form of the image pass, the head's row pass and the
         stats half of its loss launch at loss_scale 1 - no parameter, gradient or optimiser state of the engine or the head is written.
         patch logits: fp32 [B, P, C] view of the head's workspace, valid until its next launch (head.predict / ops.seg_predict turn them
         into masks); dict["counts"] feeds a segment.SegBank.  ema=True: the image pass runs on the averaged weights; the head keeps no average."""
-        self._segment_refuse(False)
-        if ema and not self._ema_active:
-            with self.ema_weights():
-                return self.segment_eval(batch, head)
-        self.forward_image(batch["image"])
-        out = head.evaluate(self.ws["img_l"], batch["mask"])
-        return head.last_logits, self._segment_result(out)
+        return self._head_eval(batch, head, SEGMENT, ema)
 
     # -- phrase grounding: word-region heat maps scored against boxes (DESIGN 3u) ---------------------------------------------------------
     def _ground_refuse(self):
@@ -1902,11 +1878,9 @@ class Engine:
         "hf" fp32 [B, H, W].  No parameter, gradient, moment or EMA buffer is written.  ema=True: on the averaged weights.  More than one
         rank: every rank scores its own shard."""
         self._ground_refuse()
-        if ema and not self._ema_active:
-            with self.ema_weights():
-                return self.ground(batch, mode, thetas, size, False, want_map)
-        self.embed(batch)
-        return self.ground_workspace(batch, mode, thetas, size, want_map)
+        with self._weights(ema):
+            self.embed(batch)
+            return self.ground_workspace(batch, mode, thetas, size, want_map)
 
     def ground_workspace(self, batch: Dict[str, torch.Tensor], mode: str = "attention", thetas=(0.5,), size=None, want_map: bool = False,
                          span_key: str = "span", box_key: str = "box"):

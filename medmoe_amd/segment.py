@@ -3,8 +3,9 @@ independent sigmoids per class, its bilinear upsample to the mask size, BCE + ba
 launches of csrc/segment.hip (medmoe_amd.ops.seg_head_fwd / seg_loss / seg_head_bwd / seg_predict).  Nothing of the shape [B, C, H, W] is
 stored in fp32 and no fp32 atomic is used: two steps on the same inputs give the same bits.
 
-The head's parameters are a `FlatStore` like every other trained arena, so the clip norm, the fused Adam launch, zero_grad and the
-Adam-state export are the arena code that already exists.  The head is fp32 throughout: the kernels read the fp32 master.
+The head's parameters are a `FlatStore` like every other trained arena (head.LinearHead, shared with the classification head), so the clip
+norm, the fused Adam launch, zero_grad and the Adam-state export are the arena code that already exists.  The head is fp32 throughout: the
+kernels read the fp32 master.
 
 Initialisation.  The head starts at ZERO (init="zero"): every full-resolution logit is 0, so the first BCE is exactly ln 2 whatever the
 features are, and because dfeat = dz W the tower's first gradient under fine-tuning is exactly zero - the first step moves the head only.
@@ -17,7 +18,7 @@ from typing import Dict, Optional, Sequence, Tuple
 import torch
 
 from . import ops
-from .flat import FlatStore
+from .head import LinearHead
 
 WEIGHT, BIAS = "seg_head.weight", "seg_head.bias"
 
@@ -46,54 +47,17 @@ def prepare_masks(masks: torch.Tensor, num_classes: int) -> torch.Tensor:
     return out.clone() if out.data_ptr() % 16 else out                       # the launch reads 16 bytes at a time: a slice may start anywhere
 
 
-class SegmenterHead:
+class SegmenterHead(LinearHead):
+    WEIGHT, BIAS, MAX_D, MAX_CLASSES = WEIGHT, BIAS, ops.SEG_MAX_D, ops.SEG_MAX_CLASSES
+
     def __init__(self, d: int, num_classes: int, device, pos_weight: Optional[torch.Tensor] = None, w_bce: float = 1.0, w_dice: float = 1.0,
                  dice_eps: float = 1.0, init: str = "zero", std: float = 0.01, seed: int = 0):
-        if d % 64 or not 64 <= d <= ops.SEG_MAX_D:
-            raise ValueError(f"SegmenterHead: d must be a multiple of 64 in 64 .. {ops.SEG_MAX_D}, got {d}")
-        if not 1 <= int(num_classes) <= ops.SEG_MAX_CLASSES:
-            raise ValueError(f"SegmenterHead: 1 <= num_classes <= {ops.SEG_MAX_CLASSES}, got {num_classes}")
         if float(w_bce) < 0.0 or float(w_dice) < 0.0 or float(w_bce) + float(w_dice) <= 0.0:
             raise ValueError(f"SegmenterHead: w_bce and w_dice must be >= 0 and not both 0, got {w_bce}, {w_dice}")
         if not float(dice_eps) >= 0.0:
             raise ValueError(f"SegmenterHead: dice_eps must be >= 0, got {dice_eps}")
-        if init not in ("zero", "normal"):
-            raise ValueError(f"SegmenterHead: init must be 'zero' or 'normal', got {init!r}")
-        self.d, self.C, self.device = int(d), int(num_classes), torch.device(device)
+        super().__init__(d, num_classes, device, pos_weight, init, std, seed)
         self.w_bce, self.w_dice, self.dice_eps = float(w_bce), float(w_dice), float(dice_eps)
-        w = torch.zeros(self.C, self.d)
-        if init == "normal":
-            w = torch.randn(self.C, self.d, generator=torch.Generator().manual_seed(int(seed))) * float(std)
-        pw = None
-        if pos_weight is not None:
-            pw = torch.as_tensor(pos_weight, dtype=torch.float32).reshape(-1)
-            if pw.numel() != self.C:
-                raise ValueError(f"SegmenterHead: pos_weight must hold {self.C} values, got {pw.numel()}")
-        self.store = FlatStore({WEIGHT: w, BIAS: torch.zeros(self.C)}, self.device)
-        self.pos_weight = None if pw is None else pw.to(self.device).contiguous()
-        self._ws: Dict[str, torch.Tensor] = {}                       # z / dz / loss / counts / scratch of the last geometry, allocated on first use
-        self._key = None
-
-    # -- parameters ------------------------------------------------------------------------------------------------------------------------
-    @property
-    def weight(self) -> torch.Tensor:
-        return self.store.f32(WEIGHT)
-
-    @property
-    def bias(self) -> torch.Tensor:
-        return self.store.f32(BIAS)
-
-    def state_dict(self) -> Dict[str, torch.Tensor]:
-        return {WEIGHT: self.weight.detach().clone(), BIAS: self.bias.detach().clone()}
-
-    def load_state_dict(self, state: Dict[str, torch.Tensor]):
-        for name, view in ((WEIGHT, self.weight), (BIAS, self.bias)):
-            if name not in state:
-                raise KeyError(f"SegmenterHead.load_state_dict: {name} is missing")
-            if tuple(state[name].shape) != tuple(view.shape):
-                raise ValueError(f"SegmenterHead.load_state_dict: {name} has shape {tuple(state[name].shape)}, this head {tuple(view.shape)}")
-            view.copy_(state[name].to(self.device, torch.float32))
-        self.store.refresh()
 
     # -- launches --------------------------------------------------------------------------------------------------------------------------
     @staticmethod
@@ -153,15 +117,6 @@ class SegmenterHead:
         if grad:
             ops.seg_head_bwd(ws["dz"], x, self.weight, dW, db, dfeat=dfeat, scratch=ws["scratch"])
         return ws["loss"][0], ws["counts"]
-
-    @property
-    def last_logits(self) -> torch.Tensor:
-        return self._ws["z"]
-
-    def adam_step(self, lr: float, weight_decay: float = 0.0, clip: float = 0.0, normsq_total: Optional[torch.Tensor] = None, **kw):
-        """The arena's fused clip + Adam launch on the head; normsq_total None: the head's own gradient norm."""
-        total = self.store.sumsq() if normsq_total is None else normsq_total
-        self.store.adam_step(total, lr, weight_decay, clip, **kw)
 
 
 class SegBank:

@@ -139,6 +139,82 @@ def test_vit_lora_engine_finetunes_adapters_moe_and_head_only():
     assert not torch.equal(p.p32[tf:], tail) and not torch.equal(eng.vlora.p32, a0) and not torch.equal(head.weight, w0)
 
 
+def _finetune_and_its_hand_run(new_engine, task):
+    """One classify_step(train_tower=True, head_lr=0.01) on a deterministic engine, and on a second engine from `new_engine` the same step
+    launch by launch.  Per run: (engine, head, loss, clip total)."""
+    kw = {"label_smoothing": 0.1} if task == "multiclass" else {"pos_weight": torch.linspace(0.5, 2.0, C)}
+    runs = []
+    for hand in (False, True):
+        batch, eng = new_engine()
+        eng.set_deterministic(True)
+        head = _head(eng, task, **kw)
+        b = _cls_batch(batch, task)
+        eng._alloc(B)
+        eng.ws["d_img_g"].fill_(float("nan")); eng.ws["d_img_l"].fill_(float("nan"))
+        if not hand:
+            loss = eng.classify_step(b, head, train_tower=True, head_lr=0.01)["loss"].clone()
+        else:
+            c = eng.cfg
+            eng.params.zero_grad()
+            if eng.vlora is not None:
+                eng.vlora.zero_grad()
+            head.store.zero_grad()
+            eng._forward_image_train(b["image"])
+            loss = head.step(eng.ws["img_g"], b["label"], 1.0, dfeat=eng.ws["d_img_g"])[0].clone()
+            eng.ws["d_img_l"].zero_()
+            eng.backward(None, 1.0)
+            eng.dropout_step += 1
+            # the clip total: every other arena's sum of squares is launched before the image arena's, then added to it in the order
+            # image arena, adapters, head - fp32 addition does not commute in its last bit, so the order is part of the step
+            side = ([eng.vlora.sumsq()] if eng.vlora is not None else []) + [head.store.sumsq()]
+            total = eng.params.sumsq()
+            for part in side:
+                total.add_(part)
+            akw = dict(betas=tuple(c.adam_betas), eps=c.adam_eps, decoupled=c.optimizer == "adamw")
+            eng.params.adam_step(total, c.lr, c.weight_decay, c.clip, **akw)
+            if eng.vlora is not None:
+                eng.vlora.adam_step(total, c.lr, c.weight_decay, c.clip, **akw)
+            head.adam_step(0.01, c.weight_decay, c.clip, normsq_total=total, **akw)
+        torch.cuda.synchronize()
+        # the head wrote ALL of d_img_g (it was NaN) and d_img_l is zero
+        assert bool(torch.isfinite(eng.ws["d_img_g"].float()).all()) and float(eng.ws["d_img_g"].float().abs().max()) > 0
+        assert bool((eng.ws["d_img_l"] == 0).all())
+        assert float(eng.params.g32.abs().max()) > 0 and eng.dropout_step == 1
+        runs.append((eng, head, loss))
+    return runs
+
+
+def _step_record(eng, head, loss):
+    rec = [eng.params.p32, eng.params.g32, eng.params.m, head.store.p32, head.store.g32, loss]
+    if eng.vlora is not None:
+        rec += [eng.vlora.p32, eng.vlora.g32]
+    return [t.clone() for t in rec]
+
+
+@pytest.mark.parametrize("task", ["multiclass", "multilabel"])
+def test_finetune_is_the_hand_run_sequence_bit_for_bit(task):
+    def new_engine():
+        _, _, _, batch, eng = make("tiny2", B, seed=3)
+        return batch, eng
+    step, hand = _finetune_and_its_hand_run(new_engine, task)
+    for a, c in zip(_step_record(*step), _step_record(*hand)):
+        assert torch.equal(a, c)
+
+
+@pytest.mark.parametrize("task", ["multiclass", "multilabel"])
+def test_finetune_with_adapters_is_the_hand_run_sequence_bit_for_bit(task):
+    """The only test of the three-arena clip total (image arena + adapters + head).  The comparison is torch.equal throughout, the
+    adapters' parameters and gradients included: two independent classify_step runs of this engine in deterministic mode were measured
+    bit-identical in every one of these buffers (deterministic mode covers the adapters' backward), so no repeat bar is needed."""
+    def new_engine():
+        _, _, _, batch, eng, _ = make_v("tiny", B)
+        return batch, eng
+    step, hand = _finetune_and_its_hand_run(new_engine, task)
+    assert float(step[0].vlora.g32.abs().max()) > 0
+    for a, c in zip(_step_record(*step), _step_record(*hand)):
+        assert torch.equal(a, c)
+
+
 def test_deterministic_engines_agree_bit_for_bit():
     from medmoe_amd import ops
     runs = []
